@@ -5,9 +5,15 @@ One "step" = one pass of the hot path over one synthetic 8K document that is alr
     flatten 32 RGBA8 layers (all 25 blend modes, S2 of SURVEY.md §8d)  ->  Gaussian blur sigma=16 of the result.
 Both results are materialised (140 algorithmic bytes per output pixel).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  Everything else it can measure or check moves
+behind --full: the clock / power sample, the bit-exact f32 leg, the oracle checks of the timed result, the CPU baseline, the
+C-ABI group leg, the other BASELINE configurations, the live rocprofv3 counter passes and, for N > 1, the all-gathered
+variant, the per-rank phase probe and the one-document-per-GPU mode.  --dump-outputs DIR writes the last timed step's
+flatten and Gaussian results as float32 .npy files (a fixed, seeded pixel sample of frames larger than DUMP_MAX_PX).
 
 Multi-GPU (one process per GPU, torch.distributed over RCCL): the headline line is ONE 8K document cut into bands of whole
 chunk rows: every rank flattens its band, receives ceil(3 sigma) rows of the flattened neighbours' bands (RCCL
@@ -143,6 +149,26 @@ def clock_power_sample(torch, step_fn, dev_index, seconds=0.4):
                 "how": f"amdsmi gpu_metrics every 2 ms over {n_steps} back-to-back steps after the timed region ({(t1 - t0) / n_steps * 1e3:.4f} ms/step there)"}
     except Exception:
         return None
+
+
+DUMP_MAX_PX = 1 << 20     # pixels per dumped output: 2 outputs x 2^20 px x 4 channels x 4 bytes = 32 MB
+DUMP_SEED = 0x5EED00D0
+
+
+def dump_outputs(out_dir, outputs):
+    """`outputs`: name -> (h, w, 4) uint8 tensor.  Writes out_dir/<name>.npy as float32: the whole frame while it has at most DUMP_MAX_PX
+    pixels, otherwise the (DUMP_MAX_PX, 4) pixels at sorted positions drawn without replacement by numpy's default_rng(DUMP_SEED) —
+    the same positions for every output and every run of the same frame size."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outputs.items():
+        h, w = t.shape[0], t.shape[1]
+        if h * w <= DUMP_MAX_PX:
+            a = t.float().cpu().numpy()
+        else:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(h * w, size=DUMP_MAX_PX, replace=False))
+            a = t.reshape(h * w, 4).index_select(0, torch.from_numpy(idx).to(t.device)).float().cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def nan_to_none(x):
@@ -573,7 +599,15 @@ def main() -> int:
     ap.add_argument("--headline-only", action="store_true", help="skip the other BASELINE configurations (development runs)")
     ap.add_argument("--tune", action="append", default=[], help="key=value kernel tuning knob (development)")
     ap.add_argument("--exact", action="store_true", help="Gaussian without FMA contraction (bit-exact with the CPU path)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every other leg: clock / power sample, bit-exact f32 leg, oracle checks, CPU baseline, C-ABI group leg, other BASELINE "
+                         "configurations, live counter passes; N > 1 adds the all-gathered variant, phase probe and doc_mode (the --no-* / --headline-only "
+                         "options thin this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's results (flatten.npy, gaussian.npy; float32) to DIR; single-GPU headline only")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus != 1 or args.config != "headline"):
+        ap.error("--dump-outputs covers the single-GPU headline (--gpus 1, --config headline)")
 
     import torch
     import torch.distributed as dist
@@ -715,7 +749,7 @@ def main() -> int:
         except Exception as e:  # noqa: BLE001 — reported on the line, the process still exits non-zero
             state["band_error"] = f"{type(e).__name__}: {e}"[:500]
             elapsed, kern, flat_view = float("nan"), {}, None
-        if not args.no_gather and not state.get("band_error"):
+        if args.full and not args.no_gather and not state.get("band_error"):
             try:
                 pipe.gather = True
                 g_el, _ = timed(step)
@@ -728,7 +762,7 @@ def main() -> int:
             except Exception as e:  # noqa: BLE001
                 state["gather_error"] = f"{type(e).__name__}: {e}"[:500]
         # per-rank phase clocks of one unpipelined step (flatten / halo exchange / filter / gather): where a rank's time goes on real links
-        if not state.get("band_error"):
+        if args.full and not state.get("band_error"):
             try:
                 pipe.gather = not args.no_gather and not state.get("gather_error")
                 ph = pipe.phase_probe(ptrs, info)
@@ -739,21 +773,22 @@ def main() -> int:
             except Exception as e:  # noqa: BLE001 — diagnostics only
                 state["phase_probe_error"] = f"{type(e).__name__}: {e}"[:300]
         # the collective-free mode in the same run (one independent 8K document per rank), reported beside the headline
-        del stack
-        torch.cuda.empty_cache()
-        dstack, _, _ = synth_stack(torch, device, w, h, n, seed=0x5EED0002 + 1000 * rank)
-        dflat = torch.empty((h, w, 4), dtype=torch.uint8, device=device)
-        dblur = torch.empty((h, w, 4), dtype=torch.uint8, device=device)
-        dptrs = [dstack[k].data_ptr() for k in range(n)]
+        if args.full:
+            del stack
+            torch.cuda.empty_cache()
+            dstack, _, _ = synth_stack(torch, device, w, h, n, seed=0x5EED0002 + 1000 * rank)
+            dflat = torch.empty((h, w, 4), dtype=torch.uint8, device=device)
+            dblur = torch.empty((h, w, 4), dtype=torch.uint8, device=device)
+            dptrs = [dstack[k].data_ptr() for k in range(n)]
 
-        def doc_step():
-            r.flatten_dev(dptrs, info, w, h, dflat.data_ptr())
-            r.gaussian_blur_dev(dflat.data_ptr(), dblur.data_ptr(), w, h, args.sigma)
+            def doc_step():
+                r.flatten_dev(dptrs, info, w, h, dflat.data_ptr())
+                r.gaussian_blur_dev(dflat.data_ptr(), dblur.data_ptr(), w, h, args.sigma)
 
-        d_el, _ = timed(doc_step)
-        doc_mode = {"value": round(w * h * args.steps * world / d_el / 1e6, 1), "unit": "Mpixels/s", "scaling": "weak",
-                    "ms_per_step": round(d_el / args.steps * 1e3, 4), "sharding": "one independent document per GPU, no collective"}
-        del dstack
+            d_el, _ = timed(doc_step)
+            doc_mode = {"value": round(w * h * args.steps * world / d_el / 1e6, 1), "unit": "Mpixels/s", "scaling": "weak",
+                        "ms_per_step": round(d_el / args.steps * 1e3, 4), "sharding": "one independent document per GPU, no collective"}
+            del dstack
     else:
         stack, modes, opac = synth_stack(torch, device, w, h, n, seed=0x5EED0002 + 1000 * rank)
         info = [(k, float(opac[k]), True, int(modes[k])) for k in range(n)]
@@ -768,9 +803,11 @@ def main() -> int:
 
         elapsed, kern = timed(step)
         flat_view = flat
-        if world == 1:
+        if args.dump_outputs:   # before any later leg reuses these buffers
+            dump_outputs(args.dump_outputs, {"flatten": flat, "gaussian": blurred})
+        if args.full and world == 1:
             state["clock_power"] = clock_power_sample(torch, step, dev_index)
-        if world == 1 and not args.exact:
+        if args.full and world == 1 and not args.exact:
             # the strict-f32 pipeline beside the default one: the same step with the Gaussian in the bit-exact mode (f32 taps, one rounding per
             # operation, no matrix cores), timed the same way into its own result buffer and checked whole-frame at tolerance 0 where the default leg is checked
             blurred_x = torch.empty((h, w, 4), dtype=torch.uint8, device=device)
@@ -898,7 +935,7 @@ def main() -> int:
         from tests import oracle_lib as O
         ch, cw = 256, 512
         cy, cx = min(1000, max(hh - ch, 0)), min(2000, max(w - cw, 0))
-        if not band_mode and hh >= cy + ch and w >= cx + cw:
+        if args.full and not band_mode and hh >= cy + ch and w >= cx + cw:
             crop_stack = stack[:, cy:cy + ch, cx:cx + cw, :].contiguous().cpu().numpy()
             ref = O.flatten_stack(crop_stack, modes, opac)
             got = flat_view[cy:cy + ch, cx:cx + cw, :].contiguous().cpu().numpy()
@@ -907,7 +944,7 @@ def main() -> int:
             if not ok:
                 out["check"]["mismatching_px"] = int((ref != got).any(-1).sum())
                 failed.append("flatten_crop_bitexact")
-        if band_mode and hh > 0 and not state.get("band_error"):
+        if args.full and band_mode and hh > 0 and not state.get("band_error"):
             # rank 0 rebuilds a window around its band from the shared seeds and runs the single-process oracle pipeline on it
             lo, hi = max(y0 - 2 * radius, 0), min(y1 + 2 * radius, h)
             if (hi - lo) * w <= (1 << 25):
@@ -932,7 +969,7 @@ def main() -> int:
                         failed.append("gathered_window_max_diff_vs_oracle")
                 state["ref_window"] = (lo + a0, lo + a1, ref_blur[a0:a1])
 
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # bounded sample of the same workload: the whole frame of the same stack while that stays a few seconds on the
             # host cores (the 8K x 32 default: ~2 s on 16 cores), otherwise a 3840x2160 window of it
             whole = n * w * h * 4 <= (6 << 30)
@@ -989,7 +1026,7 @@ def main() -> int:
                 out["value_exact_f32"] = None
                 failed.append("exact_f32_leg_gaussian_window_bitexact")
         state.pop("exact_leg", None)
-        if not args.no_group and (world == 1 or band_mode):
+        if args.full and not args.no_group and (world == 1 or band_mode):
             # the C-ABI multi-GPU path (one process, every device), beside the torch.distributed headline; the other ranks wait on the host (host_pg)
             devices = list(range(world)) if (world > 1 and backend == "nccl") else [dev_index] * world
             try:
@@ -1014,7 +1051,7 @@ def main() -> int:
                 del img
             except Exception as e:  # noqa: BLE001 — a secondary leg: reported, never fatal to the headline
                 out["c_abi_group"] = {"error": f"{type(e).__name__}: {e}"[:400]}
-        if world == 1 and not band_mode and not args.headline_only and (w, h) == (W8K, H8K):
+        if args.full and world == 1 and not band_mode and not args.headline_only and (w, h) == (W8K, H8K):
             del stack
             torch.cuda.empty_cache()
             cfgs, cfg_failed = other_configs(args, torch, r, device, O, flat, blurred)
@@ -1022,7 +1059,7 @@ def main() -> int:
             failed += cfg_failed
         # LAST, with nothing else on the device: the dominant kernel's HBM traffic from this box's counters (the other counter fields stay static: they need
         # SQ passes whose collection slows the kernels down)
-        if world == 1 and not band_mode and not args.no_live_pmc and dominant == "flatten" and not args.tune:
+        if args.full and world == 1 and not band_mode and not args.no_live_pmc and dominant == "flatten" and not args.tune:
             torch.cuda.synchronize()
             live, why = live_traffic(args)
             rf = out.get("roofline") or {}

@@ -17,7 +17,7 @@ def _run(nproc, extra, port, height=400):
     env = dict(os.environ, PFX_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "3", "--warmup", "1",
-           "--width", "640", "--height", str(height), "--layers", "6", "--sigma", "3.0", "--no-cpu-baseline"] + extra
+           "--width", "640", "--height", str(height), "--layers", "6", "--sigma", "3.0", "--no-cpu-baseline", "--full"] + extra
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=600)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert p.returncode == 0 and len(lines) == 1, p.stdout[-2000:] + p.stderr[-2000:]
@@ -72,7 +72,7 @@ def test_failed_band_pipeline_still_reports_the_collective_free_mode():
     env = dict(os.environ, PFX_BENCH_BACKEND="gloo", PFX_BENCH_TEST_FAIL_BAND="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", "29661",
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--width", "640", "--height", "400", "--layers", "6", "--sigma", "3.0",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=600)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert p.returncode != 0 and len(lines) == 1, p.stdout[-2000:] + p.stderr[-2000:]
@@ -108,7 +108,7 @@ def test_band_mode_over_rccl_when_two_gpus_are_visible():
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", "29671",
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--width", "1024", "--height", "640", "--layers", "6",
-           "--sigma", "8.0", "--no-cpu-baseline", "--exact"]
+           "--sigma", "8.0", "--no-cpu-baseline", "--exact", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert p.returncode == 0 and len(lines) == 1, p.stdout[-2000:] + p.stderr[-2000:]
@@ -246,7 +246,7 @@ def test_single_rank_line_carries_live_hbm_traffic():
         pytest.skip("rocprofv3 not installed")
     w, h, n = 2048, 1024, 20
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--width", str(w), "--height", str(h), "--layers", str(n),
-           "--sigma", "3.0", "--no-cpu-baseline", "--no-group", "--headline-only"]
+           "--sigma", "3.0", "--no-cpu-baseline", "--no-group", "--headline-only", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=600)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert p.returncode == 0 and len(lines) == 1, p.stdout[-2000:] + p.stderr[-2000:]

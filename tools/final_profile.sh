@@ -2,7 +2,7 @@
 # tools/final_profile.sh <commit> — the judged artefacts of one build from ONE box: driver-style bench line, rocprofv3 kernel stats + PMC passes, operation table
 cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/final; rm -rf $OUT; mkdir -p $OUT
-timeout 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 bash tools/prof.sh final > $OUT/prof.log 2>&1
 python tools/pmc_json.py gpurun_out/prof_final $OUT/pmc.json $1 > $OUT/pmc_json.log 2>&1; echo "pmc_json rc=$?"
 cp gpurun_out/prof_final/summary.txt $OUT/rocprof_summary.txt

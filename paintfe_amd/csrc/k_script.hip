@@ -86,7 +86,7 @@ __global__ void vm_kernel(const pfxk_vm_args A)
         case BC_IMOD:
             if (ib == 0) err = BCE_MOD_ZERO;
             else if ((((uint64_t)ia | (uint64_t)ib) >> 31) == 0) R(I.dst) = (uint64_t)((uint32_t)ia % (uint32_t)ib);
-            else if (ia == INT64_MIN && ib == -1) err = BCE_DIV_OVERFLOW;
+            else if (ia == INT64_MIN && ib == -1) err = BCE_MOD_OVERFLOW;
             else R(I.dst) = (uint64_t)(ia % ib);
             break;
         case BC_INEG: if (ia == INT64_MIN) err = BCE_NEG_OVERFLOW; else R(I.dst) = (uint64_t)(-ia); break;
@@ -116,7 +116,12 @@ __global__ void vm_kernel(const pfxk_vm_args A)
         case BC_ISIGN: R(I.dst) = (uint64_t)(int64_t)(ia > 0 ? 1 : (ia < 0 ? -1 : 0)); break;
         case BC_IMIN: R(I.dst) = (uint64_t)(ia < ib ? ia : ib); break;
         case BC_IMAX: R(I.dst) = (uint64_t)(ia > ib ? ia : ib); break;
-        case BC_ICLAMP: { const int64_t hi = (int64_t)R(I.c); int64_t v = ia; if (v < ib) v = ib; if (v > hi) v = hi; R(I.dst) = (uint64_t)v; break; }
+        case BC_ICLAMP: { // i64::clamp asserts min <= max: the host API reports it (pfx_script_host.cpp)
+            const int64_t hi = (int64_t)R(I.c);
+            if (ib > hi) { err = BCE_CLAMP_RANGE; break; }
+            int64_t v = ia; if (v < ib) v = ib; if (v > hi) v = hi; R(I.dst) = (uint64_t)v;
+            break;
+        }
         case BC_IEQ: R(I.dst) = ia == ib; break;
         case BC_INE: R(I.dst) = ia != ib; break;
         case BC_ILT: R(I.dst) = ia < ib; break;
@@ -293,21 +298,31 @@ dim3 tile_grid(int w, int h) { return dim3((w + 63) / 64, (h + 3) / 4); }
 
 } // namespace
 
+extern "C" int pfxk_vm_shape(int n_regs, int n_code, pfxk_vm_shape_t* out)
+{
+    int lanes = n_regs > 0 ? (int)(65536 / ((size_t)n_regs * 8)) : 0;
+    lanes = lanes >= 256 ? 256 : (lanes / 64) * 64;
+    if (lanes < 64 || n_code < 0) return 0; // > 128 registers: rejected by the compiler before we get here
+    const size_t lds_regs = (size_t)lanes * n_regs * 8, lds_code = ((size_t)n_code * 12 + 15) & ~(size_t)15;
+    out->lanes = lanes;
+    out->lcode = lds_regs + lds_code <= 65536;
+    out->lds_bytes = out->lcode ? lds_regs + lds_code : lds_regs;
+    return 1;
+}
+
 extern "C" hipError_t pfxk_vm_run(hipStream_t s, const pfxk_vm_args* A)
 {
     const long long n = (long long)(A->x1 - A->x0) * (A->y1 - A->y0);
     if (n <= 0) return hipSuccess;
-    int lanes = (int)(65536 / ((size_t)A->n_regs * 8));
-    lanes = lanes >= 256 ? 256 : (lanes / 64) * 64;
-    if (lanes < 64) return hipErrorInvalidValue; // > 128 registers: rejected by the compiler before we get here
-    const size_t lds_regs = (size_t)lanes * A->n_regs * 8, lds_code = ((size_t)A->n_code * 12 + 15) & ~(size_t)15;
+    pfxk_vm_shape_t sh;
+    if (!pfxk_vm_shape(A->n_regs, A->n_code, &sh)) return hipErrorInvalidValue;
+    const int lanes = sh.lanes;
     long long blocks = (n + lanes - 1) / lanes;
-    if (blocks > 256 * 32) blocks = 256 * 32; // grid stride beyond that: the staged program is reused
-    const bool lcode = lds_regs + lds_code <= 65536;
-    const size_t lds = lcode ? lds_regs + lds_code : lds_regs;
+    if (blocks > PFXK_VM_MAX_BLOCKS) blocks = PFXK_VM_MAX_BLOCKS; // grid stride beyond that: the staged program is reused
+    const size_t lds = sh.lds_bytes;
     const uint32_t g = (uint32_t)blocks;
-    if (A->heavy) { if (lcode) vm_kernel<true, true><<<g, lanes, lds, s>>>(*A); else vm_kernel<false, true><<<g, lanes, lds, s>>>(*A); }
-    else          { if (lcode) vm_kernel<true, false><<<g, lanes, lds, s>>>(*A); else vm_kernel<false, false><<<g, lanes, lds, s>>>(*A); }
+    if (A->heavy) { if (sh.lcode) vm_kernel<true, true><<<g, lanes, lds, s>>>(*A); else vm_kernel<false, true><<<g, lanes, lds, s>>>(*A); }
+    else          { if (sh.lcode) vm_kernel<true, false><<<g, lanes, lds, s>>>(*A); else vm_kernel<false, false><<<g, lanes, lds, s>>>(*A); }
     return hipGetLastError();
 }
 

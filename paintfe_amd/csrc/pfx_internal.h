@@ -158,6 +158,12 @@ int pfx_int_script_run_dev(pfx_ctx* ctx, const char* source, uint32_t* w, uint32
                            std::vector<std::string>* console, std::vector<pfx_canvas_op>* ops);
 
 extern "C" int pfx_int_script_check_limited(const char* source, uint32_t w, uint32_t h, pfx_script_result* result, uint64_t max_ops);
+// test seams of the per-pixel closure path (not in include/pfx.h): the compiled form and launch shape of a script's first bulk-iterator closure
+// (out[0 .. 9) = n_params, n_regs, n_code, n_pre, heavy, lanes, lcode, LDS bytes, BC_COUNT; then a count per opcode; cap >= 9 + BC_COUNT), and
+// pfx_script_check with the whole console
+#define PFX_CLOSURE_SHAPE_FIELDS 9
+extern "C" int pfx_int_script_closure_shape(const char* source, uint32_t w, uint32_t h, int64_t* out, int cap);
+extern "C" int pfx_int_script_check_console(const char* source, uint32_t w, uint32_t h, pfx_script_result* result, char* console, size_t cap, size_t* len);
 
 // run_one's script step on a document (pfx_project.cpp): pfx_project_run_script plus the console lines for --verbose
 int pfx_int_project_run_script(pfx_ctx* ctx, pfx_project* p, const char* source, pfx_script_result* result, std::vector<std::string>* console);

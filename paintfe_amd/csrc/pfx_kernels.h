@@ -211,6 +211,16 @@ typedef struct pfxk_vm_args {
     uint32_t step_budget;     // bytecode steps one pixel may execute before the launch reports 'Too many operations'
 } pfxk_vm_args;
 hipError_t pfxk_vm_run(hipStream_t s, const pfxk_vm_args* A);
+// the launch shape pfxk_vm_run picks for a program (host only; the shape probe of the tests reports it too): lanes per workgroup from the register
+// count (the register file fills 64 KiB of LDS at most), the program staged in LDS behind it when both fit (lcode = 1), the dynamic LDS bytes.
+// Returns 0 for a program no launch can take (more than 128 registers).
+#define PFXK_VM_MAX_BLOCKS (256 * 32) // grid size cap: larger regions are walked with a grid stride
+typedef struct pfxk_vm_shape_t {
+    int lanes;
+    int lcode;
+    size_t lds_bytes;
+} pfxk_vm_shape_t;
+int pfxk_vm_shape(int n_regs, int n_code, pfxk_vm_shape_t* out);
 // mode: 0 flip_horizontal, 1 flip_vertical, 2 rotate180, 3 rotate90 (cw), 4 rotate270 (ccw); (w, h) = source size
 hipError_t pfxk_permute(hipStream_t s, const uint8_t* d_src, uint8_t* d_dst, int mode, uint32_t w, uint32_t h);
 hipError_t pfxk_recanvas(hipStream_t s, const uint8_t* d_src, uint8_t* d_dst, uint32_t ow, uint32_t oh, uint32_t nw, uint32_t nh, int off_x, int off_y,

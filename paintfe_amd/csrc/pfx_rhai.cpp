@@ -533,6 +533,18 @@ private:
         }
         for (const char* kw : {"import", "export"})
             if (is_kw(kw)) fail("Rhai statement '" + cur_.text + "' is outside the supported subset", cur_.line, cur_.col, ST_UNSUPPORTED);
+        // an `if` / `switch` / block at the start of a statement is a statement of its own (rhai's parse_stmt takes them before any expression, and they
+        // need no ';'): what follows starts the next statement, so `if c { .. } [r, g, b, a]` is two statements, not an index into the `if`
+        if (is_kw("if") || is_kw("switch") || is_p("{")) {
+            NodeP e;
+            {
+                DepthGuard g(*this, cur_);
+                e = primary();
+            }
+            auto st = wrap_stmt(e, t0);
+            end_stmt(st, false);
+            return st;
+        }
         // expression or assignment
         NodeP e = expr(0);
         static const char* assign_ops[] = {"=", "+=", "-=", "*=", "/=", "%=", "**=", "<<=", ">>=", "&=", "|=", "^="};
@@ -2164,6 +2176,8 @@ const char* Interp::bc_error_text(int code)
     case BCE_F2I_RANGE: return "Integer overflow: to_int";
     case BCE_TOO_MANY_OPS: return "Too many operations";
     case BCE_ABS_OVERFLOW: return "Integer overflow: abs";
+    case BCE_MOD_OVERFLOW: return "Modulo division overflow";
+    case BCE_CLAMP_RANGE: return "clamp: min > max";
     default: return "runtime error in per-pixel closure";
     }
 }

@@ -106,8 +106,15 @@ enum BcOp : uint16_t {
     BC_COUNT
 };
 enum BcErr : int32_t { BCE_NONE = 0, BCE_ADD_OVERFLOW, BCE_SUB_OVERFLOW, BCE_MUL_OVERFLOW, BCE_DIV_ZERO, BCE_DIV_OVERFLOW, BCE_MOD_ZERO, BCE_NEG_OVERFLOW,
-             BCE_POW_OVERFLOW, BCE_POW_NEGATIVE, BCE_F2I_RANGE, BCE_TOO_MANY_OPS, BCE_SHIFT, BCE_ABS_OVERFLOW };
+             BCE_POW_OVERFLOW, BCE_POW_NEGATIVE, BCE_F2I_RANGE, BCE_TOO_MANY_OPS, BCE_SHIFT, BCE_ABS_OVERFLOW,
+             BCE_MOD_OVERFLOW,   // appended: the codes above keep their values
+             BCE_CLAMP_RANGE };
 struct BcIns { uint16_t op, dst, a, b, c, line; };
+// the f64 libm routines: a program using any of them runs the kernel instantiation that carries them (HEAVY, k_script.hip)
+inline bool bc_heavy_op(uint16_t op)
+{
+    return op == BC_FMOD || op == BC_FPOW || op == BC_FSIN || op == BC_FCOS || op == BC_FTAN || op == BC_FATAN2 || op == BC_FEXP || op == BC_FLN;
+}
 struct BcProgram {
     std::vector<BcIns> code;
     std::vector<uint64_t> consts;

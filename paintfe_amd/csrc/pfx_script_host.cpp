@@ -37,6 +37,12 @@ namespace {
 
 using VT = Value::T;
 
+bool program_is_heavy(const rhai::BcProgram& p)
+{
+    for (const rhai::BcIns& ins : p.code) if (rhai::bc_heavy_op(ins.op)) return true;
+    return false;
+}
+
 struct ScriptHost : rhai::Host {
     pfx_ctx* ctx = nullptr; // NULL: language-only check mode
     uint32_t w = 0, h = 0;
@@ -48,6 +54,9 @@ struct ScriptHost : rhai::Host {
     std::vector<uint8_t> host_mask;
     uint64_t rng = 0;
     std::vector<pfx_canvas_op> ops;
+    // shape probe (pfx_int_script_closure_shape): the first bulk-iterator call compiles its closure into *probe, launches nothing and ends the script
+    rhai::BcProgram* probe = nullptr;
+    bool probed = false;
 
     size_t bytes() const { return (size_t)w * h * 4; }
     const void* d_mask() const { return has_mask ? ctx->st_mask.p : nullptr; }
@@ -118,6 +127,15 @@ struct ScriptHost : rhai::Host {
         return PFX_OK;
     }
 
+    int probe_closure(rhai::Interp& in, const rhai::Closure& c, int n_params, rhai::Error& err)
+    {
+        if (!in.compile_closure(c, n_params, (int64_t)w, (int64_t)h, *probe, err)) return 2;
+        probed = true;
+        err.msg = "shape probe: stopped at the first bulk iterator";
+        err.status = PFX_ERR_SCRIPT;
+        return 2;
+    }
+
     int run_closure(rhai::Interp& in, const rhai::Closure& c, int n_params, int x0, int y0, int x1, int y1, rhai::Error& err)
     {
         rhai::BcProgram prog;
@@ -145,9 +163,7 @@ struct ScriptHost : rhai::Host {
         A.n_pre = prog.n_pre;
         A.n_regs = prog.n_regs;
         A.n_params = n_params;
-        for (const rhai::BcIns& ins : prog.code) // f64 libm routines live in the heavier of the two kernel instantiations
-            if (ins.op == rhai::BC_FMOD || ins.op == rhai::BC_FPOW || ins.op == rhai::BC_FSIN || ins.op == rhai::BC_FCOS || ins.op == rhai::BC_FTAN ||
-                ins.op == rhai::BC_FATAN2 || ins.op == rhai::BC_FEXP || ins.op == rhai::BC_FLN) A.heavy = 1;
+        A.heavy = program_is_heavy(prog);
         A.w = (int)w; A.h = (int)h;
         A.x0 = x0; A.y0 = y0; A.x1 = x1; A.y1 = y1;
         // Operation budget.  The reference counts a closure's operations against the script's single 50 M budget (set_max_operations,
@@ -284,9 +300,10 @@ int ScriptHost::call(rhai::Interp& in, const std::string& name, std::vector<Valu
         }
     }
     // ---------------------------------------------------------------- bulk iterators
-    FN("for_each_pixel") if (sig({VT::Fn})) { if (need_image()) return 2; return dev(run_closure(in, *a[0].fn, 6, 0, 0, (int)w, (int)h, err)); }
-    FN("map_channels") if (sig({VT::Fn})) { if (need_image()) return 2; return dev(run_closure(in, *a[0].fn, 4, 0, 0, (int)w, (int)h, err)); }
+    FN("for_each_pixel") if (sig({VT::Fn})) { if (probe) return probe_closure(in, *a[0].fn, 6, err); if (need_image()) return 2; return dev(run_closure(in, *a[0].fn, 6, 0, 0, (int)w, (int)h, err)); }
+    FN("map_channels") if (sig({VT::Fn})) { if (probe) return probe_closure(in, *a[0].fn, 4, err); if (need_image()) return 2; return dev(run_closure(in, *a[0].fn, 4, 0, 0, (int)w, (int)h, err)); }
     FN("for_region") if (sig({VT::Int, VT::Int, VT::Int, VT::Int, VT::Fn})) { // scripting.rs:513-516
+        if (probe) return probe_closure(in, *a[4].fn, 6, err);
         if (need_image()) return 2;
         const int64_t rx = a[0].i, ry = a[1].i;
         const uint32_t x0 = i64_as_u32(std::max<int64_t>(rx, 0)), y0 = i64_as_u32(std::max<int64_t>(ry, 0));
@@ -672,6 +689,55 @@ int pfx_int_script_check_limited(const char* source, uint32_t w, uint32_t h, pfx
     rhai::Error err;
     const bool ok = in.run(source, err);
     fill_result(result, ok ? nullptr : &err, in.console, in.ops());
+    return ok ? PFX_OK : (err.status ? err.status : PFX_ERR_SCRIPT);
+}
+
+// Test seam: the compiled form and launch shape of a script's first per-pixel closure, without a device.  The script runs in the language-only evaluator
+// up to its first map_channels / for_each_pixel / for_region call, whose closure is compiled as run_closure compiles it; nothing is launched.
+// out[0 .. PFX_CLOSURE_SHAPE_FIELDS): n_params, n_regs, n_code, n_pre, heavy, lanes, lcode, LDS bytes, BC_COUNT; then one count per opcode.
+int pfx_int_script_closure_shape(const char* source, uint32_t w, uint32_t h, int64_t* out, int cap)
+{
+    if (!source || !out || cap < PFX_CLOSURE_SHAPE_FIELDS + (int)rhai::BC_COUNT) return PFX_ERR_INVALID;
+    ScriptHost host;
+    host.w = w;
+    host.h = h;
+    host.rng = time_seed();
+    rhai::BcProgram prog;
+    host.probe = &prog;
+    rhai::Interp in(&host);
+    rhai::Error err;
+    const bool ok = in.run(source, err);
+    if (!host.probed) return ok ? PFX_ERR_INVALID : (err.status ? err.status : PFX_ERR_SCRIPT); // no bulk iterator reached, or its closure did not compile
+    pfxk_vm_shape_t sh{};
+    if (!pfxk_vm_shape(prog.n_regs, (int)prog.code.size(), &sh)) return PFX_ERR_INVALID;
+    const int64_t head[PFX_CLOSURE_SHAPE_FIELDS] = {prog.n_params, prog.n_regs, (int64_t)prog.code.size(), prog.n_pre, program_is_heavy(prog) ? 1 : 0,
+                                                    sh.lanes, sh.lcode, (int64_t)sh.lds_bytes, (int64_t)rhai::BC_COUNT};
+    for (int k = 0; k < PFX_CLOSURE_SHAPE_FIELDS; ++k) out[k] = head[k];
+    for (int k = 0; k < (int)rhai::BC_COUNT; ++k) out[PFX_CLOSURE_SHAPE_FIELDS + k] = 0;
+    for (const rhai::BcIns& ins : prog.code) ++out[PFX_CLOSURE_SHAPE_FIELDS + ins.op];
+    return PFX_OK;
+}
+
+// pfx_script_check with the whole console (pfx_script_result holds its first 2 KiB): up to cap - 1 bytes of it, '\n'-terminated lines, NUL-terminated,
+// go to `console`; *len receives the full length.  The tests' host reference for per-pixel closures prints one line per pixel.
+int pfx_int_script_check_console(const char* source, uint32_t w, uint32_t h, pfx_script_result* result, char* console, size_t cap, size_t* len)
+{
+    if (result) std::memset(result, 0, sizeof *result);
+    if (!source || !console || !cap || !len) return PFX_ERR_INVALID;
+    ScriptHost host;
+    host.w = w;
+    host.h = h;
+    host.rng = time_seed();
+    rhai::Interp in(&host);
+    rhai::Error err;
+    const bool ok = in.run(source, err);
+    fill_result(result, ok ? nullptr : &err, in.console, in.ops());
+    std::string joined;
+    for (const std::string& l : in.console) { joined += l; joined += '\n'; }
+    *len = joined.size();
+    const size_t n = std::min(joined.size(), cap - 1);
+    std::memcpy(console, joined.data(), n);
+    console[n] = 0;
     return ok ? PFX_OK : (err.status ? err.status : PFX_ERR_SCRIPT);
 }
 

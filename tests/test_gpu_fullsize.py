@@ -13,6 +13,7 @@ import pytest
 import torch  # noqa: F401  -- at collection time, i.e. before any test loads libpfx.so: PyTorch must bring up the HIP runtime
 #                              first (it ships its own copy; loaded second it reports no device), as bench.py does
 
+from . import gauss_model as GM
 from . import inputs as I
 from . import oracle_lib as O
 
@@ -118,6 +119,9 @@ def test_gaussian_8k_sigma16_windows(env, stack8k, exact):
         got = host(blurred[y:y + wh, x:x + ww, :])
         d = np.abs(ref.astype(np.int16) - got.astype(np.int16))
         assert d.max() <= tol, f"window at ({x},{y}) exact={exact}: max diff {int(d.max())}"
+        if not exact:   # and to the float64 model of the matrix-core kernel's own arithmetic (tests/gauss_model.py) on the same crop
+            m = GM.model_mfma(host(flat[y0:y1, x0:x1, :]), sigma)[y - y0:y - y0 + wh, x - x0:x - x0 + ww]
+            GM.check(m, GM.eps_mfma(radius), got, f"window at ({x},{y}) against the model")
 
 
 @pytest.mark.parametrize("radius", [3, 5, 7, 8])

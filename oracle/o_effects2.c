@@ -22,7 +22,9 @@
  *   src/ops/effects/artistic.rs:123-215       oil_painting_core
  *   src/ops/effects/artistic.rs:266-309       color_filter_core
  *   src/ops/effects/contours.rs:56-112        contours_core
- * Transcendentals are glibc's (Rust's f32::exp/ln/cos/sin/powf lower to the system libm on Linux).
+ * Transcendentals are glibc's (Rust's f32::exp/ln/cos/sin/powf lower to the system libm on Linux); those of twist,
+ * gaussian noise, reduce_noise and vignette go through o_common.h's helpers, which pfxo_set_libm can switch to the
+ * device kernels' evaluation.
  */
 #include "o_common.h"
 
@@ -46,6 +48,138 @@ static inline float hash_f32(uint32_t x, uint32_t y, uint32_t seed)
     return (float)(h & 0x00FFFFFFu) / 16777216.0f;
 }
 float pfxo_hash_f32(uint32_t x, uint32_t y, uint32_t seed) { return hash_f32(x, y, seed); }
+
+/* ---- libm flavours (o_common.h) ---- */
+int o_libm_flavour = O_LIBM_GLIBC;
+long long o_libm_ambiguous = 0;
+void pfxo_set_libm(int flavour) { o_libm_flavour = flavour; }
+int pfxo_get_libm(void) { return o_libm_flavour; }
+long long pfxo_libm_ambiguous(void) { return __atomic_load_n(&o_libm_ambiguous, __ATOMIC_RELAXED); }
+void pfxo_libm_reset(void) { __atomic_store_n(&o_libm_ambiguous, 0, __ATOMIC_RELAXED); }
+
+/* The device's libm_exp (paintfe_amd/csrc/k_libm.h), restated: glibc's expf algorithm (sysdeps/ieee754/flt-32/e_expf.c)
+ * in f64 with the contractions of glibc's FMA build written out as fma().  The table and constants are the device
+ * header's (tests/test_libm_model_host.py reads them out of it and compares). */
+static const uint64_t O_EXP2F_TAB[32] = {
+    0x3ff0000000000000ull, 0x3fefd9b0d3158574ull, 0x3fefb5586cf9890full, 0x3fef9301d0125b51ull,
+    0x3fef72b83c7d517bull, 0x3fef54873168b9aaull, 0x3fef387a6e756238ull, 0x3fef1e9df51fdee1ull,
+    0x3fef06fe0a31b715ull, 0x3feef1a7373aa9cbull, 0x3feedea64c123422ull, 0x3feece086061892dull,
+    0x3feebfdad5362a27ull, 0x3feeb42b569d4f82ull, 0x3feeab07dd485429ull, 0x3feea47eb03a5585ull,
+    0x3feea09e667f3bcdull, 0x3fee9f75e8ec5f74ull, 0x3feea11473eb0187ull, 0x3feea589994cce13ull,
+    0x3feeace5422aa0dbull, 0x3feeb737b0cdc5e5ull, 0x3feec49182a3f090ull, 0x3feed503b23e255dull,
+    0x3feee89f995ad3adull, 0x3feeff76f2fb5e47ull, 0x3fef199bdd85529cull, 0x3fef3720dcef9069ull,
+    0x3fef5818dcfba487ull, 0x3fef7c97337b9b5full, 0x3fefa4afa2a490daull, 0x3fefd0765b6e4540ull};
+static const double O_EXP_INVLN2N = 0x1.71547652b82fep+0 * 32.0, O_EXP_SHIFT = 0x1.8p52;
+static const double O_EXP_C0 = 0x1.c6af84b912394p-5 / 32.0 / 32.0 / 32.0, O_EXP_C1 = 0x1.ebfce50fac4f3p-3 / 32.0 / 32.0,
+                    O_EXP_C2 = 0x1.62e42ff0c52d6p-1 / 32.0;
+static const float O_EXP_LO = -0x1.9fe368p6f, O_EXP_HI = 0x1.62e42ep6f;
+float o_libm_exp(float x, int variant)
+{
+    if (!(x >= O_EXP_LO)) return (x != x) ? x : 0.0f;
+    if (x > O_EXP_HI) return INFINITY;
+    const double z = O_EXP_INVLN2N * (double)x;
+    double kd = z + O_EXP_SHIFT;
+    uint64_t ki;
+    memcpy(&ki, &kd, 8);
+    kd -= O_EXP_SHIFT;
+    const double r = variant != 0 ? z - kd : fma(O_EXP_INVLN2N, (double)x, -kd);
+    const uint64_t t = O_EXP2F_TAB[ki & 31u] + (ki << 47);
+    double sc;
+    memcpy(&sc, &t, 8);
+    const double r2 = r * r;
+    double y;
+    if (variant == 1) y = (O_EXP_C0 * r + O_EXP_C1) * r2 + (O_EXP_C2 * r + 1.0);
+    else y = fma(fma(O_EXP_C0, r, O_EXP_C1), r2, fma(O_EXP_C2, r, 1.0));
+    return (float)(y * sc);
+}
+float pfxo_libm_eval(int fn, float x)
+{
+    switch (fn) {
+    case 0: return o_cosf(x);
+    case 1: return o_sinf(x);
+    case 2: return o_logf(x);
+    case 3: return o_expf(x);
+    case 4: return o_sqf(x);
+    default: return o_brush_expf(x);
+    }
+}
+int pfxo_libm_host_has_fma(void)
+{
+#if defined(__x86_64__) || defined(__i386__)
+    __builtin_cpu_init();
+    return __builtin_cpu_supports("fma") ? 1 : 0;
+#else
+    return 0;
+#endif
+}
+void pfxo_libm_exp_tables(uint64_t tab[32], double consts[7])
+{
+    memcpy(tab, O_EXP2F_TAB, sizeof O_EXP2F_TAB);
+    const double c[7] = {O_EXP_INVLN2N, O_EXP_SHIFT, O_EXP_C0, O_EXP_C1, O_EXP_C2, O_EXP_LO, O_EXP_HI};
+    memcpy(consts, c, sizeof c);
+}
+static inline float o_f32_of(uint32_t b) { float f; memcpy(&f, &b, 4); return f; }
+static inline uint32_t o_bits_of(float f) { uint32_t b; memcpy(&b, &f, 4); return b; }
+long long pfxo_libm_check_exp(int variant, float lo, float hi, float* first_bad, int threads)
+{
+    /* every f32 in [lo, hi], both <= 0: the bit patterns from hi's to lo's (magnitude grows with the pattern) */
+    if (!(lo <= hi) || hi > 0.0f) return -1;
+    const int64_t b0 = (int64_t)o_bits_of(hi == 0.0f ? -0.0f : hi), b1 = (int64_t)o_bits_of(lo);
+    long long bad = 0;
+    uint32_t first = 0xFFFFFFFFu;
+    o_set_threads(threads);
+#pragma omp parallel for schedule(static, 1 << 16) reduction(+ : bad) reduction(min : first)
+    for (int64_t b = b0; b <= b1; ++b) {
+        const float x = o_f32_of((uint32_t)b);
+        const float e = expf(x), d = o_libm_exp(x, variant);
+        if (o_bits_of(e) != o_bits_of(d)) {
+            ++bad;
+            if ((uint32_t)b < first) first = (uint32_t)b;
+        }
+    }
+    if (first_bad) *first_bad = bad ? o_f32_of(first) : 0.0f;
+    return bad;
+}
+long long pfxo_libm_check_sq(int library, int threads)
+{
+    /* library = 0: o_sqf's glibc form as compiled here, where powf(q, 2.0f) is folded into q * q (as the reference's compiler
+     * folds it); library = 1: glibc's powf routine itself, called through a pointer */
+    float (*volatile pw)(float, float) = powf;
+    long long bad = 0;
+    const int saved = o_libm_flavour;
+    o_libm_flavour = O_LIBM_GLIBC;
+    o_set_threads(threads);
+#pragma omp parallel for schedule(static, 1 << 16) reduction(+ : bad)
+    for (int64_t b = 0; b <= (int64_t)o_bits_of(1.0f); ++b) {
+        const float q = o_f32_of((uint32_t)b);
+        const float v = library ? pw(q, 2.0f) : o_sqf(q);
+        bad += o_bits_of(v) != o_bits_of((float)((double)q * (double)q));
+    }
+    o_libm_flavour = saved;
+    return bad;
+}
+long long pfxo_libm_check_noise_log(int threads)
+{
+    long long bad = 0;
+    o_set_threads(threads);
+#pragma omp parallel for schedule(static, 1 << 16) reduction(+ : bad)
+    for (int64_t k = 0; k < (1 << 24); ++k) {
+        const float u1 = fmaxf((float)k / 16777216.0f, 0.0001f);
+        bad += o_bits_of(logf(u1)) != o_bits_of((float)log((double)u1));
+    }
+    return bad;
+}
+long long pfxo_libm_check_noise_cos(int threads)
+{
+    long long bad = 0;
+    o_set_threads(threads);
+#pragma omp parallel for schedule(static, 1 << 16) reduction(+ : bad)
+    for (int64_t k = 0; k < (1 << 24); ++k) {
+        const float a = 2.0f * PI_F * ((float)k / 16777216.0f);
+        bad += o_bits_of(cosf(a)) != o_bits_of((float)cos((double)a));
+    }
+    return bad;
+}
 
 /* noise.rs:53-71 */
 static float perlin_noise_2d(float x, float y, uint32_t seed)
@@ -303,7 +437,7 @@ void pfxo_twist(const uint8_t* src, uint32_t w32, uint32_t h32, float angle_deg,
             float dist = sqrtf(dx * dx + dy * dy);
             float norm = dist / max_r;
             float rotation = twist_amount * (1.0f - norm);
-            float cos_r = cosf(rotation), sin_r = sinf(rotation);
+            float cos_r = o_cosf(rotation), sin_r = o_sinf(rotation);
             float p[4];
             sample_bilinear(src, wl, hl, cx + dx * cos_r - dy * sin_r, cy + dx * sin_r + dy * cos_r, p);
             for (int c = 0; c < 4; ++c) dst[oi + c] = round_u8(p[c]);
@@ -335,7 +469,7 @@ void pfxo_add_noise(const uint8_t* src, uint32_t w32, uint32_t h32, float amount
                 else if (noise_type == 1) {
                     float u1 = fmaxf(hash_f32(qx, qy, seed), 0.0001f);
                     float u2 = hash_f32(qx, qy, seed + 7u);
-                    noise_val = sqrtf(-2.0f * logf(u1)) * cosf(2.0f * PI_F * u2) * 0.33f;
+                    noise_val = sqrtf(-2.0f * o_logf(u1)) * o_cosf(2.0f * PI_F * u2) * 0.33f;
                 } else noise_val = turbulence_2d(sx, sy, seed, oct, 0.5f) * 2.0f - 1.0f;
                 nr = ng = nb = noise_val * strength;
             } else if (noise_type == 2) {
@@ -376,7 +510,7 @@ void pfxo_reduce_noise(const uint8_t* src, uint32_t w32, uint32_t h32, float str
                     float spatial = (float)(dx * dx + dy * dy) / (2.0f * sigma_s * sigma_s);
                     float dr = cr - pr, dg = cg - pg, db = cb - pb;
                     float range = (dr * dr + dg * dg + db * db) / (2.0f * sigma_r * sigma_r + 0.001f);
-                    float weight = expf(-spatial - range);
+                    float weight = o_expf(-spatial - range);
                     sum[0] += pr * weight; sum[1] += pg * weight; sum[2] += pb * weight; sum[3] += pa * weight;
                     weight_sum += weight;
                 }
@@ -405,7 +539,7 @@ void pfxo_vignette(const uint8_t* src, uint32_t w32, uint32_t h32, float amount,
             if (masked_out(mask, wl, x, y)) { memcpy(dst + oi, src + oi, 4); continue; }
             float dx = (float)x - cx, dy = (float)y - cy;
             float dist = sqrtf(dx * dx + dy * dy) / max_dist;
-            float vf = rs_clampf(1.0f - (amount * powf(fminf(dist / soft, 1.0f), 2.0f)), 0.0f, 1.0f);
+            float vf = rs_clampf(1.0f - (amount * o_sqf(fminf(dist / soft, 1.0f))), 0.0f, 1.0f);
             for (int c = 0; c < 3; ++c) dst[oi + c] = round_u8((float)src[oi + c] * vf);
             dst[oi + 3] = src[oi + 3];
         }

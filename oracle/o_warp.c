@@ -165,7 +165,7 @@ void pfxo_displacement_brush(float* disp, uint32_t w, uint32_t h, int mode, floa
             float* d = disp + ((size_t)py * w + (size_t)px) * 2;
             switch (mode) {
             case 0: {
-                float weight = expf(-dist_sq / sigma_sq_2) * strength;
+                float weight = o_brush_expf(-dist_sq / sigma_sq_2) * strength;
                 d[0] += delta_x * weight; d[1] += delta_y * weight;
                 break;
             }
@@ -178,12 +178,12 @@ void pfxo_displacement_brush(float* disp, uint32_t w, uint32_t h, int mode, floa
             }
             case 2: {
                 float dist = fmaxf(sqrtf(dist_sq), 0.001f);
-                float weight = expf(-dist_sq / sigma_sq_2) * strength;
+                float weight = o_brush_expf(-dist_sq / sigma_sq_2) * strength;
                 d[0] += -dx / dist * weight * 2.0f; d[1] += -dy / dist * weight * 2.0f;
                 break;
             }
             default: {
-                float weight = expf(-dist_sq / sigma_sq_2) * strength * dir;
+                float weight = o_brush_expf(-dist_sq / sigma_sq_2) * strength * dir;
                 d[0] += -dy * weight * 0.1f; d[1] += dx * weight * 0.1f;
             }
             }

@@ -225,6 +225,24 @@ void pfxo_eraser_commit(uint8_t* layer, const uint8_t* preview, uint32_t w, uint
 
 int pfxo_version(void);
 
+/* ---- libm flavour of the transcendental call sites (twist, gaussian noise, reduce_noise, vignette, displacement brush) ----
+ * 0 (default): glibc's f32 routines, as the reference.  1: each call evaluated the way its device kernel evaluates it.
+ * 2..5: the device flavour with one deliberate defect (o_common.h), for the tests to reject.  Process-wide: not thread safe. */
+void pfxo_set_libm(int flavour);
+int pfxo_get_libm(void);
+/* calls since the last reset whose f64 result lay within 4 f64 ulps of an f32 rounding boundary (flavours >= 1 only) */
+long long pfxo_libm_ambiguous(void);
+void pfxo_libm_reset(void);
+/* one call-site function under the current flavour; fn: 0 cos, 1 sin, 2 log, 3 exp, 4 powf(x, 2), 5 the brush's exp */
+float pfxo_libm_eval(int fn, float x);
+/* self-checks of the device restatement against the host's glibc, exhaustive over f32 ranges (OpenMP) */
+int pfxo_libm_host_has_fma(void);
+void pfxo_libm_exp_tables(uint64_t tab[32], double consts[7]); /* EXP2F_TAB; InvLn2N SHIFT C0 C1 C2 lower upper */
+long long pfxo_libm_check_exp(int variant, float lo, float hi, float* first_bad, int threads); /* differences from expf on [lo, hi] <= 0 */
+long long pfxo_libm_check_sq(int library, int threads); /* powf(q, 2) != (float)((double)q*q) over every f32 q in [0, 1] */
+long long pfxo_libm_check_noise_log(int threads); /* logf(u1) != (float)log((double)u1), u1 = max(k/2^24, 1e-4), k < 2^24 */
+long long pfxo_libm_check_noise_cos(int threads); /* cosf(a) != (float)cos((double)a), a = 2*PI_F*(k/2^24), k < 2^24 */
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@
 // source is read roughly once from HBM).  The fused mesh warp evaluates the two bicubic surfaces in registers from
 // control points staged in LDS and never materialises the 8 B/px displacement field.
 #include "k_common.h"
+#include "k_libm.h"
 #include <type_traits>
 #include "pfx_kernels.h"
 
@@ -434,8 +435,8 @@ extern "C" hipError_t pfxk_warp_displacement(hipStream_t s, const uint8_t* d_src
 // ---- DisplacementField brushes on a device-resident field (apply_push / expand / contract / twirl, transform.rs:1051-1200) ----
 // The reference stamps dabs one after another; here one lane owns a pixel of the stroke's bounding box and walks the dab list in
 // order, accumulating in registers (same per-pixel order of the `+=`), one read and one write of the field per launch.
-// exp() is evaluated in f64 and rounded once (see k_effects2.hip's header): the field may differ from the CPU path in the last
-// ulp of a weight, which stays far below the warp's +-1 LSB.
+// exp() is k_libm.h's libm_exp, glibc's expf bit for bit on the weights' arguments (in [-4.5, 0]): the field equals the host path's
+// (pfx_displacement_brush) and the reference's bit for bit.
 // CHUNKED: the launch runs over the 64 x 64 chunks some dab's box touches (`chunks[blockIdx.x]` = chunk x | chunk y << 16, built by the host) instead of the
 // dabs' common bounding box, which for dabs spread over a large field is mostly untouched
 template <bool CHUNKED>
@@ -467,7 +468,7 @@ __global__ __launch_bounds__(256) void disp_brush_kernel(float2* __restrict__ di
         if (dist_sq > D.r * D.r) return;
         touched = true;
         if (D.mode == 0) {        // push :1051-1085
-            const float weight = (float)exp((double)(-dist_sq / D.sigma_sq_2)) * D.strength;
+            const float weight = libm_exp(-dist_sq / D.sigma_sq_2) * D.strength;
             d.x += D.delta_x * weight;
             d.y += D.delta_y * weight;
         } else if (D.mode == 1) { // expand :1087-1120
@@ -478,11 +479,11 @@ __global__ __launch_bounds__(256) void disp_brush_kernel(float2* __restrict__ di
             d.y += dy / dist * weight;
         } else if (D.mode == 2) { // contract :1122-1155
             const float dist = __builtin_fmaxf(__builtin_sqrtf(dist_sq), 0.001f);
-            const float weight = (float)exp((double)(-dist_sq / D.sigma_sq_2)) * D.strength;
+            const float weight = libm_exp(-dist_sq / D.sigma_sq_2) * D.strength;
             d.x += -dx / dist * weight * 2.0f;
             d.y += -dy / dist * weight * 2.0f;
         } else {                  // twirl cw (3) / ccw (4) :1157-1200
-            const float weight = (float)exp((double)(-dist_sq / D.sigma_sq_2)) * D.strength * (D.mode == 3 ? 1.0f : -1.0f);
+            const float weight = libm_exp(-dist_sq / D.sigma_sq_2) * D.strength * (D.mode == 3 ? 1.0f : -1.0f);
             d.x += -dy * weight * 0.1f;
             d.y += dx * weight * 0.1f;
         }

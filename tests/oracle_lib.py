@@ -557,3 +557,83 @@ def eraser_commit(layer, preview, selection=None):
     m, pm = _opt_u8(selection)
     lib().pfxo_eraser_commit(out.ctypes.data_as(C.c_void_p), pp, C.c_uint32(w), C.c_uint32(h), pm)
     return out
+
+
+# ---- libm flavour of the transcendental call sites (pfxo_set_libm, oracle/o_common.h) ----
+LIBM_FLAVOURS = {"glibc": 0, "device": 1, "nudged": 2, "exp_nofma": 3, "exp_unfused_r": 4, "brush_f64": 5}
+LIBM_FNS = {"cos": 0, "sin": 1, "log": 2, "exp": 3, "sq": 4, "brush_exp": 5}
+
+
+def _libm_lib():
+    L = lib()
+    L.pfxo_libm_ambiguous.restype = C.c_longlong
+    L.pfxo_libm_eval.restype = C.c_float
+    L.pfxo_libm_eval.argtypes = [C.c_int, C.c_float]
+    for f in ("pfxo_libm_check_exp", "pfxo_libm_check_sq", "pfxo_libm_check_noise_log", "pfxo_libm_check_noise_cos"):
+        getattr(L, f).restype = C.c_longlong
+    return L
+
+
+class libm_flavour:
+    """``with libm_flavour("device"):`` — the oracle's twist / gaussian noise / reduce_noise / vignette / displacement brush
+    evaluate their transcendentals the way the named flavour does ("glibc" is the default and the reference; "device" is the
+    HIP kernels' evaluation; the others are the device flavour with one deliberate defect).  Restores the previous flavour."""
+
+    def __init__(self, name: str):
+        self.flavour = LIBM_FLAVOURS[name]
+
+    def __enter__(self):
+        L = _libm_lib()
+        self.saved = L.pfxo_get_libm()
+        L.pfxo_set_libm(self.flavour)
+        return self
+
+    def __exit__(self, *exc):
+        _libm_lib().pfxo_set_libm(self.saved)
+        return False
+
+
+def libm_ambiguous() -> int:
+    """calls (flavours other than glibc) since the last libm_reset() whose f64 result lay within 4 f64 ulps of an f32
+    rounding boundary: only there may the device's f64 routine round differently"""
+    return int(_libm_lib().pfxo_libm_ambiguous())
+
+
+def libm_reset():
+    _libm_lib().pfxo_libm_reset()
+
+
+def libm_eval(fn: str, x) -> np.ndarray:
+    """one call-site function (cos, sin, log, exp, sq, brush_exp) under the current flavour, per element"""
+    L = _libm_lib()
+    xs = np.atleast_1d(np.asarray(x, np.float32))
+    return np.array([L.pfxo_libm_eval(LIBM_FNS[fn], float(v)) for v in xs], np.float32)
+
+
+def libm_host_has_fma() -> bool:
+    return bool(_libm_lib().pfxo_libm_host_has_fma())
+
+
+def libm_exp_tables():
+    """(EXP2F_TAB as 32 uint64, (InvLn2N, SHIFT, C0, C1, C2, lower, upper)) of the oracle's libm_exp restatement"""
+    tab = np.zeros(32, np.uint64)
+    consts = np.zeros(7, np.float64)
+    _libm_lib().pfxo_libm_exp_tables(tab.ctypes.data_as(C.c_void_p), consts.ctypes.data_as(C.c_void_p))
+    return tab, tuple(float(c) for c in consts)
+
+
+def libm_check_exp(variant: int, lo: float, hi: float, threads: int = 0):
+    """(number of f32 x in [lo, hi] <= 0 where the restated libm_exp differs from the host's expf, the first such x);
+    variant: 0 the device form, 1 without any fma, 2 with the unfused r = z - kd"""
+    first = C.c_float(0.0)
+    n = _libm_lib().pfxo_libm_check_exp(C.c_int(variant), C.c_float(lo), C.c_float(hi), C.byref(first), C.c_int(threads))
+    return int(n), float(first.value)
+
+
+def libm_check_sq(library: bool, threads: int = 0) -> int:
+    return int(_libm_lib().pfxo_libm_check_sq(C.c_int(int(library)), C.c_int(threads)))
+
+
+def libm_check_noise(fn: str, threads: int = 0) -> int:
+    L = _libm_lib()
+    return int((L.pfxo_libm_check_noise_log if fn == "log" else L.pfxo_libm_check_noise_cos)(C.c_int(threads)))

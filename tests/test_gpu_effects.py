@@ -3,9 +3,11 @@ the C ABI vs the CPU oracle on seeded random inputs — ragged sizes, selection 
 settings, clamped parameters, off-canvas origins).
 
 Bars (written per case below):
-  * EXACT (tolerance 0): everything built from integer / hash / sqrt / divide arithmetic;
-  * LIBM  (+-1 LSB, < 0.1 % of channels off): the four effects that evaluate one libm function per pixel on the device
-    (twist: sin/cos, gaussian noise: ln/cos, reduce_noise: exp, vignette: powf) — see k_effects2.hip's header.
+  * EXACT (tolerance 0): everything built from integer / hash / sqrt / divide arithmetic, and reduce_noise (exp: glibc's
+    expf algorithm, k_libm.h) and vignette (powf(q, 2): the exact square);
+  * LIBM  (+-1 LSB, < 0.1 % of channels off): the two effects whose device libm rounds correctly where glibc does not
+    (twist: sin/cos, gaussian noise: ln/cos) — see k_effects2.hip's header.
+tests/test_gpu_libm_model.py holds all four to an exact model of the device's libm (oracle_lib.libm_flavour("device")).
 """
 import numpy as np
 import pytest
@@ -78,12 +80,12 @@ CASES = [
     ("add_noise", EXACT, dict(amount=30.0, noise_type="gaussian", monochrome=False, seed=42, scale=0.01, octaves=1)),  # colour branch is uniform
     ("add_noise", EXACT, dict(amount=50.0, noise_type="perlin", monochrome=False, seed=42, scale=5.0, octaves=3)),
     ("add_noise", EXACT, dict(amount=50.0, noise_type="perlin", monochrome=True, seed=1, scale=12.0, octaves=20)),
-    ("reduce_noise", LIBM, dict(strength=0.5, radius=2)),
-    ("reduce_noise", LIBM, dict(strength=40.0, radius=4)),
-    ("reduce_noise", LIBM, dict(strength=0.0, radius=0)),
-    ("vignette", LIBM, dict(amount=0.8, softness=0.5)),
-    ("vignette", LIBM, dict(amount=2.5, softness=0.0)),
-    ("vignette", LIBM, dict(amount=0.0, softness=0.5)),                                         # identity
+    ("reduce_noise", EXACT, dict(strength=0.5, radius=2)),
+    ("reduce_noise", EXACT, dict(strength=40.0, radius=4)),
+    ("reduce_noise", EXACT, dict(strength=0.0, radius=0)),
+    ("vignette", EXACT, dict(amount=0.8, softness=0.5)),
+    ("vignette", EXACT, dict(amount=2.5, softness=0.0)),
+    ("vignette", EXACT, dict(amount=0.0, softness=0.5)),                                         # identity
     ("halftone", EXACT, dict(dot_size=4.0, angle_deg=45.0, shape="circle")),
     ("halftone", EXACT, dict(dot_size=7.3, angle_deg=15.0, shape="square")),
     ("halftone", EXACT, dict(dot_size=1.0, angle_deg=-60.0, shape="diamond")),
@@ -184,7 +186,7 @@ def test_effects_small_and_wide_images(gpu, oracle):
         for name, cls, kw in (("bulge", EXACT, dict(amount=0.7)), ("ink", EXACT, dict(edge_strength=2.0, threshold=0.5)),
                               ("oil_painting", EXACT, dict(radius=2, levels=8)), ("crystallize", EXACT, dict(cell_size=4.0, seed=2)),
                               ("zoom_blur", EXACT, dict(center_x=0.5, center_y=0.5, strength=0.5, samples=4)),
-                              ("reduce_noise", LIBM, dict(strength=10.0, radius=3)), ("vignette", LIBM, dict(amount=0.9, softness=0.4)),
+                              ("reduce_noise", EXACT, dict(strength=10.0, radius=3)), ("vignette", EXACT, dict(amount=0.9, softness=0.4)),
                               ("dents", EXACT, dict(scale=3.0, amount=4.0, seed=1, octaves=2, roughness=0.5, wrap=True))):
             check(gpu.effect(name, img, **kw), oracle.effect(name, img, **kw), cls, f"{name} {w}x{h}")
 

@@ -666,7 +666,7 @@ def test_displacement_brushes_spread_over_a_large_field(gpu):
             gpu.r.displacement_brushes_dev(dev2, w, h, [d])
         one_by_one = gpu.r.dev_download(dev2, (h, w, 2), np.float32)
         assert np.array_equal(got.view(np.uint32), one_by_one.view(np.uint32))
-        assert np.allclose(got, ref, rtol=2e-6, atol=2e-6), float(np.abs(got - ref).max())
+        assert np.array_equal(got.view(np.uint32), ref.view(np.uint32)), float(np.abs(got - ref).max())
         untouched = ref.view(np.uint32) == start.view(np.uint32)
         assert np.array_equal(got.view(np.uint32)[untouched], start.view(np.uint32)[untouched])
     finally:
@@ -690,9 +690,8 @@ def test_displacement_brushes_on_a_device_field(gpu):
         gpu.r.displacement_brushes_dev(dev, w, h, dabs[:17])      # two calls: the field persists between dab batches
         gpu.r.displacement_brushes_dev(dev, w, h, dabs[17:])
         got = gpu.r.dev_download(dev, (h, w, 2), np.float32)
-        # weights use a device exp(): last-ulp differences per dab, accumulated over up to 43 overlapping dabs
-        assert np.allclose(got, ref, rtol=2e-6, atol=2e-6), float(np.abs(got - ref).max())
-        assert (got.view(np.uint32) == ref.view(np.uint32)).mean() > 0.98
+        # the weights' exp is glibc's expf bit for bit (k_libm.h): the field is the oracle's
+        assert np.array_equal(got.view(np.uint32), ref.view(np.uint32)), float(np.abs(got - ref).max())
         img = I.random_rgba(w, h, 5)
         src = gpu.r.dev_alloc(w * h * 4)
         dst = gpu.r.dev_alloc(w * h * 4)
@@ -703,8 +702,7 @@ def test_displacement_brushes_on_a_device_field(gpu):
         finally:
             gpu.r.dev_free(src)
             gpu.r.dev_free(dst)
-        d = np.abs(out.astype(int) - O.warp_displacement(img, ref).astype(int))
-        assert d.max() <= 1 and (d > 0).mean() < 1e-3
+        assert np.array_equal(out, O.warp_displacement(img, ref))
     finally:
         gpu.r.dev_free(dev)
 

@@ -19,6 +19,40 @@ namespace {
 PFX_DEV double as_f(uint64_t b) { return __builtin_bit_cast(double, b); }
 PFX_DEV uint64_t f_bits(double d) { return __builtin_bit_cast(uint64_t, d); }
 
+// BC_FPOW.  OCML's pow is within an ulp, but not exact where the result is a double: pow(3, 1) gave 2.9999999999999996 and pow(2, 11)
+// 2047.9999999999998, which a script's to_int / floor turns into 2 and 2047 (the host's glibc gives 3 and 2048).  An integer exponent takes an
+// exact route first: a base of +-2^k is ldexp (one rounding, subnormal results included); another finite base with 0 < n <= 64 is multiplied
+// out by squaring as long as fma shows every product exact and it stays clear of the subnormal range.  Everything else, the special
+// arguments included, is OCML's pow.
+PFX_DEV double vm_pow(double x, double y)
+{
+    if (isfinite(x) && x != 0.0 && fabs(y) <= 4096.0 && y == rint(y)) {
+        const int n = (int)y;
+        int k;
+        const double m = frexp(x, &k); // |m| in [0.5, 1)
+        if (fabs(m) == 0.5) {
+            const double r = ldexp(1.0, (k - 1) * n);
+            return (m < 0.0 && (n & 1)) ? -r : r;
+        }
+        if (n > 0 && n <= 64) {
+            auto exact_mul = [](double a, double b, double& p) {
+                p = a * b;
+                return isfinite(p) && fabs(p) >= 0x1p-900 && fma(a, b, -p) == 0.0;
+            };
+            double r = 1.0, b = x;
+            bool exact = true;
+            for (int e = n;;) {
+                if (e & 1) exact = exact_mul(r, b, r);
+                e >>= 1;
+                if (!e || !exact) break;
+                exact = exact_mul(b, b, b);
+            }
+            if (exact) return r;
+        }
+    }
+    return pow(x, y);
+}
+
 // LCODE: the program (12 bytes per instruction) is staged in LDS behind the register file — instruction fetch is then an LDS
 // read instead of a dependent global load per bytecode instruction, which is what the interpreter's time went into.
 // A workgroup walks over pixels with a grid stride so the staged program serves many pixels.
@@ -134,10 +168,12 @@ __global__ void vm_kernel(const pfxk_vm_args A)
         case BC_FDIV: R(I.dst) = f_bits(as_f(R(I.a)) / as_f(R(I.b))); break;
         case BC_FMOD: if constexpr (HEAVY) { R(I.dst) = f_bits(fmod(as_f(R(I.a)), as_f(R(I.b)))); } else err = 255; break;
         case BC_FNEG: R(I.dst) = R(I.a) ^ 0x8000000000000000ull; break;
-        case BC_FPOW: if constexpr (HEAVY) { R(I.dst) = f_bits(pow(as_f(R(I.a)), as_f(R(I.b)))); } else err = 255; break;
+        case BC_FPOW: if constexpr (HEAVY) { R(I.dst) = f_bits(vm_pow(as_f(R(I.a)), as_f(R(I.b)))); } else err = 255; break;
         case BC_FABS: R(I.dst) = R(I.a) & 0x7fffffffffffffffull; break;
-        case BC_FMIN: R(I.dst) = f_bits(fmin(as_f(R(I.a)), as_f(R(I.b)))); break;
-        case BC_FMAX: R(I.dst) = f_bits(fmax(as_f(R(I.a)), as_f(R(I.b)))); break;
+        // min / max as the host API defines them (pfx_script_host.cpp: fmin_first): a NaN operand yields the other one, equal operands (+0 and -0) the
+        // first.  The device's fmin orders -0 below +0, so min(0.0, -0.0) gave -0.0 where the host gives 0.0.
+        case BC_FMIN: { const double x = as_f(R(I.a)), y = as_f(R(I.b)); R(I.dst) = f_bits((y < x || x != x) ? y : x); break; }
+        case BC_FMAX: { const double x = as_f(R(I.a)), y = as_f(R(I.b)); R(I.dst) = f_bits((y > x || x != x) ? y : x); break; }
         case BC_FCLAMP: { double v = as_f(R(I.a)); const double lo = as_f(R(I.b)), hi = as_f(R(I.c)); if (v < lo) v = lo; if (v > hi) v = hi; R(I.dst) = f_bits(v); break; }
         case BC_FFLOOR: R(I.dst) = f_bits(floor(as_f(R(I.a)))); break;
         case BC_FCEIL: R(I.dst) = f_bits(ceil(as_f(R(I.a)))); break;

@@ -164,6 +164,9 @@ extern "C" int pfx_int_script_check_limited(const char* source, uint32_t w, uint
 #define PFX_CLOSURE_SHAPE_FIELDS 9
 extern "C" int pfx_int_script_closure_shape(const char* source, uint32_t w, uint32_t h, int64_t* out, int cap);
 extern "C" int pfx_int_script_check_console(const char* source, uint32_t w, uint32_t h, pfx_script_result* result, char* console, size_t cap, size_t* len);
+// the interpreter's f64 libm calls inside closure bodies: trace them, or answer them from a table (pfx_script_host.cpp)
+extern "C" int pfx_int_script_libm_hook(int mode, const uint64_t* table, size_t rows);
+extern "C" int pfx_int_script_libm_trace(uint64_t* out, size_t cap, size_t* n, uint64_t* misses);
 
 // run_one's script step on a document (pfx_project.cpp): pfx_project_run_script plus the console lines for --verbose
 int pfx_int_project_run_script(pfx_ctx* ctx, pfx_project* p, const char* source, pfx_script_result* result, std::vector<std::string>* console);

@@ -9,6 +9,8 @@
 #include "pfx_rhai.h"
 
 #include <algorithm>
+#include <array>
+#include <atomic>
 #include <cctype>
 #include <cerrno>
 #include <cmath>
@@ -16,6 +18,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <map>
+#include <mutex>
 #include <set>
 
 #include <pthread.h>
@@ -826,7 +830,7 @@ bool int_pow(int64_t base, int64_t e, int64_t& out)
     return true;
 }
 
-Value binary_op(const std::string& op, const Value& a, const Value& b, const Node& at)
+Value binary_op(const Interp& in, const std::string& op, const Value& a, const Value& b, const Node& at)
 {
     using V = Value;
     if (a.t == V::Int && b.t == V::Int) {
@@ -876,7 +880,7 @@ Value binary_op(const std::string& op, const Value& a, const Value& b, const Nod
         if (op == "*") return V::from_float(x * y);
         if (op == "/") return V::from_float(x / y);
         if (op == "%") return V::from_float(std::fmod(x, y));
-        if (op == "**") return V::from_float(b.t == V::Int ? std::pow(x, (double)b.i) : std::pow(x, y));
+        if (op == "**") return V::from_float(in.libm(LM_POW, x, y)); // an integer exponent is promoted like the other operand
         if (op == "==") return V::from_bool(x == y);
         if (op == "!=") return V::from_bool(x != y);
         if (op == "<") return V::from_bool(x < y);
@@ -1051,6 +1055,7 @@ struct Eval {
 
     Value call_closure(const Closure& c, std::vector<Value>& args, const Node& at)
     {
+        struct Level { Interp& i; explicit Level(Interp& x) : i(x) { ++i.closure_level; } ~Level() { --i.closure_level; } } level(in);
         if (!c.fn_name.empty()) {
             auto it = in.fns_.find(c.fn_name + "/" + std::to_string(args.size()));
             if (it == in.fns_.end()) fail("Function not found: " + signature(c.fn_name, args), at);
@@ -1109,8 +1114,8 @@ struct Eval {
         }
         if (n == 1 && is(0, V::Float)) { // f64 methods of the standard library not re-registered by the host
             const double x = a[0].f;
-            if (name == "exp") { out = V::from_float(std::exp(x)); return true; }
-            if (name == "ln") { out = V::from_float(std::log(x)); return true; }
+            if (name == "exp") { out = V::from_float(in.libm(LM_EXP, x)); return true; }
+            if (name == "ln") { out = V::from_float(in.libm(LM_LN, x)); return true; }
             if (name == "log10" || name == "log") { out = V::from_float(std::log10(x)); return true; }
             if (name == "asin") { out = V::from_float(std::asin(x)); return true; }
             if (name == "acos") { out = V::from_float(std::acos(x)); return true; }
@@ -1273,7 +1278,7 @@ struct Eval {
         case NK::Binary: {
             Value a = eval(*n.kids[0]);
             Value b = eval(*n.kids[1]);
-            return binary_op(n.text, a, b, n);
+            return binary_op(in, n.text, a, b, n);
         }
         case NK::And: {
             if (!truthy(eval(*n.kids[0]), n)) return Value::from_bool(false);
@@ -1347,7 +1352,7 @@ struct Eval {
             Value* dst = lvalue(*n.kids[0], is_const);
             if (is_const) fail("Cannot modify constant: " + (n.kids[0]->k == NK::Var ? n.kids[0]->text : std::string("<indexed>")), n);
             if (n.text == "=") *dst = rhs.copy();
-            else *dst = binary_op(n.text.substr(0, n.text.size() - 1), *dst, rhs, n);
+            else *dst = binary_op(in, n.text.substr(0, n.text.size() - 1), *dst, rhs, n);
             if (n.kids[0]->k == NK::Index && dst->t == Value::Array) { // an array stored into an element: the whole container is what the limit measures
                 const Node* root = n.kids[0].get();
                 while (root->k == NK::Index) root = root->kids[0].get();
@@ -1479,6 +1484,76 @@ bool Interp::run_here(const char* source, Error& err)
         err = {std::string("script runtime: ") + e.what(), 0, 0, ST_SCRIPT};
         return false;
     }
+}
+
+// ---- the libm seam (pfx_rhai.h).  While it is off, no call takes its lock.
+namespace {
+struct LibmHook {
+    std::atomic<int> mode{LIBM_OFF};
+    std::mutex mu;
+    std::set<std::array<uint64_t, 3>> trace;
+    std::map<std::array<uint64_t, 3>, uint64_t> table;
+    uint64_t misses = 0;
+};
+LibmHook& libm_hook()
+{
+    static LibmHook h;
+    return h;
+}
+double bits_f(uint64_t b) { double d; std::memcpy(&d, &b, 8); return d; }
+uint64_t f_bits(double d) { uint64_t b; std::memcpy(&b, &d, 8); return b; }
+} // namespace
+
+void libm_hook_set(int mode, const uint64_t* table, size_t rows)
+{
+    LibmHook& h = libm_hook();
+    std::lock_guard<std::mutex> g(h.mu);
+    h.trace.clear();
+    h.table.clear();
+    h.misses = 0;
+    for (size_t k = 0; table && k < rows; ++k) h.table[{table[4 * k], table[4 * k + 1], table[4 * k + 2]}] = table[4 * k + 3];
+    h.mode.store(mode == LIBM_TRACE || mode == LIBM_OVERRIDE ? mode : LIBM_OFF);
+}
+
+size_t libm_hook_trace(uint64_t* out, size_t cap_rows, uint64_t* misses)
+{
+    LibmHook& h = libm_hook();
+    std::lock_guard<std::mutex> g(h.mu);
+    size_t k = 0;
+    for (const auto& r : h.trace) {
+        if (k < cap_rows && out) for (int j = 0; j < 3; ++j) out[3 * k + j] = r[j];
+        ++k;
+    }
+    if (misses) *misses = h.misses;
+    return k;
+}
+
+double Interp::libm(LibmOp op, double x, double y) const
+{
+    auto glibc = [&]() {
+        switch (op) {
+        case LM_POW: return std::pow(x, y);
+        case LM_SIN: return std::sin(x);
+        case LM_COS: return std::cos(x);
+        case LM_TAN: return std::tan(x);
+        case LM_ATAN2: return std::atan2(x, y);
+        case LM_EXP: return std::exp(x);
+        default: return std::log(x);
+        }
+    };
+    LibmHook& h = libm_hook();
+    const int mode = h.mode.load(std::memory_order_relaxed);
+    if (mode == LIBM_OFF || closure_level == 0) return glibc();
+    const bool two = op == LM_POW || op == LM_ATAN2;
+    const std::array<uint64_t, 3> key = {(uint64_t)op, f_bits(x), two ? f_bits(y) : 0};
+    std::lock_guard<std::mutex> g(h.mu);
+    h.trace.insert(key);
+    if (mode == LIBM_OVERRIDE) {
+        auto it = h.table.find(key);
+        if (it != h.table.end()) return bits_f(it->second);
+        ++h.misses;
+    }
+    return glibc();
 }
 
 bool Interp::run(const char* source, Error& err)

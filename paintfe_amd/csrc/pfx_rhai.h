@@ -123,6 +123,15 @@ struct BcProgram {
     int n_pre = 0;    // code[0 .. n_pre) are LOADKs into registers nothing else writes: a lane runs them once, every pixel starts at n_pre (hoist_constants)
 };
 
+// ---- test seam: the f64 libm calls of closure bodies (pfx_int_script_libm_hook) ------------------------------------------
+// The interpreter's pow / `**`, sin, cos, tan, atan2, exp and ln go through libm(): glibc, unless the seam is on and the call is made while a closure body
+// (or a script fn called from one) is being evaluated.  Then mode 1 records (op, bits of x, bits of y) and mode 2 also answers from a table of results
+// (the device's libm, measured by the tests), falling back to glibc and counting a miss for a call it does not hold.  Off by default.
+enum LibmOp : uint64_t { LM_POW = 0, LM_SIN, LM_COS, LM_TAN, LM_ATAN2, LM_EXP, LM_LN };
+enum LibmHookMode : int { LIBM_OFF = 0, LIBM_TRACE, LIBM_OVERRIDE };
+void libm_hook_set(int mode, const uint64_t* table, size_t rows); // table rows: op, x bits, y bits, result bits
+size_t libm_hook_trace(uint64_t* out, size_t cap_rows, uint64_t* misses); // distinct (op, x bits, y bits) rows since the last set, sorted; returns their count
+
 // ---- host interface -----------------------------------------------------------------------------------------------------
 class Interp;
 struct Host {
@@ -146,6 +155,11 @@ public:
     // host-side call of a closure / fn pointer (used by nothing on the pixel path; available for completeness)
     bool call_closure(const Closure& c, std::vector<Value>& args, Value& out, Error& err);
     static const char* bc_error_text(int code);
+    // closure bodies being evaluated: the libm seam applies inside them only.  Every call of a closure counts, one made with .call() at the
+    // script's top level included — that is how the tests' host reference drives the pixel closure — so a script whose header calls a closure
+    // sees the seam there too, although the device receives that value from the host; the corpus makes no such calls
+    int closure_level = 0;
+    double libm(LibmOp op, double x, double y = 0.0) const;
 
 private:
     friend struct Eval;

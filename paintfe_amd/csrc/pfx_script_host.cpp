@@ -37,6 +37,11 @@ namespace {
 
 using VT = Value::T;
 
+// min / max of two floats (and BC_FMIN / BC_FMAX in k_script.hip): a NaN operand yields the other one, equal operands (+0 and -0) the first.  C and
+// IEEE 754-2008 leave the sign of min(+0, -0) open; spelled out here so that the interpreter and the VM agree whatever the compilers inline.
+double fmin_first(double x, double y) { return (y < x || x != x) ? y : x; }
+double fmax_first(double x, double y) { return (y > x || x != x) ? y : x; }
+
 bool program_is_heavy(const rhai::BcProgram& p)
 {
     for (const rhai::BcIns& ins : p.code) if (rhai::bc_heavy_op(ins.op)) return true;
@@ -458,16 +463,17 @@ int ScriptHost::call(rhai::Interp& in, const std::string& name, std::vector<Valu
     }
     for (const char* nm : {"min", "min_i"}) FN(nm) if (sig({VT::Int, VT::Int})) { out = Value::from_int(std::min(a[0].i, a[1].i)); return 2; }
     for (const char* nm : {"max", "max_i"}) FN(nm) if (sig({VT::Int, VT::Int})) { out = Value::from_int(std::max(a[0].i, a[1].i)); return 2; }
-    for (const char* nm : {"min", "min_f"}) FN(nm) if (sig({VT::Float, VT::Float})) { out = Value::from_float(std::fmin(a[0].f, a[1].f)); return 2; }
-    for (const char* nm : {"max", "max_f"}) FN(nm) if (sig({VT::Float, VT::Float})) { out = Value::from_float(std::fmax(a[0].f, a[1].f)); return 2; }
+    for (const char* nm : {"min", "min_f"}) FN(nm) if (sig({VT::Float, VT::Float})) { out = Value::from_float(fmin_first(a[0].f, a[1].f)); return 2; }
+    for (const char* nm : {"max", "max_f"}) FN(nm) if (sig({VT::Float, VT::Float})) { out = Value::from_float(fmax_first(a[0].f, a[1].f)); return 2; }
     FN("abs_i") if (sig({VT::Int})) { out = Value::from_int(a[0].i < 0 ? (int64_t)(0ull - (uint64_t)a[0].i) : a[0].i); return 2; }
     {
-        struct { const char* n; double (*f)(double); } f1[] = {{"floor", std::floor}, {"ceil", std::ceil}, {"round", std::round}, {"sqrt", std::sqrt},
-                                                               {"sin", std::sin}, {"cos", std::cos}, {"tan", std::tan}};
+        struct { const char* n; double (*f)(double); } f1[] = {{"floor", std::floor}, {"ceil", std::ceil}, {"round", std::round}, {"sqrt", std::sqrt}};
         for (const auto& e : f1) FN(e.n) if (sig({VT::Float})) { out = Value::from_float(e.f(a[0].f)); return 2; }
+        struct { const char* n; rhai::LibmOp op; } lm[] = {{"sin", rhai::LM_SIN}, {"cos", rhai::LM_COS}, {"tan", rhai::LM_TAN}};
+        for (const auto& e : lm) FN(e.n) if (sig({VT::Float})) { out = Value::from_float(in.libm(e.op, a[0].f)); return 2; }
     }
-    FN("pow") if (sig({VT::Float, VT::Float})) { out = Value::from_float(std::pow(a[0].f, a[1].f)); return 2; }
-    FN("atan2") if (sig({VT::Float, VT::Float})) { out = Value::from_float(std::atan2(a[0].f, a[1].f)); return 2; }
+    FN("pow") if (sig({VT::Float, VT::Float})) { out = Value::from_float(in.libm(rhai::LM_POW, a[0].f, a[1].f)); return 2; }
+    FN("atan2") if (sig({VT::Float, VT::Float})) { out = Value::from_float(in.libm(rhai::LM_ATAN2, a[0].f, a[1].f)); return 2; }
     FN("PI") if (sig({})) { out = Value::from_float(3.14159265358979323846); return 2; }
     FN("rgb_to_hsl") if (sig({VT::Int, VT::Int, VT::Int})) { // :1295-1327
         const double rf = (double)clamp_u8(a[0].i) / 255.0, gf = (double)clamp_u8(a[1].i) / 255.0, bf = (double)clamp_u8(a[2].i) / 255.0;
@@ -739,6 +745,24 @@ int pfx_int_script_check_console(const char* source, uint32_t w, uint32_t h, pfx
     std::memcpy(console, joined.data(), n);
     console[n] = 0;
     return ok ? PFX_OK : (err.status ? err.status : PFX_ERR_SCRIPT);
+}
+
+// Test seam: the interpreter's libm calls inside closure bodies (pfx_rhai.h, libm_hook_set).  mode 0 off, 1 trace, 2 trace and answer from `table`
+// (rows of op, x bits, y bits, result bits; op as rhai::LibmOp); either clears the trace.  The hook is process-wide: set it back to 0 after use.
+int pfx_int_script_libm_hook(int mode, const uint64_t* table, size_t rows)
+{
+    if (mode < rhai::LIBM_OFF || mode > rhai::LIBM_OVERRIDE || (rows && !table)) return PFX_ERR_INVALID;
+    rhai::libm_hook_set(mode, table, rows);
+    return PFX_OK;
+}
+
+// the distinct (op, x bits, y bits) calls recorded since the last pfx_int_script_libm_hook, sorted, up to cap rows into out; *n receives their count and
+// *misses the override mode's calls that were not in its table
+int pfx_int_script_libm_trace(uint64_t* out, size_t cap, size_t* n, uint64_t* misses)
+{
+    if (!n || (cap && !out)) return PFX_ERR_INVALID;
+    *n = rhai::libm_hook_trace(out, cap, misses);
+    return PFX_OK;
 }
 
 } // extern "C"

@@ -7,8 +7,10 @@ reference tree: parity is anchored on the reference's call sites, tests and gold
 import numpy as np
 import pytest
 
+from . import closure_ref as R
 from . import inputs as I
 from . import oracle_lib as O
+from . import vm_libm_probe as P
 
 pytestmark = pytest.mark.gpu
 
@@ -288,6 +290,18 @@ def test_closure_float_math(r):
     exp = np.stack([np.clip(v, 0, 255) for v in ref(None, None, c[..., 0], c[..., 1], c[..., 2], c[..., 3])], -1).astype(np.uint8)
     d = np.abs(out.astype(int) - exp.astype(int))
     assert d.max() <= 1 and (d > 0).mean() < 1e-3  # pow() on the device vs numpy's libm: last-ulp differences before floor()
+    # exact: the host interpreter with the device's pow results substituted (tests/vm_libm_probe.py)
+    clo = src.strip()[len("map_channels("):-2]
+    h, w = img.shape[:2]
+    px = [tuple(int(v) for v in img[y, x]) for y in range(h) for x in range(w)]
+
+    def host():
+        lines, err = R.check_console(f"let f = {clo};\n" + "\n".join(f"print(f.call({a}, {b}, {c}, {e}));" for a, b, c, e in px))
+        return [R.parse_result(s) for s in lines], err
+    (_, err), sub, table = P.substituted(r, host)
+    assert err is None and sub is not None and sub[1] is None and table
+    want = np.array([R.write_back(old, res) for old, res in zip(px, sub[0])], np.uint8).reshape(h, w, 4)
+    assert np.array_equal(out, want), int(np.count_nonzero(out != want))
 
 
 def test_closure_reads_neighbours_from_the_pre_call_image(r):

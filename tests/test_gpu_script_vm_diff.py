@@ -1,8 +1,10 @@
 """Differential test of the script VM (k_script.hip: vm_kernel) against the host interpreter (pfx_rhai.cpp: Interp), on the seeded
 closure corpus of tests/closure_gen.py.  The host runs the same closure text on the same inputs (tests/closure_ref.py), pixel by
 pixel, and the bulk iterators' write-back rule turns its results into the expected image.  Result elements that do not touch
-pow / sin / cos / tan / atan2 / exp / ln are held bit-exact; the others may differ by 1 on fewer than 0.1 % of them.  A failing
-closure must fail on the device with the host's message, at the host's line, for the first failing pixel in row-major order."""
+pow / sin / cos / tan / atan2 / exp / ln are held bit-exact; the others may differ by 1 on fewer than 0.1 % of them from the host with
+glibc (the contract against the reference), and must equal at tolerance 0 the host run again with the device's libm results substituted for
+the calls it traced (tests/vm_libm_probe.py: the libm seam and the device probe).  A failing closure must fail on the device with the host's
+message, at the host's line, for the first failing pixel in row-major order."""
 import numpy as np
 import pytest
 
@@ -10,6 +12,7 @@ from paintfe_amd import PfxError
 
 from . import closure_gen as G
 from . import closure_ref as R
+from . import vm_libm_probe as P
 
 pytestmark = pytest.mark.gpu
 
@@ -63,6 +66,16 @@ def compare(p, out, exp, pixels, what):
             assert d.max(initial=0) <= 1 and np.count_nonzero(d) <= 0.001 * d.size, (what, c, int(d.max()), int(np.count_nonzero(d)))
 
 
+def compare_substituted(p, out, exp_sub, pixels, what):
+    """every element, libm or not, equals the host run with the device's libm: tolerance 0"""
+    ys = np.array([y for _, y in pixels], dtype=np.int64)
+    xs = np.array([x for x, _ in pixels], dtype=np.int64)
+    got, want = out[ys, xs], exp_sub[ys, xs]
+    bad = np.nonzero((got != want).any(axis=1))[0]
+    assert bad.size == 0, (f"{what}: {bad.size} pixels differ from the host with the device's libm, first (x, y) = {pixels[bad[0]]}: "
+                           f"device {got[bad[0]]} host {want[bad[0]]}\n{p.device_script()}")
+
+
 def check_errors(dev_err, host_err, src):
     assert dev_err is not None, f"the host fails with {host_err}, the device does not\n{src}"
     assert dev_err[0] == -6 and host_err[0] == -6, (dev_err, host_err)
@@ -81,7 +94,7 @@ def test_small_corpus_matches_host(r, chunk):
         w, h = p.width, p.height
         img, mask = R.image(w, h)
         x0, y0, x1, y1 = clip_region(p, w, h)
-        results, host_err = R.host_loop(p, (x0, y0, x1, y1), w, h)
+        (results, host_err), sub, _ = P.substituted(r, lambda: R.host_loop(p, (x0, y0, x1, y1), w, h))
         src = p.device_script()
         out, dev_err = device_run(r, src, img, mask)
         if host_err is not None:
@@ -96,6 +109,9 @@ def test_small_corpus_matches_host(r, chunk):
         outside[y0:y1, x0:x1] = False
         assert np.array_equal(out[outside], img[outside]), f"seed {seed}: pixels outside the region changed"
         compare(p, out, exp, pixels, f"seed {seed}")
+        if sub is not None:
+            assert sub[1] is None, (seed, sub[1])
+            compare_substituted(p, out, expected_image(img, pixels, sub[0]), pixels, f"seed {seed}")
 
 
 # ---------------------------------------------------------------- launch geometry
@@ -150,13 +166,16 @@ def test_geometry_classes_against_host(r, record_property):
             img, mask = R.image(w, h)
             out, dev_err = device_run(r, q.device_script(), img, mask)
             pixels = sample_pixels(w, h, lanes, rng)
-            results, host_err = R.host_run(q, pixels, w, h)
+            (results, host_err), sub, _ = P.substituted(r, lambda: R.host_run(q, pixels, w, h))
             if host_err is not None:
                 # the host stops at the first failing pixel of the sample; the device reports the first of the frame: same kind, not before it
                 assert dev_err is not None and dev_err[0] == -6, (key, (w, h), host_err, dev_err)
                 continue
             assert dev_err is None, (key, (w, h), dev_err)
             compare(q, out, expected_image(img, pixels, results), pixels, f"class {key} frame {w}x{h} seed {q.seed}")
+            if sub is not None:
+                assert sub[1] is None, (key, (w, h), sub[1])
+                compare_substituted(q, out, expected_image(img, pixels, sub[0]), pixels, f"class {key} frame {w}x{h} seed {q.seed}")
 
 
 def test_whole_frame_equals_four_region_bands(r):
@@ -225,3 +244,46 @@ def test_vm_error_texts_match_host(r, expr, msg):
     assert out is None and dev_err == (-6, 2, msg)
     host = R.check_console(f"let f = |r, g, b, a| {{\n    let v = {expr};\n    [v, g, b, a]\n}};\nprint(f.call(1, 7, 2, 0));")[1]
     assert host[1] == 2 and R.same_error(msg, host[2]), host
+
+
+# ---------------------------------------------------------------- negative control of the exact comparison
+NUDGES = [1 << j for j in range(0, 53, 2)]
+NUDGE_DETECTED = 1 << 42     # measured: the smallest nudge the corpus detects
+
+
+def test_nudged_libm_table_is_detected(r, record_property):
+    """the substituted comparison is not vacuous: the device's libm results nudged by k ulps make the corpus differ from the device.  The smallest
+    k (of 1, 4, 16, ..) that some corpus program detects is recorded"""
+    runs = []
+    for seed in SMALL:
+        p = G.generate(seed)
+        if not any(p.libm[:4]):
+            continue
+        w, h = p.width, p.height
+        img, mask = R.image(w, h)
+        x0, y0, x1, y1 = clip_region(p, w, h)
+        run = (lambda p=p, reg=(x0, y0, x1, y1), w=w, h=h: R.host_loop(p, reg, w, h))
+        (results, host_err), sub, table = P.substituted(r, run)
+        if host_err is not None or sub is None:
+            continue
+        out, dev_err = device_run(r, p.device_script(), img, mask)
+        assert dev_err is None
+        pixels = [(x, y) for y in range(y0, y1) for x in range(x0, x1)]
+        runs.append((p, img, pixels, out, run, table))
+        if len(runs) == 24:
+            break
+    assert runs, "no corpus program with libm-dependent channels"
+    detected = None
+    for k in NUDGES:
+        for p, img, pixels, out, run, table in runs:
+            with P.traced(P.nudge(table, k)):
+                res, err = run()
+            if err is not None or not np.array_equal(expected_image(img, pixels, res)[tuple(np.array(pixels).T[::-1])],
+                                                     out[tuple(np.array(pixels).T[::-1])]):
+                detected = k
+                break
+        if detected is not None:
+            break
+    record_property("smallest_detected_nudge_ulps", detected)
+    print(f"smallest nudge detected over {len(runs)} corpus programs: {detected} ulps")
+    assert detected is not None and detected <= NUDGE_DETECTED

@@ -357,7 +357,28 @@ __global__ __launch_bounds__(GF_T) void gauss_plane_exact_kernel(const uint8_t* 
 
 int g_fused_exact = 1; // pfxk_gauss_set_fused_exact (pfx_tune "gauss_fused_exact"): 0 = the bit-exact mode always through the two kernels (A/B, parity tests)
 extern "C" void pfxk_gauss_set_fused_exact(int on) { g_fused_exact = on; }
-extern "C" int pfxk_gauss_fused_exact_max_radius(void) { return g_fused_exact ? GF_MAXR : 0; }
+extern "C" int pfxk_gauss_fused_exact_enabled(void) { return g_fused_exact != 0; }   // the knob: read where the path is chosen (pfx_gauss.cpp)
+extern "C" int pfxk_gauss_fused_exact_max_radius(void) { return GF_MAXR; }           // the compiled limit, whatever the knob says
+
+// launch geometry of both forms: strips of GF_W columns (pixels, or quads of the plane form), and row segments so that there is one round of workgroups per
+// XCD (32 CUs x what the LDS footprint allows), segments of at least 8r + 64 rows (the 2r rows of run-in stay small)
+struct gf_geometry { int strips, nseg, seg_rows; dim3 grid; };
+static gf_geometry gf_geometry_for(int cols, int h, int radius, size_t lds)
+{
+    gf_geometry g; g.strips = (cols + GF_W - 1) / GF_W;
+    const int wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160u * 1024u) / lds));
+    const int sg_max = (g.strips + 7) / 8;
+    g.nseg = std::min(std::max(1, 32 * wg_per_cu / sg_max), std::max(1, h / (8 * radius + 64)));
+    g.seg_rows = (h + g.nseg - 1) / g.nseg;
+    g.nseg = (h + g.seg_rows - 1) / g.seg_rows;
+    g.grid = dim3(8u * (uint32_t)(sg_max * g.nseg));
+    return g;
+}
+// `return go(std::integral_constant<int, radius>{})` for the radii both kernels are instantiated for
+static_assert(GF_MAXR == 16, "gauss_fused_exact_kernel / gauss_plane_exact_kernel are instantiated for radii 1 .. 16");
+#define PFX_GF_CASE(R) case R: return go(std::integral_constant<int, R>{});
+#define PFX_GF_DISPATCH(radius) switch (radius) { PFX_GF_CASE(1) PFX_GF_CASE(2) PFX_GF_CASE(3) PFX_GF_CASE(4) PFX_GF_CASE(5) PFX_GF_CASE(6) PFX_GF_CASE(7) PFX_GF_CASE(8) PFX_GF_CASE(9) PFX_GF_CASE(10) PFX_GF_CASE(11) PFX_GF_CASE(12) PFX_GF_CASE(13) PFX_GF_CASE(14) PFX_GF_CASE(15) PFX_GF_CASE(16) default: return hipErrorInvalidValue; }
+
 static hipError_t launch_fused_exact(hipStream_t stream, const uint8_t* d_src, uint8_t* d_dst, const float* d_wts_tap0, int radius, uint32_t w, uint32_t h,
                                      int epilogue /* 0 blur, 1 sharpen, 2 glow, 3 chain */, float p0, const uint8_t* d_mask, const pfxk_chain* chain, const uint8_t* d_luts)
 {
@@ -366,28 +387,20 @@ static hipError_t launch_fused_exact(hipStream_t stream, const uint8_t* d_src, u
     if (epilogue == 3 && (!chain || chain->n > PFXK_CHAIN_MAX || chain->n_luts > PFXK_CHAIN_LUTS || (chain->n_luts && !d_luts))) return hipErrorInvalidValue;
     const int RR = 2 * radius + 1 + GF_RB;
     const size_t lds = (size_t)RR * GF_W * 16 + (size_t)GF_RB * gf_src_pitch(radius) * 4 + (epilogue == 3 ? (size_t)chain->n_luts * 1024 : 0);
-    const int strips = (int)((w + GF_W - 1) / GF_W);
-    // one round of workgroups per XCD (32 CUs x what the LDS footprint allows), segments of at least 8r + 64 rows (the 2r rows of run-in stay small)
-    const int wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160u * 1024u) / lds));
-    const int sg_max = (strips + 7) / 8;
-    int nseg = std::max(1, 32 * wg_per_cu / sg_max);
-    nseg = std::min(nseg, std::max(1, (int)h / (8 * radius + 64)));
-    const int seg_rows = ((int)h + nseg - 1) / nseg;
-    nseg = ((int)h + seg_rows - 1) / seg_rows;
-    const dim3 grid(8u * (uint32_t)(sg_max * nseg));
+    const gf_geometry g = gf_geometry_for((int)w, (int)h, radius, lds);
     auto go2 = [&](auto rc, auto ec) -> hipError_t {
         constexpr int R = decltype(rc)::value, E = decltype(ec)::value;
         static lds_grant grant;   // one per (R, E) instantiation
         if constexpr (E == 3) {
             hipError_t e = grant_lds(grant, (const void*)gauss_fused_exact_kernel<R, 3, pfxk_chain>, lds);
             if (e) return e;
-            gauss_fused_exact_kernel<R, 3, pfxk_chain><<<grid, GF_T, lds, stream>>>(*chain, (const uint32_t*)d_src, (uint32_t*)d_dst, d_wts_tap0, (int)w, (int)h, seg_rows, nseg, strips,
-                                                                                    nullptr, 0.0f, d_luts);
+            gauss_fused_exact_kernel<R, 3, pfxk_chain><<<g.grid, GF_T, lds, stream>>>(*chain, (const uint32_t*)d_src, (uint32_t*)d_dst, d_wts_tap0, (int)w, (int)h, g.seg_rows, g.nseg, g.strips,
+                                                                                      nullptr, 0.0f, d_luts);
         } else {
             hipError_t e = grant_lds(grant, (const void*)gauss_fused_exact_kernel<R, E>, lds);
             if (e) return e;
-            gauss_fused_exact_kernel<R, E><<<grid, GF_T, lds, stream>>>(gf_no_chain{}, (const uint32_t*)d_src, (uint32_t*)d_dst, d_wts_tap0, (int)w, (int)h, seg_rows, nseg, strips, d_mask, p0,
-                                                                        nullptr);
+            gauss_fused_exact_kernel<R, E><<<g.grid, GF_T, lds, stream>>>(gf_no_chain{}, (const uint32_t*)d_src, (uint32_t*)d_dst, d_wts_tap0, (int)w, (int)h, g.seg_rows, g.nseg, g.strips, d_mask, p0,
+                                                                          nullptr);
         }
         return hipGetLastError();
     };
@@ -397,13 +410,7 @@ static hipError_t launch_fused_exact(hipStream_t stream, const uint8_t* d_src, u
         if (epilogue == 3) return go2(rc, std::integral_constant<int, 3>{});
         return go2(rc, std::integral_constant<int, 0>{});
     };
-    static_assert(GF_MAXR == 16, "gauss_fused_exact_kernel is instantiated for radii 1 .. 16");
-    switch (radius) {
-#define PFX_GF(R) case R: return go(std::integral_constant<int, R>{});
-        PFX_GF(1) PFX_GF(2) PFX_GF(3) PFX_GF(4) PFX_GF(5) PFX_GF(6) PFX_GF(7) PFX_GF(8) PFX_GF(9) PFX_GF(10) PFX_GF(11) PFX_GF(12) PFX_GF(13) PFX_GF(14) PFX_GF(15) PFX_GF(16)
-#undef PFX_GF
-    default: return hipErrorInvalidValue;
-    }
+    PFX_GF_DISPATCH(radius)
 }
 extern "C" hipError_t pfxk_gauss_fused_exact(hipStream_t stream, const uint8_t* d_src, uint8_t* d_dst, const float* d_wts_tap0, int radius, uint32_t w, uint32_t h,
                                              int epilogue /* 0 blur, 1 sharpen, 2 glow */, float p0, const uint8_t* d_mask)
@@ -424,26 +431,14 @@ extern "C" hipError_t pfxk_gauss_plane_exact(hipStream_t stream, const uint8_t* 
     if (radius < 1 || radius > GF_MAXR || (w & 3u) != 0 || ((uintptr_t)d_src & 3u) || ((uintptr_t)d_dst & 3u)) return hipErrorInvalidValue;
     const int RR = 2 * radius + 1 + GF_RB, R4 = (radius + 3) & ~3, ND = (4 * GF_W + 2 * R4) / 4, SPD = ND + 1 + ((4 - ((ND + 1) & 3)) & 3) + 1;
     const size_t lds = (size_t)RR * GF_W * 16 + (size_t)GF_RB * SPD * 4;
-    const int wq = (int)(w >> 2), strips = (wq + GF_W - 1) / GF_W;
-    const int wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160u * 1024u) / lds));
-    const int sg_max = (strips + 7) / 8;
-    int nseg = std::max(1, 32 * wg_per_cu / sg_max);
-    nseg = std::min(nseg, std::max(1, (int)h / (8 * radius + 64)));
-    const int seg_rows = ((int)h + nseg - 1) / nseg;
-    nseg = ((int)h + seg_rows - 1) / seg_rows;
-    const dim3 grid(8u * (uint32_t)(sg_max * nseg));
+    const gf_geometry g = gf_geometry_for((int)(w >> 2), (int)h, radius, lds);
     auto go = [&](auto rc) -> hipError_t {
         constexpr int R = decltype(rc)::value;
         static lds_grant grant;
         hipError_t e = grant_lds(grant, (const void*)gauss_plane_exact_kernel<R>, lds);
         if (e) return e;
-        gauss_plane_exact_kernel<R><<<grid, GF_T, lds, stream>>>(d_src, d_dst, d_wts_tap0, (int)w, (int)h, seg_rows, nseg, strips);
+        gauss_plane_exact_kernel<R><<<g.grid, GF_T, lds, stream>>>(d_src, d_dst, d_wts_tap0, (int)w, (int)h, g.seg_rows, g.nseg, g.strips);
         return hipGetLastError();
     };
-    switch (radius) {
-#define PFX_GP(R) case R: return go(std::integral_constant<int, R>{});
-        PFX_GP(1) PFX_GP(2) PFX_GP(3) PFX_GP(4) PFX_GP(5) PFX_GP(6) PFX_GP(7) PFX_GP(8) PFX_GP(9) PFX_GP(10) PFX_GP(11) PFX_GP(12) PFX_GP(13) PFX_GP(14) PFX_GP(15) PFX_GP(16)
-#undef PFX_GP
-    default: return hipErrorInvalidValue;
-    }
+    PFX_GF_DISPATCH(radius)
 }

@@ -40,27 +40,16 @@ int check_img(pfx_ctx* ctx, const void* src, const void* dst, uint32_t w, uint32
 // Aliasing rule of the `_dev` entry points (include/pfx.h): src == dst is allowed where the header says so; buffers that overlap in
 // any other way, or at all for a neighbourhood operation, are refused — a kernel that reads a halo while other workgroups write the
 // same memory would race silently.
-bool ranges_overlap(const void* a, const void* b, size_t bytes)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + bytes && y < x + bytes;
-}
-bool ranges_overlap2(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + b_bytes && y < x + a_bytes;
-}
 int check_disjoint(pfx_ctx* ctx, const void* src, const void* dst, uint32_t w, uint32_t h, const char* who, bool same_ok = false)
 {
     if (src == dst) return same_ok ? PFX_OK : pfx_fail(ctx, PFX_ERR_INVALID, "%s: src and dst must be different buffers", who);
-    if (ranges_overlap(src, dst, (size_t)w * h * 4))
-        return pfx_fail(ctx, PFX_ERR_INVALID, "%s: src and dst overlap", who);
+    if (pfx_ranges_overlap(src, img_bytes(w, h), dst, img_bytes(w, h))) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: src and dst overlap", who);
     return PFX_OK;
 }
 // the same for a source whose extent differs from the destination's (the warps sample an sw x sh image into a w x h one)
 int check_disjoint2(pfx_ctx* ctx, const void* src, uint32_t sw, uint32_t sh, const void* dst, uint32_t w, uint32_t h, const char* who)
 {
-    if (ranges_overlap2(src, (size_t)sw * sh * 4, dst, (size_t)w * h * 4)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: src and dst overlap", who);
+    if (pfx_ranges_overlap(src, img_bytes(sw, sh), dst, img_bytes(w, h))) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: src and dst overlap", who);
     return PFX_OK;
 }
 
@@ -292,7 +281,7 @@ int flatten_common(pfx_ctx* ctx, const void* const* layer_ptrs, const void* cons
     // a workgroup would read pixels another one has already replaced
     if (!from_store && layer_ptrs && dst_dev)
         for (uint32_t l = 0; l < n_layers; ++l)
-            if (layer_ptrs[l] && layer_ptrs[l] != dst_dev && ranges_overlap(layer_ptrs[l], dst_dev, img_bytes(w, h)))
+            if (layer_ptrs[l] && layer_ptrs[l] != dst_dev && pfx_ranges_overlap(layer_ptrs[l], img_bytes(w, h), dst_dev, img_bytes(w, h)))
                 return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_flatten_dev: dst partially overlaps layer %u (it may be a layer, or disjoint from all)", l);
     uint32_t n_desc = 0, active_pos = 0xFFFFFFFFu;
     const uint8_t* active_pixels = nullptr;
@@ -459,58 +448,6 @@ int pfx_int_flatten_with_chunk_keys_dev(pfx_ctx* ctx, const void* const* layer_p
     return flatten_common(ctx, layer_ptrs_dev, nullptr, layers, n_layers, w, h, false, dst_dev, nullptr, nullptr, chunk_keys_host);
 }
 
-// sharpen / glow with the Gaussian and the combine in ONE kernel (k_gauss_exact.hip, epilogue 1 / 2) where the bit-exact fused Gaussian applies: radius 1 .. 16,
-// distinct buffers, exact mode.  Returns 1 when it ran, 0 when the caller has to take the two-step path, < 0 on error.
-// the f32 taps of sigma on the device (cached per context): *wts points at tap 0, pfxk_gauss_weight_pad() zero taps on both sides
-int pfx_int_gauss_exact_weights(pfx_ctx* ctx, float sigma, const float** wts)
-{
-    uint32_t sigma_bits; std::memcpy(&sigma_bits, &sigma, 4);
-    const int pad = pfxk_gauss_weight_pad();
-    if (!ctx->wts_valid || ctx->wts_sigma_bits != sigma_bits) {
-        std::vector<float> k;
-        pfx_host_gaussian_kernel(sigma, k);
-        std::vector<float> padded(k.size() + 2 * (size_t)pad, 0.0f);
-        std::copy(k.begin(), k.end(), padded.begin() + pad);
-        PFX_TRY(pfx_reserve(ctx, ctx->d_wts, padded.size() * sizeof(float)));
-        PFX_TRY(pfx_h2d(ctx, ctx->d_wts.p, padded.data(), padded.size() * sizeof(float)));
-        ctx->wts_sigma_bits = sigma_bits;
-        ctx->wts_valid = true;
-    }
-    *wts = (const float*)ctx->d_wts.p + pad;
-    return PFX_OK;
-}
-int pfx_int_gauss_exact_combine_applies(pfx_ctx* ctx, const void* src_dev, const void* dst_dev, uint32_t w, uint32_t h, float sigma)
-{
-    const int radius = pfx_host_gaussian_radius(sigma);
-    return ctx->exact && radius >= 1 && radius <= pfxk_gauss_fused_exact_max_radius() && src_dev != dst_dev && !ranges_overlap(src_dev, dst_dev, img_bytes(w, h));
-}
-int pfx_int_gauss_exact_combine(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, float sigma, int epilogue, float p0, const void* mask_dev)
-{
-    const int radius = pfx_host_gaussian_radius(sigma);
-    if (!pfx_int_gauss_exact_combine_applies(ctx, src_dev, dst_dev, w, h, sigma)) return 0;
-    const float* wts = nullptr;
-    PFX_TRY(pfx_int_gauss_exact_weights(ctx, sigma, &wts));
-    PFX_HIP(ctx, pfxk_gauss_fused_exact(ctx->stream, (const uint8_t*)src_dev, (uint8_t*)dst_dev, wts, radius, w, h, epilogue, p0, (const uint8_t*)mask_dev));
-    return 1;
-}
-
-// the matrix-core Gaussian's f16 tap tables for sigma on the device (cached per context)
-static int gauss_mfma_tables(pfx_ctx* ctx, float sigma)
-{
-    uint32_t sigma_bits; std::memcpy(&sigma_bits, &sigma, 4);
-    if (!ctx->wsplit_valid || ctx->wsplit_sigma_bits != sigma_bits) {
-        std::vector<float> k;
-        pfx_host_gaussian_kernel(sigma, k);
-        std::vector<uint16_t> ws;
-        ctx->wsplit_inv_scale = pfx_host_gaussian_split_f16(k, pfxk_gauss_mfma_wlen(), pfxk_gauss_mfma_woff(), ws, &ctx->wsplit_bias, &ctx->wsplit_bias_single);
-        PFX_TRY(pfx_reserve(ctx, ctx->d_wsplit, ws.size() * sizeof(uint16_t)));
-        PFX_TRY(pfx_h2d(ctx, ctx->d_wsplit.p, ws.data(), ws.size() * sizeof(uint16_t)));
-        ctx->wsplit_sigma_bits = sigma_bits;
-        ctx->wsplit_valid = true;
-    }
-    return PFX_OK;
-}
-
 int pfx_gaussian_blur_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, float sigma, void* tmp_dev)
 {
     return pfx_gaussian_blur_band_dev(ctx, src_dev, dst_dev, w, h, sigma, tmp_dev, 0);
@@ -522,50 +459,7 @@ int pfx_gaussian_blur_band_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev,
     PFX_TRY(check_img(ctx, src_dev, dst_dev, w, h, "pfx_gaussian_blur_dev"));
     PFX_TRY(check_disjoint(ctx, src_dev, dst_dev, w, h, "pfx_gaussian_blur_dev", true)); // in place: the two-pass kernels (through tmp)
     PFX_REQUIRE(ctx, (uint64_t)first_row + h <= 0x7fffffffull, "pfx_gaussian_blur_band_dev: band outside any image");   // the kernels carry image rows in 32-bit signed integers
-    // radius first: a huge sigma must be refused before a tap array of that size is built (the C ABI must not throw)
-    const int radius = pfx_host_gaussian_radius(sigma);
-    if (radius > pfxk_gauss_max_radius())
-        return pfx_fail(ctx, PFX_ERR_UNSUPPORTED, "gaussian radius %d beyond the device tile limit %d", radius, pfxk_gauss_max_radius());
-    uint32_t sigma_bits; std::memcpy(&sigma_bits, &sigma, 4);
-    if (!ctx->exact && radius >= 1 && radius <= pfxk_gauss_mfma_max_radius() && src_dev != dst_dev) {
-        // default mode: fused H+V on the matrix cores, no intermediate in HBM, no scratch (k_gauss.hip:gauss_strip_kernel)
-        PFX_TRY(gauss_mfma_tables(ctx, sigma));
-        pfx_timer t(ctx, "gauss_mfma");
-        PFX_HIP(ctx, pfxk_gauss_mfma(ctx->stream, (const uint8_t*)src_dev, (uint8_t*)dst_dev, (const uint16_t*)ctx->d_wsplit.p,
-                                     radius, ctx->wsplit_inv_scale, ctx->wsplit_bias, ctx->wsplit_bias_single, w, h, first_row, ctx->n_cus > 0 ? ctx->n_cus : 256));
-        return PFX_OK;
-    }
-    const int pad = pfxk_gauss_weight_pad(); // zero taps on both sides: the kernels' register blocking reads past the ends
-    if (!ctx->wts_valid || ctx->wts_sigma_bits != sigma_bits) {
-        std::vector<float> k;
-        pfx_host_gaussian_kernel(sigma, k);
-        std::vector<float> padded(k.size() + 2 * (size_t)pad, 0.0f);
-        std::copy(k.begin(), k.end(), padded.begin() + pad);
-        PFX_TRY(pfx_reserve(ctx, ctx->d_wts, padded.size() * sizeof(float)));
-        PFX_TRY(pfx_h2d(ctx, ctx->d_wts.p, padded.data(), padded.size() * sizeof(float)));
-        ctx->wts_sigma_bits = sigma_bits;
-        ctx->wts_valid = true;
-    }
-    const float* wts = (const float*)ctx->d_wts.p + pad;
-    if (ctx->exact && radius >= 1 && radius <= pfxk_gauss_fused_exact_max_radius() && src_dev != dst_dev) {
-        // bit-exact mode at small radii (what sharpen / glow / drop shadow and the batch pipeline run): both passes in one kernel, no f32 intermediate in HBM
-        pfx_timer t(ctx, "gauss_fused");
-        PFX_HIP(ctx, pfxk_gauss_fused_exact(ctx->stream, (const uint8_t*)src_dev, (uint8_t*)dst_dev, wts, radius, w, h, 0, 0.0f, nullptr));
-        return PFX_OK;
-    }
-    if (!tmp_dev) {
-        PFX_TRY(pfx_reserve(ctx, ctx->st_tmp, (size_t)w * h * 16));
-        tmp_dev = ctx->st_tmp.p;
-    }
-    {
-        pfx_timer t(ctx, "gauss_h");
-        PFX_HIP(ctx, pfxk_gauss_h(ctx->stream, (const uint8_t*)src_dev, (float*)tmp_dev, wts, radius, w, h, ctx->exact ? 1 : 0));
-    }
-    {
-        pfx_timer t(ctx, "gauss_v");
-        PFX_HIP(ctx, pfxk_gauss_v(ctx->stream, (const float*)tmp_dev, (uint8_t*)dst_dev, wts, radius, w, h, ctx->exact ? 1 : 0));
-    }
-    return PFX_OK;
+    return pfx_gauss_blur(ctx, ctx->exact, src_dev, dst_dev, w, h, sigma, tmp_dev, first_row);   // which kernels run: pfx_gauss.cpp
 }
 
 int pfx_box_blur_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, float radius,
@@ -785,43 +679,21 @@ int pfx_chain_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, 
         }
         const pfx_chain_op& so = ops[st.stencil];
         void* out = stencil_out(seen++);
-        bool fused = false;
         // The pointwise run rides in the Gaussian's store only when it is light: a Gaussian kernel is bound by its own arithmetic and dependency chains, not by HBM,
         // so an op of ~140 instructions per pixel (HSL, vibrance) costs there what it costs as a streaming pass of its own and the fused launch saves nothing
         // (8K sigma 16 -> HSL: 0.210 ms fused against 0.206 as two launches; bit-exact sigma 4 -> HSL 0.381 against 0.371: profiles/r06_tuning.md); light ops
-        // (invert, exposure, brightness / contrast, tables ...) cost a few instructions and save the 8 B/px round trip.  pfx_tune "chain_fuse_heavy" = 1 fuses anyway.
-        bool heavy = false;
+        // (invert, exposure, brightness / contrast, tables ...) cost a few instructions and save the 8 B/px round trip.  pfx_tune "chain_fuse_heavy" = 1 fuses anyway
+        // (the rule itself: pfx_gauss.cpp).
+        bool heavy = false, rode = false;
         for (uint32_t k = 0; k < st.count; ++k) {
             const pfx_chain_op& o = ops[st.first + k];
             heavy = heavy || (o.kind == PFX_CHAIN_ADJUST && (o.op == PFX_OP_HSL || o.op == PFX_OP_VIBRANCE)) || (o.kind == PFX_CHAIN_RHAI && o.op == PFX_RHAI_HSL);
         }
-        if (so.kind == PFX_CHAIN_GAUSSIAN && st.count && (!heavy || ctx->chain_fuse_heavy)) {
-            const float sigma = so.params[0];
-            const int radius = pfx_host_gaussian_radius(sigma);
-            if (ctx->exact && radius >= 1 && radius <= pfxk_gauss_fused_exact_max_radius()) {
-                const float* wts = nullptr;
-                PFX_TRY(pfx_int_gauss_exact_weights(ctx, sigma, &wts));
-                pfx_timer t(ctx, "gauss_fused_chain");
-                PFX_HIP(ctx, pfxk_gauss_fused_exact_chain(ctx->stream, (const uint8_t*)cur, (uint8_t*)out, wts, radius, w, h, &C, (const uint8_t*)ctx->d_chain_luts.p));
-                fused = true;
-            } else if (!ctx->exact && radius >= 1 && radius <= pfxk_gauss_mfma_max_radius() && C.n_luts == 0 && ctx->chain_mfma_epilogue) {
-                // default mode: the chain rides in the matrix-core Gaussian's store (table-free ops, aligned buffers; otherwise the two launches below)
-                PFX_TRY(gauss_mfma_tables(ctx, sigma));
-                pfx_timer t(ctx, "gauss_mfma_chain");
-                const hipError_t e = pfxk_gauss_mfma_chain(ctx->stream, (const uint8_t*)cur, (uint8_t*)out, (const uint16_t*)ctx->d_wsplit.p, radius, ctx->wsplit_inv_scale,
-                                                           ctx->wsplit_bias, ctx->wsplit_bias_single, w, h, 0u, ctx->n_cus > 0 ? ctx->n_cus : 256, &C);
-                if (e == hipSuccess) fused = true;
-                else if (e != hipErrorNotSupported) PFX_HIP(ctx, e);
-                else (void)hipGetLastError();
-            }
-        }
-        if (!fused) {
-            if (so.kind == PFX_CHAIN_GAUSSIAN) PFX_TRY(pfx_gaussian_blur_dev(ctx, cur, out, w, h, so.params[0], nullptr));
-            else PFX_TRY(pfx_box_blur_dev(ctx, cur, out, w, h, so.params[0], nullptr, nullptr));
-            if (st.count) {
-                pfx_timer t(ctx, "chain");
-                PFX_HIP(ctx, pfxk_pointwise_chain(ctx->stream, (const uint8_t*)out, (uint8_t*)out, (const uint8_t*)ctx->d_chain_luts.p, &C, w, h));
-            }
+        if (so.kind == PFX_CHAIN_GAUSSIAN) PFX_TRY(pfx_gauss_chain(ctx, ctx->exact, cur, out, w, h, so.params[0], st.count ? &C : nullptr, heavy, &rode));
+        else PFX_TRY(pfx_box_blur_dev(ctx, cur, out, w, h, so.params[0], nullptr, nullptr));
+        if (st.count && !rode) {
+            pfx_timer t(ctx, "chain");
+            PFX_HIP(ctx, pfxk_pointwise_chain(ctx->stream, (const uint8_t*)out, (uint8_t*)out, (const uint8_t*)ctx->d_chain_luts.p, &C, w, h));
         }
         cur = out;
     }

@@ -14,48 +14,11 @@ int check2(pfx_ctx* ctx, const void* a, const void* b, uint32_t w, uint32_t h, c
     if (!a || !b) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: null image pointer", who);
     if (w == 0 || h == 0 || (uint64_t)w * h > 256000000ull) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: bad image size %ux%u", who, w, h);
     // the effect kernels read neighbourhoods / gather from src while other workgroups write dst: the buffers must not overlap (pfx.h)
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    const size_t bytes = (size_t)w * h * 4;
-    if (x < y + bytes && y < x + bytes) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: src and dst overlap", who);
+    if (pfx_ranges_overlap(a, (size_t)w * h * 4, b, (size_t)w * h * 4)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: src and dst overlap", who);
     return pfx_use(ctx);
 }
 
 inline int32_t f32_as_i32(float v) { return v != v ? 0 : (v >= 2147483648.0f ? 2147483647 : (v <= -2147483648.0f ? (-2147483647 - 1) : (int32_t)v)); }
-
-// The Gaussian inside a composite effect: bit-exact unless the caller opted out (pfx_internal.h: gauss_fast_effects).  The reference's tests hold these
-// effects at tolerance 0 (tests/visual_filters.rs:43-55,154-165), and the default-mode Gaussian's +-1 LSB would be multiplied by `amount` / `intensity`.
-struct exact_gauss_scope {
-    pfx_ctx* c; bool saved;
-    explicit exact_gauss_scope(pfx_ctx* ctx) : c(ctx), saved(ctx->exact) { if (!ctx->gauss_fast_effects) ctx->exact = true; }
-    ~exact_gauss_scope() { c->exact = saved; }
-};
-int effect_gaussian(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, float radius)
-{
-    exact_gauss_scope g(ctx);
-    return pfx_gaussian_blur_dev(ctx, src_dev, dst_dev, w, h, radius, nullptr);
-}
-
-// Gaussian of src into the context scratch, then the two-input pass (stylize.rs: `blurred = parallel_gaussian_blur_pub(flat, radius)`)
-int blur_then_combine(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, float radius, int op, float p0,
-                      const void* mask_dev, const char* timer)
-{
-    const size_t bytes = (size_t)w * h * 4;
-    {   // small radii: the bit-exact Gaussian and the combine in one kernel — the blurred image never exists in memory
-        exact_gauss_scope g(ctx);
-        if (pfx_int_gauss_exact_combine_applies(ctx, src_dev, dst_dev, w, h, radius)) {   // the timer only around a launch that happens
-            pfx_timer t(ctx, timer);
-            const int ran = pfx_int_gauss_exact_combine(ctx, src_dev, dst_dev, w, h, radius, op == PFXK_FX_SHARPEN ? 1 : 2, p0, mask_dev);
-            if (ran < 0) return ran;
-            if (ran == 1) return PFX_OK;
-        }
-    }
-    PFX_TRY(pfx_reserve(ctx, ctx->st_aux2, bytes));
-    PFX_TRY(effect_gaussian(ctx, src_dev, ctx->st_aux2.p, w, h, radius));
-    pfx_timer t(ctx, timer);
-    PFX_HIP(ctx, pfxk_combine(ctx->stream, (const uint8_t*)src_dev, (const uint8_t*)ctx->st_aux2.p, (const uint8_t*)mask_dev,
-                              (uint8_t*)dst_dev, w, h, op, p0));
-    return PFX_OK;
-}
 
 template <class F>
 int host_wrap(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_t w, uint32_t h, const uint8_t* mask, const char* who, F&& dev_call)
@@ -83,13 +46,13 @@ extern "C" {
 int pfx_sharpen_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, float amount, float radius, const void* mask_dev)
 {
     PFX_TRY(check2(ctx, src_dev, dst_dev, w, h, "pfx_sharpen_dev"));
-    return blur_then_combine(ctx, src_dev, dst_dev, w, h, radius, PFXK_FX_SHARPEN, amount, mask_dev, "sharpen");
+    return pfx_gauss_combine(ctx, pfx_effect_exact(ctx), src_dev, dst_dev, w, h, radius, PFX_GAUSS_SHARPEN, amount, mask_dev, "sharpen");
 }
 
 int pfx_glow_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, float radius, float intensity, const void* mask_dev)
 {
     PFX_TRY(check2(ctx, src_dev, dst_dev, w, h, "pfx_glow_dev"));
-    return blur_then_combine(ctx, src_dev, dst_dev, w, h, radius, PFXK_FX_GLOW, intensity, mask_dev, "glow");
+    return pfx_gauss_combine(ctx, pfx_effect_exact(ctx), src_dev, dst_dev, w, h, radius, PFX_GAUSS_GLOW, intensity, mask_dev, "glow");
 }
 
 int pfx_bokeh_blur_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, float radius, const void* mask_dev)
@@ -393,11 +356,10 @@ int pfx_shadow_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w,
     if (widen_radius) spread = f32_as_i32(roundf(fmaxf(blur_radius, 1.0f))); // render.rs:251
     PFX_REQUIRE(ctx, spread <= 4096, "drop shadow: spread too large");
     // The reference expands the shadow's alpha plane to (a, a, a, a), blurs all four channels and reads one back (render.rs:291-301).  Where the bit-exact fused
-    // Gaussian applies (the effect's default mode, radius <= 16) and rows are dword-aligned, the PLANE is blurred instead — per element the same products and sums
+    // Gaussian applies (the effect's default mode, small radii) and rows are dword-aligned, the PLANE is blurred instead — per element the same products and sums
     // (k_gauss_exact.hip: gauss_plane_exact_kernel) — and the composite reads the plane; otherwise the RGBA image goes through the Gaussian as before.
-    const int g_radius = blur_radius > 0.5f ? pfx_host_gaussian_radius(blur_radius) : 0;
-    const bool plane_path = (w & 3u) == 0 && !ctx->gauss_fast_effects && ctx->shadow_plane_blur &&
-                            (g_radius == 0 || (g_radius >= 1 && g_radius <= pfxk_gauss_fused_exact_max_radius()));
+    const bool blurred = blur_radius > 0.5f; // render.rs:297
+    const bool plane_path = pfx_gauss_plane_applies(ctx, pfx_effect_exact(ctx), w, h, blurred ? pfx_host_gaussian_radius(blur_radius) : 0);
     PFX_TRY(pfx_reserve(ctx, ctx->fx_a, 2 * n + 8));
     if (!plane_path) PFX_TRY(pfx_reserve(ctx, ctx->fx_b, 4 * n));
     uint8_t* plane_a = (uint8_t*)ctx->fx_a.p;
@@ -408,18 +370,13 @@ int pfx_shadow_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w,
         PFX_HIP(ctx, pfxk_shadow_alpha(ctx->stream, (const uint8_t*)src_dev, plane_a, plane_b, plane_path ? nullptr : (uint8_t*)ctx->fx_b.p,
                                        offset_x, offset_y, spread, w, h));
     }
-    if (blur_radius > 0.5f) { // render.rs:297
-        if (plane_path) {
-            const float* wts = nullptr;
-            PFX_TRY(pfx_int_gauss_exact_weights(ctx, blur_radius, &wts));
-            pfx_timer t(ctx, "gauss_plane");
-            PFX_HIP(ctx, pfxk_gauss_plane_exact(ctx->stream, plane_a, plane_b, wts, g_radius, w, h));
-            alpha_img = plane_b;
-        } else {
-            PFX_TRY(pfx_reserve(ctx, ctx->st_aux2, 4 * n));
-            PFX_TRY(effect_gaussian(ctx, ctx->fx_b.p, ctx->st_aux2.p, w, h, blur_radius));
-            alpha_img = ctx->st_aux2.p;
-        }
+    if (blurred && plane_path) {
+        PFX_TRY(pfx_gauss_plane(ctx, plane_a, plane_b, w, h, blur_radius));
+        alpha_img = plane_b;
+    } else if (blurred) {
+        PFX_TRY(pfx_reserve(ctx, ctx->st_aux2, 4 * n));
+        PFX_TRY(pfx_gauss_blur(ctx, pfx_effect_exact(ctx), ctx->fx_b.p, ctx->st_aux2.p, w, h, blur_radius, nullptr, 0));
+        alpha_img = ctx->st_aux2.p;
     }
     pfxk_fx_params P{};
     P.f[0] = opacity;

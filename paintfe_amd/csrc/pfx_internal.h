@@ -109,7 +109,6 @@ int pfx_fail(pfx_ctx* ctx, int status, const char* fmt, ...);
         if (!(cond)) return pfx_fail((ctx), PFX_ERR_INVALID, "%s", (msg)); \
     } while (0)
 
-// do [a, a + a_bytes) and [b, b + b_bytes) share a byte?  (aliasing rule of the `_dev` entry points, include/pfx.h)
 // The document-size limit every entry point enforces: non-zero sides and at most 256 M pixels (TiledImage::new clamps beyond that, ref: src/canvas/tiled_image.rs:15-26;
 // io.rs:500 refuses sides over 25 000).  The kernels index pixels with 32-bit arithmetic under this bound.
 inline bool pfx_dims_ok(uint32_t w, uint32_t h) { return w != 0 && h != 0 && (uint64_t)w * h <= 256000000ull; }
@@ -119,6 +118,7 @@ inline bool pfx_rect_inside(uint32_t x, uint32_t y, uint32_t rw, uint32_t rh, ui
     return rw != 0 && rh != 0 && (uint64_t)x + rw <= w && (uint64_t)y + rh <= h;
 }
 
+// do [a, a + a_bytes) and [b, b + b_bytes) share a byte?  (aliasing rule of the `_dev` entry points, include/pfx.h)
 inline bool pfx_ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
 {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
@@ -145,10 +145,33 @@ struct pfx_timer {
 extern "C" int pfx_int_flatten_with_chunk_keys_dev(pfx_ctx* ctx, const void* const* layer_ptrs_dev, const pfx_layer_info* layers, uint32_t n_layers,
                                                    uint32_t w, uint32_t h, void* dst_dev, const uint8_t* chunk_keys_host);
 
+// ---- the Gaussian's host side (pfx_gauss.cpp): the tap-table caches, the one decision which kernel runs, the launches ----
+enum { PFX_GAUSS_PLAIN = 0, PFX_GAUSS_SHARPEN = 1, PFX_GAUSS_GLOW = 2, PFX_GAUSS_CHAIN = 3, PFX_GAUSS_PLANE = 4 };   // what rides in the Gaussian's store
+// a path: radius beyond pfxk_gauss_max_radius() | the blur alone (a rider gets a launch of its own behind it) | with the chain / the sharpen, glow or chain in
+// its store | the drop shadow's one-channel plane form
+enum { PFX_GAUSS_UNSUPPORTED = -1, PFX_GAUSS_MFMA = 0, PFX_GAUSS_FUSED, PFX_GAUSS_TWO_PASS, PFX_GAUSS_MFMA_RIDE, PFX_GAUSS_FUSED_RIDE, PFX_GAUSS_PLANE_FUSED };
+struct pfx_gauss_case {   // plain ints: the test seam fills it from Python
+    // exact: the effective mode — ctx->exact for a plain blur or a chain, pfx_effect_exact() inside an effect; same: src == dst; overlap: the two images share
+    // a byte (src == dst included); ride: PFX_GAUSS_PLAIN ..
+    int exact, radius, same, overlap, ride;
+    // chain: tables its ops read; pfx_tune "chain_mfma"; it holds an HSL / vibrance op (pfx_chain_dev); pfx_tune "chain_fuse_heavy"
+    uint32_t n_luts; int chain_mfma, heavy, fuse_heavy;
+    // plane: image width; pfx_tune "shadow_plane", "gauss_fast_effects".  fused_enabled: pfx_tune "gauss_fused_exact" (process-wide)
+    uint32_t w; int shadow_plane, fast_effects, fused_enabled;
+};
+// the decision, pure: a PFX_GAUSS_* path.  Exported as a test seam (not in include/pfx.h)
+extern "C" int pfx_int_gauss_path(const pfx_gauss_case* c);
+// The Gaussian inside sharpen / glow / drop shadow: bit-exact unless the caller opted out (gauss_fast_effects above).  The reference's tests hold these effects
+// at tolerance 0 (tests/visual_filters.rs:43-55,154-165), and the default-mode Gaussian's +-1 LSB would be multiplied by `amount` / `intensity`.
+inline bool pfx_effect_exact(const pfx_ctx* ctx) { return ctx->exact || !ctx->gauss_fast_effects; }
+// arguments are the caller's to check; `exact` as in pfx_gauss_case
+int pfx_gauss_blur(pfx_ctx* ctx, bool exact, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, float sigma, void* tmp_dev, uint32_t first_row);
+int pfx_gauss_combine(pfx_ctx* ctx, bool exact, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, float sigma, int ride /* _SHARPEN | _GLOW */, float p0, const void* mask_dev, const char* timer);
+int pfx_gauss_chain(pfx_ctx* ctx, bool exact, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, float sigma, const pfxk_chain* C, bool heavy, bool* rode);
+bool pfx_gauss_plane_applies(const pfx_ctx* ctx, bool exact, uint32_t w, uint32_t h, int radius);
+int pfx_gauss_plane(pfx_ctx* ctx, const void* src_plane, void* dst_plane, uint32_t w, uint32_t h, float sigma);
+
 // blur_with_selection on device-resident images (pfx_api.cpp); mask_host may be NULL (= no selection)
-extern "C" int pfx_int_gauss_exact_weights(pfx_ctx* ctx, float sigma, const float** wts);
-extern "C" int pfx_int_gauss_exact_combine_applies(pfx_ctx* ctx, const void* src_dev, const void* dst_dev, uint32_t w, uint32_t h, float sigma);
-extern "C" int pfx_int_gauss_exact_combine(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, float sigma, int epilogue, float p0, const void* mask_dev); // 1 ran, 0 not applicable
 int pfx_int_blur_with_selection_dev(pfx_ctx* ctx, const void* d_src, void* d_dst, uint32_t w, uint32_t h, float sigma,
                                     const uint8_t* mask_host, const void* d_mask);
 

@@ -85,8 +85,10 @@ int        pfxk_gauss_max_radius(void);
 int        pfxk_gauss_weight_pad(void);
 void       pfxk_gauss_set_v_config(int cfg); // tuning knob, 0 = shipped
 void       pfxk_gauss_set_mfma_segments(int n); // tuning knob of the matrix-core kernel, 0 = automatic
-/* bit-exact mode, radii 1 .. pfxk_gauss_fused_exact_max_radius(): both passes in one kernel, the f32 intermediate in an LDS ring (k_gauss.hip) */
+/* bit-exact mode, radii 1 .. pfxk_gauss_fused_exact_max_radius() (the compiled limit): both passes in one kernel, the f32 intermediate in an LDS ring (k_gauss_exact.hip);
+   _enabled: the process-wide A/B knob, read where the path is chosen (pfx_gauss.cpp), not by the launchers */
 void pfxk_gauss_set_fused_exact(int on);
+int pfxk_gauss_fused_exact_enabled(void);
 int pfxk_gauss_fused_exact_max_radius(void);
 /* one-channel form (w % 4 == 0, tight rows, radii 1 .. pfxk_gauss_fused_exact_max_radius()): element by element what one channel of pfxk_gauss_fused_exact gives on (a, a, a, a) */
 hipError_t pfxk_gauss_plane_exact(hipStream_t stream, const uint8_t* d_src, uint8_t* d_dst, const float* d_wts_tap0, int radius, uint32_t w, uint32_t h);

@@ -767,6 +767,41 @@ typedef struct pfx_batch_stats {
 int pfx_batch_pipeline(const int* devices, uint32_t n_devices, uint32_t n_images, const pfx_batch_params* params,
                        const uint8_t* const* image_pool_host, uint32_t n_pool, pfx_batch_stats* stats, char* err, size_t err_cap);
 
+/* ================= shape tool: the 17 built-in SDF shapes (ref: src/ops/shapes.rs:1169-1305 rasterize_shape) =================
+ * A pure per-pixel map over the shape's bounding box: the signed distance at the pixel centre (shape_sdf, :827), a smoothstep coverage, the fill / outline /
+ * both colour mix.  Everything that is uniform over the image (rotation, angles, vertex lists, the heart's path) is computed on the host with the host libm, as
+ * the reference does.  Bit-exact class, except pentagon, hexagon, octagon, star5 and star6, which evaluate atan2 / cos / sin per pixel: +-1 LSB class (the f64
+ * routine rounded once, like pfx_twist_core).  The reference's 20 shape goldens are reproduced with tolerance 0.
+ * Out of scope: custom SVG shapes (PlacedShape::custom_shape_data — kurbo polylines with 4-sample supersampling, :1065-1163).
+ * The struct is always passed by pointer.  kind >= PFX_SHAPE_COUNT, fill_mode > PFX_SHAPE_BOTH or a non-finite cx / cy / hw / hh / rotation (the reference's
+ * `as i32` would saturate the box to the whole canvas) return PFX_ERR_INVALID. */
+typedef enum pfx_shape_kind { /* ShapeKind's declaration order, shapes.rs:159-178 */
+    PFX_SHAPE_ELLIPSE = 0, PFX_SHAPE_RECTANGLE, PFX_SHAPE_ROUNDED_RECT, PFX_SHAPE_TRAPEZOID, PFX_SHAPE_PARALLELOGRAM,
+    PFX_SHAPE_TRIANGLE, PFX_SHAPE_RIGHT_TRIANGLE, PFX_SHAPE_PENTAGON, PFX_SHAPE_HEXAGON, PFX_SHAPE_OCTAGON, PFX_SHAPE_CROSS,
+    PFX_SHAPE_CHECK, PFX_SHAPE_HEART, PFX_SHAPE_DIAMOND, PFX_SHAPE_STAR5, PFX_SHAPE_STAR6, PFX_SHAPE_ARROW, PFX_SHAPE_COUNT
+} pfx_shape_kind;
+typedef enum pfx_shape_fill { PFX_SHAPE_OUTLINE = 0, PFX_SHAPE_FILLED, PFX_SHAPE_BOTH } pfx_shape_fill; /* ShapeFillMode, shapes.rs:268-272 */
+typedef struct pfx_shape {          /* PlacedShape, shapes.rs:322 — the fields the rasteriser reads */
+    float cx, cy, hw, hh, rotation, outline_width, corner_radius;
+    uint8_t primary[4], secondary[4];
+    uint8_t kind, fill_mode, anti_alias, _pad;
+} pfx_shape;
+/* the rasteriser's bounding box (:1175-1207): rotated corners of shape_local_corners, padded by 2, floor / ceil, clamped to the canvas.
+ * box = x0, y0, bw, bh; an empty box is 0, 0, 0, 0 and PFX_OK.  Host only, no context. */
+int pfx_shape_bounds(const pfx_shape* shape, uint32_t canvas_w, uint32_t canvas_h, int32_t box[4]);
+/* the reference's `buf` over that box, bit for bit (box_rgba = bw*bh*4 bytes): pixels with coverage <= 0.001 are zero, pixels whose alpha rounds to 0 keep
+ * their colour bytes.  An empty box returns PFX_OK and leaves the buffer untouched. */
+int pfx_shape_rasterize(pfx_ctx* ctx, const pfx_shape* shape, uint32_t canvas_w, uint32_t canvas_h, uint8_t* box_rgba);
+int pfx_shape_rasterize_dev(pfx_ctx* ctx, const pfx_shape* shape, uint32_t canvas_w, uint32_t canvas_h, void* box_dev);
+/* the whole canvas (canvas_w*canvas_h*4, every byte written): zero outside the box, inside it the box pixels with a > 0 — the tool's preview layer
+ * (ref: src/ui/panels/tools/behavior/advanced.rs:979-1021; tests/visual_shapes.rs:18-41 rasterize_to_canvas), the form pfx_composite_preview takes */
+int pfx_shape_preview(pfx_ctx* ctx, const pfx_shape* shape, uint32_t canvas_w, uint32_t canvas_h, uint8_t* canvas_rgba);
+int pfx_shape_preview_dev(pfx_ctx* ctx, const pfx_shape* shape, uint32_t canvas_w, uint32_t canvas_h, void* canvas_dev);
+/* rasterise and commit in one kernel over the box, no intermediate buffer (advanced.rs:1054 onward): equals pfx_shape_preview followed by pfx_brush_commit with
+ * the same blend mode and selection (canvas_w*canvas_h bytes or NULL).  Layer pixels outside the box are neither read nor written. */
+int pfx_shape_draw_dev(pfx_ctx* ctx, void* layer_dev, uint32_t canvas_w, uint32_t canvas_h, const pfx_shape* shape, uint8_t blend_mode,
+                       const void* selection_dev /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,12 @@ class CanvasOp(C.Structure):
     _fields_ = [("kind", C.c_int32), ("w", C.c_uint32), ("h", C.c_uint32), ("anchor_x", C.c_uint32), ("anchor_y", C.c_uint32)]
 
 
+class Shape(C.Structure):   # pfx_shape
+    _fields_ = [("cx", C.c_float), ("cy", C.c_float), ("hw", C.c_float), ("hh", C.c_float), ("rotation", C.c_float), ("outline_width", C.c_float),
+                ("corner_radius", C.c_float), ("primary", C.c_uint8 * 4), ("secondary", C.c_uint8 * 4), ("kind", C.c_uint8), ("fill_mode", C.c_uint8),
+                ("anti_alias", C.c_uint8), ("_pad", C.c_uint8)]
+
+
 _lib = None
 
 

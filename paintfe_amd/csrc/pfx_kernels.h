@@ -287,6 +287,25 @@ hipError_t pfxk_brush_commit(hipStream_t s, uint8_t* d_layer, const uint8_t* d_p
 hipError_t pfxk_blend_arrays(hipStream_t s, const uint8_t* d_base, const uint8_t* d_top, uint8_t* d_dst, size_t n_px,
                              uint32_t mode, float opacity, int fast_div);
 
+// ---- k_shapes.hip ---- the shape tool's SDF rasteriser (shapes.rs:1169-1305); the host side (pfx_shapes.cpp) prepares everything that is uniform over the image
+enum { PFXK_SDF_ELLIPSE = 0, PFXK_SDF_BOX, PFXK_SDF_ROUNDED, PFXK_SDF_CONVEX /* trapezoid, parallelogram, right triangle */, PFXK_SDF_TRIANGLE,
+       PFXK_SDF_POLYGON /* pentagon, hexagon, octagon */, PFXK_SDF_CROSS, PFXK_SDF_CHECK, PFXK_SDF_HEART, PFXK_SDF_DIAMOND, PFXK_SDF_STAR /* star5, star6 */,
+       PFXK_SDF_ARROW };
+enum { PFXK_SHAPE_BOX = 0 /* d_out = bw*bh pixels */, PFXK_SHAPE_CANVAS = 1 /* d_out = the whole canvas, every pixel written */,
+       PFXK_SHAPE_COMMIT = 2 /* d_out = the layer, blended in place over the box */ };
+#define PFXK_SHAPE_MAX_VERTS 96
+typedef struct pfxk_shape_params { // passed by value: lands in SGPRs / scalar loads
+    int32_t  x0, y0, bw, bh;       // the box in canvas pixels (inside the canvas; bw or bh == 0: empty)
+    float    cx, cy, inv_cos, inv_sin, hx, hy, outline_width /* .max(0.0) applied */, corner_radius;
+    uint32_t primary, secondary;   // r | g << 8 | b << 16 | a << 24
+    int32_t  fill_mode, anti_alias;
+    float    k[12];                // per-SDF constants, layout next to each branch of shape_sdf (k_shapes.hip)
+    int32_t  n_verts;
+    float    verts[PFXK_SHAPE_MAX_VERTS][2]; // PFXK_SDF_CONVEX: 3 or 4 vertices; PFXK_SDF_HEART: the 96-vertex path
+} pfxk_shape_params;
+hipError_t pfxk_shape(hipStream_t s, int form, int sdf, const pfxk_shape_params* P, uint8_t* d_out, const uint8_t* d_selection /* COMMIT only, may be NULL */,
+                      uint32_t mode /* COMMIT only: BlendMode::to_u8 */, uint32_t canvas_w, uint32_t canvas_h);
+
 #ifdef __cplusplus
 }
 #endif

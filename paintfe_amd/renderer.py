@@ -8,7 +8,8 @@ reference's ``&[u8]`` + ``(w, h)``.  All pixel work happens in libpfx.so's HIP k
 from __future__ import annotations
 
 import ctypes as C
-from typing import Iterable, Optional, Sequence
+from dataclasses import dataclass
+from typing import Iterable, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -47,6 +48,9 @@ GRID_STYLES = ["lines", "checkerboard"]                               # GridStyl
 OUTLINE_MODES = ["outside", "inside", "center"]                       # OutlineMode
 COLOR_FILTER_MODES = ["multiply", "screen", "overlay", "soft_light"]  # ColorFilterMode
 RESIZE_FILTERS = ["nearest", "bilinear", "bicubic", "lanczos3"]       # ScriptFilterType / Interpolation
+SHAPE_KINDS = ["ellipse", "rectangle", "rounded_rect", "trapezoid", "parallelogram", "triangle", "right_triangle", "pentagon", "hexagon", "octagon", "cross",
+               "check", "heart", "diamond", "star5", "star6", "arrow"]       # ShapeKind, shapes.rs:159-178
+SHAPE_FILLS = ["outline", "filled", "both"]                                   # ShapeFillMode, shapes.rs:268-272
 CANVAS_OPS = ["flip_horizontal", "flip_vertical", "rotate_90cw", "rotate_90ccw", "rotate_180", "resize_image", "resize_canvas"]  # CanvasOpRequest
 
 
@@ -93,6 +97,38 @@ _EFFECTS = {
     "contours": lambda scale, frequency, line_width, line_color, seed, octaves, blend: [
         C.c_float(scale), C.c_float(frequency), C.c_float(line_width), _c4(line_color), C.c_uint32(seed), C.c_uint32(octaves), C.c_float(blend)],
 }
+
+
+@dataclass
+class Shape:
+    """PlacedShape (ref: src/ops/shapes.rs:322): the fields the rasteriser reads.  `kind` / `fill` are names from SHAPE_KINDS / SHAPE_FILLS or their indices."""
+    kind: object
+    fill: object = "both"
+    cx: float = 0.0
+    cy: float = 0.0
+    hw: float = 0.0
+    hh: float = 0.0
+    rotation: float = 0.0
+    outline_width: float = 1.0
+    corner_radius: float = 0.0
+    primary: Tuple[int, int, int, int] = (0, 0, 0, 255)
+    secondary: Tuple[int, int, int, int] = (255, 255, 255, 255)
+    anti_alias: bool = True
+
+    def to_c(self) -> "_lib.Shape":
+        kind = SHAPE_KINDS.index(self.kind) if isinstance(self.kind, str) else int(self.kind)
+        fill = SHAPE_FILLS.index(self.fill) if isinstance(self.fill, str) else int(self.fill)
+        return _lib.Shape(self.cx, self.cy, self.hw, self.hh, self.rotation, self.outline_width, self.corner_radius, _c4(self.primary), _c4(self.secondary),
+                          kind, fill, int(bool(self.anti_alias)), 0)
+
+
+def shape_bounds(shape: Shape, canvas_w: int, canvas_h: int):
+    """(x0, y0, bw, bh) of the shape's rasterised box (rasterize_shape, shapes.rs:1175-1207); an empty box is (0, 0, 0, 0).  Host only."""
+    box = (C.c_int32 * 4)()
+    st = _lib.load().pfx_shape_bounds(C.byref(shape.to_c()), C.c_uint32(canvas_w), C.c_uint32(canvas_h), box)
+    if st != 0:
+        raise PfxError(st, "pfx_shape_bounds: bad shape or canvas size")
+    return tuple(int(v) for v in box)
 
 
 def script_check(source: str, w: int = 64, h: int = 64):
@@ -494,6 +530,51 @@ class GpuRenderer:
         self._check(self._lib.pfx_brush_commit(self._h, _p(l), _p(p), C.c_uint32(w), C.c_uint32(h), C.c_uint8(blend_mode),
                                                C.c_int(int(is_eraser)), _p(sel)))
         return l
+
+    # ------------------------------------------------------------------ shape tool (ref: src/ops/shapes.rs:1169-1305)
+    shape_bounds = staticmethod(shape_bounds)
+
+    def rasterize_shape(self, shape: Shape, canvas_w: int, canvas_h: int):
+        """rasterize_shape: (buf, (x0, y0, bw, bh)) with buf the (bh, bw, 4) box buffer"""
+        box = shape_bounds(shape, canvas_w, canvas_h)
+        buf = np.zeros((box[3], box[2], 4), np.uint8)
+        if buf.size:
+            self._check(self._lib.pfx_shape_rasterize(self._h, C.byref(shape.to_c()), C.c_uint32(canvas_w), C.c_uint32(canvas_h), _p(buf)))
+        return buf, box
+
+    def shape_preview(self, shape: Shape, canvas_w: int, canvas_h: int):
+        """the shape on a zeroed canvas (the tool's preview layer; tests/visual_shapes.rs rasterize_to_canvas)"""
+        out = np.empty((canvas_h, canvas_w, 4), np.uint8)
+        self._check(self._lib.pfx_shape_preview(self._h, C.byref(shape.to_c()), C.c_uint32(canvas_w), C.c_uint32(canvas_h), _p(out)))
+        return out
+
+    def draw_shape(self, layer, shape: Shape, blend_mode: int = 0, selection=None):
+        """rasterise and commit into a copy of `layer` on the device (pfx_shape_draw_dev): shape_preview + brush_commit in one kernel"""
+        l = _u8(layer)
+        h, w = l.shape[:2]
+        sel = None if selection is None else _u8(selection)
+        d_layer = self.dev_alloc(l.nbytes)
+        d_sel = self.dev_alloc(sel.nbytes) if sel is not None else 0
+        try:
+            self.dev_upload(d_layer, l)
+            if sel is not None:
+                self.dev_upload(d_sel, sel)
+            self.draw_shape_dev(d_layer, w, h, shape, blend_mode, d_sel)
+            return self.dev_download(d_layer, l.shape)
+        finally:
+            self.dev_free(d_layer)
+            if d_sel:
+                self.dev_free(d_sel)
+
+    def draw_shape_dev(self, layer_ptr: int, w: int, h: int, shape: Shape, blend_mode: int = 0, selection_ptr: int = 0):
+        self._check(self._lib.pfx_shape_draw_dev(self._h, C.c_void_p(layer_ptr), C.c_uint32(w), C.c_uint32(h), C.byref(shape.to_c()), C.c_uint8(blend_mode),
+                                                 C.c_void_p(selection_ptr or None)))
+
+    def shape_preview_dev(self, shape: Shape, w: int, h: int, canvas_ptr: int):
+        self._check(self._lib.pfx_shape_preview_dev(self._h, C.byref(shape.to_c()), C.c_uint32(w), C.c_uint32(h), C.c_void_p(canvas_ptr)))
+
+    def rasterize_shape_dev(self, shape: Shape, w: int, h: int, box_ptr: int):
+        self._check(self._lib.pfx_shape_rasterize_dev(self._h, C.byref(shape.to_c()), C.c_uint32(w), C.c_uint32(h), C.c_void_p(box_ptr)))
 
     # ------------------------------------------------------------------ script front-end
     def resize_image(self, img, new_w: int, new_h: int, filter="bilinear"):   # transform.rs:347 (imageops::resize)

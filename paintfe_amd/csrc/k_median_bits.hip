@@ -364,24 +364,20 @@ __global__ __launch_bounds__(256) void median_bits2_kernel(const uint8_t* __rest
     }
 }
 
-int g_mb_pair = 1; // pfxk_median_bits_set_pair: radii 2..7 on the column-pair kernel
 } // namespace
-
-extern "C" void pfxk_median_bits_set_pair(int on) { g_mb_pair = on; }
 
 extern "C" size_t pfxk_median_bits_scratch(int radius, uint32_t w, uint32_t h)
 {
     return (size_t)h * 4u * mb_dwords(w, radius) * 8u * sizeof(uint32_t);
 }
 
-extern "C" hipError_t pfxk_median_bits(hipStream_t s, const uint8_t* d_src, uint8_t* d_dst, const uint8_t* d_mask, uint32_t* d_planes, int radius,
-                                       uint32_t w, uint32_t h)
+extern "C" hipError_t pfxk_median_bits(hipStream_t s, const uint8_t* d_src, uint8_t* d_dst, const uint8_t* d_mask, uint32_t* d_planes, int radius, uint32_t w, uint32_t h, int pair)
 {
     if (w == 0 || h == 0) return hipSuccess;
-    if (radius < 2 || radius > 8) return hipErrorInvalidValue;
+    if (radius < 2 || radius > (pair ? 7 : 8)) return hipErrorInvalidValue;   // the column-pair kernel has no radius-8 build (18-bit fields)
     const uint32_t nd = mb_dwords(w, radius);
     median_planes_kernel<<<dim3((nd + 7u) / 8u, (h + MP_ROWS - 1) / MP_ROWS), 256, 0, s>>>((const uint32_t*)d_src, d_planes, radius, (int)w, (int)h, nd);
-    if (g_mb_pair && radius <= 7) {
+    if (pair) {
         const dim3 g2((w + MB2_COLS - 1) / MB2_COLS, (h + PFX_MB2_ROWS - 1) / PFX_MB2_ROWS);
 #define PFX_MB2(R) case R: if (d_mask) median_bits2_kernel<R, true><<<g2, 256, 0, s>>>(d_src, d_planes, d_dst, d_mask, (int)w, (int)h, nd); \
                            else median_bits2_kernel<R, false><<<g2, 256, 0, s>>>(d_src, d_planes, d_dst, d_mask, (int)w, (int)h, nd); break;

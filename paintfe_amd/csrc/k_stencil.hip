@@ -867,57 +867,31 @@ __global__ __launch_bounds__(256) void pixelate4_kernel(const uint32_t* __restri
 
 } // namespace
 
-int g_median_search1 = 0; // pfxk_median_set_search1: the value search with one pixel per lane (the pre-sharing kernel)
-extern "C" void pfxk_median_set_search1(int on) { g_median_search1 = on; }
-int g_median_xlane = 1;  // pfxk_median_set_xlane (pfx_tune "median_xlane"): bits 0-1: radius 2 on the cross-lane network, one (1) or two (2) rows per lane, or on median_shared_kernel (0); bit 2: radius 3 on it too
-extern "C" void pfxk_median_set_xlane(int on) { g_median_xlane = on; }
-extern "C" int pfxk_median_get_xlane(void) { return g_median_xlane; }
-int g_median_single = 0; // pfxk_median_set_single: the one-window-per-lane networks for radii 2 and 3
-extern "C" void pfxk_median_set_single(int on) { g_median_single = on; }
-// radii from which a lane takes 16 columns instead of 8 / 64 rows instead of 16 (128 rows from twice that radius on).  Round-4 sweep of 3 x 4 shapes per radius
-// (tools/lab/box_sweep.py, profiles/r04_box_sweep.txt): 8K r = 5 / 9 / 16 / 24 0.132 / 0.145 / 0.157 / 0.171 -> 0.128 / 0.139 / 0.151 / 0.165 ms; r >= 48 unchanged
-int g_box_px_switch = 12, g_box_py_switch = 20;
-extern "C" void pfxk_box_set_switch(int px, int py) { if (px >= 0) g_box_px_switch = px; if (py >= 0) g_box_py_switch = py; }
-// radii from which the horizontal pass uses prefix sums (pfx_tune "box_prefix_from"; 0 = never).  8K, tools/lab/box_prefix_ab.py: the prefix pass costs ~0.115 ms whatever the
-// radius (three barriers, a 6-step scan), the sliding window 0.06 ms at r = 9 and 0.15 at r = 100: r = 48 0.201 / 0.221 ms, r = 100 0.276 / 0.237, r = 300 0.570 / 0.339
-int g_box_prefix_from = 72;
-extern "C" void pfxk_box_set_prefix_from(int r) { g_box_prefix_from = r; }
-inline int bxp_words_host(int r) { const int i = BXP_TILE + 2 * r + 1; return i + (i >> 5) + 1; }
-int g_box_px_force = 0, g_box_py_force = 0; // development sweep (pfx_tune "box_px" / "box_py"): 0 = by radius
-extern "C" void pfxk_box_set_force(int px, int py) { if (px >= 0) g_box_px_force = px; if (py >= 0) g_box_py_force = py; }
-int g_box_two_pass = 0; // pfxk_box_set_two_pass: keep the u8 intermediate in HBM (the pre-fusion path; A/B and parity tests)
-extern "C" void pfxk_box_set_two_pass(int on) { g_box_two_pass = on; }
-int g_box_strip = 2, g_box_strip_fill = 100, g_box_strip_nseg = 0; // pfxk_box_set_strip: 2 (default) = the fused strip walk for radii 1 .. BS_MAXR (8K r = 1 .. 4: 0.085-0.098 ms against the 64 x 64 tile kernel's 0.095-0.102),
-                                                                    // 1 = the tile kernel up to BF_MAXR and the strip walk above, 0 = tile kernel / two passes; chip fill in % of one round of workgroups; forced segment count
-extern "C" void pfxk_box_set_strip(int on, int fill, int nseg) { if (on >= 0) g_box_strip = on; if (fill > 0) g_box_strip_fill = fill; if (nseg >= 0) g_box_strip_nseg = nseg; }
-extern "C" hipError_t pfxk_box_blur(hipStream_t s, const uint8_t* d_src, uint8_t* d_tmp, uint8_t* d_dst,
-                                    const uint8_t* d_mask, int radius, uint32_t w, uint32_t h, int force_two_pass)
+// the compiled limits, for the one place that chooses the kernel (pfx_stencil.cpp: pfx_int_box_plan); the launcher below refuses a plan outside them
+constexpr size_t bxp_lds(int r) { const int i = BXP_TILE + 2 * r + 1; return ((size_t)5 * (i + (i >> 5) + 1) + 16) * 4; }   // 5 x bxp_words(r) + 16 words
+extern "C" int pfxk_box_tile_max_radius(void) { return BF_MAXR; }
+extern "C" int pfxk_box_strip_max_radius(void) { return BS_MAXR; }
+extern "C" int pfxk_box_prefix_max_radius(void) { static const int rmax = [] { int r = 0; while (bxp_lds(r + 1) <= 160u * 1024u) ++r; return r; }(); return rmax; }
+extern "C" hipError_t pfxk_box_blur(hipStream_t s, const uint8_t* d_src, uint8_t* d_tmp, uint8_t* d_dst, const uint8_t* d_mask, int radius, uint32_t w, uint32_t h,
+                                    const pfx_box_plan* plan, int strip_fill, int strip_nseg)
 {
     if (w == 0 || h == 0) return hipSuccess;
     const uint32_t d = (uint32_t)(2 * radius + 1);
-    if (d >= 4096u) return hipErrorInvalidValue;
+    if (radius < 1 || d >= 4096u) return hipErrorInvalidValue;
     const uint32_t magic = (uint32_t)((0x100000000ull / d) + 1ull), half = d / 2u;
-    if (radius <= BF_MAXR && g_box_strip != 2 && g_box_two_pass == 0 && !force_two_pass && d_src != d_dst) { // small radii: both passes in one kernel (the halo recomputation stays below 1.6x)
+    if (plan->kind == PFX_BOX_TILE) { // small radii: both passes in one kernel (the halo recomputation stays below 1.6x)
+        static_assert(BF_MAXR == 4, "box_fused_kernel is instantiated for radii 1 .. 4");
+        static decltype(&box_fused_kernel<1>) const kernels[BF_MAXR] = {box_fused_kernel<1>, box_fused_kernel<2>, box_fused_kernel<3>, box_fused_kernel<4>};
+        static lds_grant grants[BF_MAXR];
+        if (radius > BF_MAXR || d_src == d_dst) return hipErrorInvalidValue;   // in place the kernel would stage a halo tile from src while neighbouring workgroups write dst
         const int side = BF_T + 2 * radius;
         const size_t lds = (size_t)(side * (side | 1) + side * (BF_T + 1)) * 4;
-        auto go = [&](auto rc) -> hipError_t {
-            constexpr int R = decltype(rc)::value;
-            static lds_grant grant;
-            hipError_t e = grant_lds(grant, (const void*)box_fused_kernel<R>, lds);
-            if (e) return e;
-            box_fused_kernel<R><<<dim3((w + BF_T - 1) / BF_T, (h + BF_T - 1) / BF_T), 256, lds, s>>>((const uint32_t*)d_src, d_mask, (uint32_t*)d_dst, half, magic, (int)w, (int)h);
-            return hipGetLastError();
-        };
-        static_assert(BF_MAXR == 4, "box_fused_kernel is instantiated for radii 1 .. 4");
-        switch (radius) {
-        case 1: return go(std::integral_constant<int, 1>{});
-        case 2: return go(std::integral_constant<int, 2>{});
-        case 3: return go(std::integral_constant<int, 3>{});
-        case 4: return go(std::integral_constant<int, 4>{});
-        default: break;   // radius 0 never reaches the kernels (pfx_api.cpp copies); fall through to the two-pass path
-        }
+        if (hipError_t e = grant_lds(grants[radius - 1], (const void*)kernels[radius - 1], lds)) return e;
+        kernels[radius - 1]<<<dim3((w + BF_T - 1) / BF_T, (h + BF_T - 1) / BF_T), 256, lds, s>>>((const uint32_t*)d_src, d_mask, (uint32_t*)d_dst, half, magic, (int)w, (int)h);
+        return hipGetLastError();
     }
-    if ((radius > BF_MAXR || g_box_strip == 2) && radius >= 1 && radius <= BS_MAXR && g_box_strip && g_box_two_pass == 0 && !force_two_pass && d_src != d_dst && (uint64_t)w * h < (1ull << 29)) { // fused strip walk, no intermediate in HBM
+    if (plan->kind == PFX_BOX_STRIP) { // fused strip walk, no intermediate in HBM
+        if (radius > BS_MAXR || d_src == d_dst || (uint64_t)w * h >= (1ull << 29)) return hipErrorInvalidValue;
         const int RR = 2 * radius + 1 + BS_RB;
         const size_t lds = (size_t)(((RR * BS_RP + 3) & ~3) + 4 * 2 * bs_pp(radius)) * 4;   // the ring, then two rows of prefix pairs per wave on a 16-byte boundary
         const int strips = (int)((w + BS_W - 1) / BS_W);
@@ -925,53 +899,31 @@ extern "C" hipError_t pfxk_box_blur(hipStream_t s, const uint8_t* d_src, uint8_t
         // second, partly filled round would double the launch's time.  Segments are at least 6r rows (the 2r rows of run-in stay below a third).
         const int wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160u * 1024u) / lds));
         const int sg_max = (strips + 7) / 8;
-        int nseg = std::max(1, 32 * wg_per_cu * g_box_strip_fill / 100 / sg_max);
+        int nseg = std::max(1, 32 * wg_per_cu * strip_fill / 100 / sg_max);
         nseg = std::min(nseg, std::max(1, (int)h / std::max(64, 6 * radius)));
-        if (g_box_strip_nseg > 0) nseg = g_box_strip_nseg;
+        if (strip_nseg > 0) nseg = strip_nseg;
         const int seg_rows = ((int)h + nseg - 1) / nseg;
         nseg = ((int)h + seg_rows - 1) / seg_rows;
         const float inv_d = 1.0f / (float)d;
-        auto go = [&](auto mk) -> hipError_t {
-            constexpr bool MK = decltype(mk)::value;
-            static lds_grant grant;
-            hipError_t e = grant_lds(grant, (const void*)box_strip_kernel<MK>, lds);
-            if (e) return e;
-            box_strip_kernel<MK><<<dim3(8u * (uint32_t)(sg_max * nseg)), 256, lds, s>>>((const uint32_t*)d_src, d_mask, (uint32_t*)d_dst, radius, inv_d, (int)w, (int)h,
-                                                                                      seg_rows, nseg, strips);
-            return hipGetLastError();
-        };
-        return d_mask ? go(std::true_type{}) : go(std::false_type{});
+        static lds_grant grants[2];
+        const auto kernel = d_mask ? box_strip_kernel<true> : box_strip_kernel<false>;
+        if (hipError_t e = grant_lds(grants[d_mask != nullptr], (const void*)kernel, lds)) return e;
+        kernel<<<dim3(8u * (uint32_t)(sg_max * nseg)), 256, lds, s>>>((const uint32_t*)d_src, d_mask, (uint32_t*)d_dst, radius, inv_d, (int)w, (int)h, seg_rows, nseg, strips);
+        return hipGetLastError();
     }
-    // outputs per lane grow with the radius: a lane's first window costs 2r + 1 reads whatever it is followed by
-    auto launch_h = [&](auto px_c) -> hipError_t {
-        constexpr int PX = decltype(px_c)::value;
-        const int n = BX_THREADS * PX + 2 * radius, n2 = BX_THREADS * PX;
-        const size_t lds = (size_t)((n + (n >> 5) + 1) + (n2 + (n2 >> 5) + 1)) * 4;
-        hipError_t e = grant_lds_for((const void*)box_h_kernel<PX>, lds);
-        if (e) return e;
-        box_h_kernel<PX><<<dim3((w + BX_THREADS * PX - 1) / (BX_THREADS * PX), h), BX_THREADS, lds, s>>>((const uint32_t*)d_src, (uint32_t*)d_tmp, radius, half, magic, (int)w, (int)h);
+    // the two passes, H into d_tmp (tile: a workgroup's outputs per row).  Outputs per lane grow with the radius: a lane's first window costs 2r + 1 reads whatever follows it
+    auto launch_h = [&](auto kernel, int tile, size_t lds) -> hipError_t {
+        if (lds > 160u * 1024u) return hipErrorInvalidValue;
+        if (hipError_t e = grant_lds_for((const void*)kernel, lds)) return e;
+        kernel<<<dim3((w + tile - 1) / tile, h), BX_THREADS, lds, s>>>((const uint32_t*)d_src, (uint32_t*)d_tmp, radius, half, magic, (int)w, (int)h);
         return hipGetLastError();
     };
-    const int px = g_box_px_force ? g_box_px_force : (radius < g_box_px_switch ? 8 : 16);
-    if (g_box_prefix_from > 0 && radius >= g_box_prefix_from && g_box_px_force == 0) {
-        const size_t lds = ((size_t)5 * bxp_words_host(radius) + 16) * 4;
-        if (lds <= 160u * 1024u) {
-            hipError_t e0 = grant_lds_for((const void*)box_h_prefix_kernel, lds);
-            if (e0) return e0;
-            box_h_prefix_kernel<<<dim3((w + BXP_TILE - 1) / BXP_TILE, h), BX_THREADS, lds, s>>>((const uint32_t*)d_src, (uint32_t*)d_tmp, radius, half, magic, (int)w, (int)h);
-            e0 = hipGetLastError();
-            if (e0) return e0;
-            goto vertical;
-        }
-    }
-    {
-    hipError_t e = px == 4 ? launch_h(std::integral_constant<int, 4>{}) : (px == 8 ? launch_h(std::integral_constant<int, 8>{}) : launch_h(std::integral_constant<int, 16>{}));
+    auto sliding = [&](auto kernel, int px) { const int n2 = BX_THREADS * px, n = n2 + 2 * radius; return launch_h(kernel, n2, (size_t)((n + (n >> 5) + 1) + (n2 + (n2 >> 5) + 1)) * 4); };
+    const hipError_t e = plan->h_kind == PFX_BOX_PREFIX ? launch_h(box_h_prefix_kernel, BXP_TILE, bxp_lds(radius))
+                       : plan->px == 4 ? sliding(box_h_kernel<4>, 4) : (plan->px == 8 ? sliding(box_h_kernel<8>, 8) : sliding(box_h_kernel<16>, 16));
     if (e) return e;
-    }
-vertical:
 #define PFX_BV(PY) box_v_kernel<PY><<<dim3((w + 63) / 64, (h + 4 * PY - 1) / (4 * PY)), 256, 0, s>>>((const uint32_t*)d_tmp, (const uint32_t*)d_src, d_mask, (uint32_t*)d_dst, radius, half, magic, (int)w, (int)h)
-    const int py = g_box_py_force ? g_box_py_force : (radius < g_box_py_switch ? 16 : (radius < 2 * g_box_py_switch ? 64 : 128));
-    if (py == 16) PFX_BV(16); else if (py == 32) PFX_BV(32); else if (py == 64) PFX_BV(64); else PFX_BV(128);
+    if (plan->py == 16) PFX_BV(16); else if (plan->py == 32) PFX_BV(32); else if (plan->py == 64) PFX_BV(64); else PFX_BV(128);
 #undef PFX_BV
     return hipGetLastError();
 }
@@ -1027,73 +979,48 @@ __global__ __launch_bounds__(64) void median_hist_kernel(const uint32_t* __restr
     }
 }
 
-extern "C" hipError_t pfxk_median(hipStream_t s, const uint8_t* d_src, uint8_t* d_dst, const uint8_t* d_mask, int radius,
-                                  uint32_t w, uint32_t h)
+// `path`: what pfx_stencil.cpp chose (pfx_int_median_path); a radius the path has no kernel for is refused.  The aligned (VEC / DIRECT) instantiations are geometry, not choice
+extern "C" hipError_t pfxk_median(hipStream_t s, const uint8_t* d_src, uint8_t* d_dst, const uint8_t* d_mask, int path, int radius, uint32_t w, uint32_t h)
 {
     if (w == 0 || h == 0) return hipSuccess;
-    if (radius <= 1) { // 3x3: min3/med3/max3 network
-        const dim3 g((w + 255) / 256, (h + 3) / 4);
-        if ((w & 3u) == 0 && (((uintptr_t)d_src | (uintptr_t)d_dst) & 15u) == 0) median3_kernel<true><<<g, 256, 0, s>>>((const uint32_t*)d_src, (uint32_t*)d_dst, d_mask, (int)w, (int)h);
-        else median3_kernel<false><<<g, 256, 0, s>>>((const uint32_t*)d_src, (uint32_t*)d_dst, d_mask, (int)w, (int)h);
+    const bool direct = (w & 3u) == 0 && (((uintptr_t)d_src | (uintptr_t)d_dst) & 15u) == 0;
+    auto run = [&](auto kernel, dim3 g, int block, size_t lds, auto... r) -> hipError_t {   // r: the radius, for the kernels that take it at run time
+        if (lds) if (hipError_t e = grant_lds_for((const void*)kernel, lds)) return e;
+        kernel<<<g, block, lds, s>>>((const uint32_t*)d_src, (uint32_t*)d_dst, d_mask, r..., (int)w, (int)h);
         return hipGetLastError();
+    };
+    auto tiles = [&](int tx, int ty) { return dim3((w + tx - 1) / tx, (h + ty - 1) / ty); };
+    switch (path) {
+    case PFX_MEDIAN_NET3: // 3x3: min3/med3/max3 network
+        if (radius != 1) break;
+        return direct ? run(median3_kernel<true>, tiles(256, 4), 256, 0) : run(median3_kernel<false>, tiles(256, 4), 256, 0);
+    case PFX_MEDIAN_XLANE7: // 7x7 on the cross-lane network (pfx_tune "median_xlane" bit 2)
+        if (radius != 3) break;
+        return direct ? run(median_xlane2_kernel<true, 1, 3>, tiles(MX_W, MX_H), 256, 0) : run(median_xlane2_kernel<false, 1, 3>, tiles(MX_W, MX_H), 256, 0);
+    case PFX_MEDIAN_XLANE: case PFX_MEDIAN_XLANE_ROWS2: // 5x5: four windows per lane, sorted columns shared across lanes, one row per lane or two
+        if (radius != 2) break;
+        if (path == PFX_MEDIAN_XLANE_ROWS2) return direct ? run(median_xlane2_kernel<true, 2>, tiles(MX_W, 2 * MX_H), 256, 0) : run(median_xlane2_kernel<false, 2>, tiles(MX_W, 2 * MX_H), 256, 0);
+        return direct ? run(median_xlane2_kernel<true, 1>, tiles(MX_W, MX_H), 256, 0) : run(median_xlane2_kernel<false, 1>, tiles(MX_W, MX_H), 256, 0);
+    case PFX_MEDIAN_SHARED: // 5x5 / 7x7 / 9x9: four windows per lane on shared sorted columns
+        if (radius == 2) return direct ? run(median_shared_kernel<2, true>, tiles(MS_W, MS_H), 256, 0) : run(median_shared_kernel<2, false>, tiles(MS_W, MS_H), 256, 0);
+        if (radius == 3) return direct ? run(median_shared_kernel<3, true>, tiles(MS_W, MS_H), 256, 0) : run(median_shared_kernel<3, false>, tiles(MS_W, MS_H), 256, 0);
+        if (radius == 4) return direct ? run(median_shared_kernel<4, true>, tiles(MS_W, MS_H), 256, 0) : run(median_shared_kernel<4, false>, tiles(MS_W, MS_H), 256, 0);
+        break;
+    case PFX_MEDIAN_SINGLE_NET: // the single-window selection networks (pfx_tune "median_single": A/B and parity of the two paths)
+        if (radius == 2) return run(median_net_kernel<2>, tiles(MD_TX, MD_TY), MD_TX * MD_TY, 0);
+        if (radius == 3) return run(median_net_kernel<3>, tiles(MD_TX, MD_TY), MD_TX * MD_TY, 0);
+        break;
+    case PFX_MEDIAN_HIST: // sliding histogram, a lane per run of MH_RUN pixels (16-bit counters: the entry points stop at PFX_MEDIAN_MAX_RADIUS)
+        if (radius < 1) break;
+        return run(median_hist_kernel, dim3((uint32_t)(((size_t)((w + MH_RUN - 1) / MH_RUN) * h + 63) / 64)), 64, (size_t)4 * 256 * 64 * sizeof(uint16_t), radius);
+    case PFX_MEDIAN_SEARCH4: // the value search, four pixels per lane: a third of the LDS reads per pixel
+        if (radius < 1 || radius > PFXK_MEDIAN_TILE_MAX_RADIUS) break;
+        return run(median_search4_kernel, tiles(MQ_TX, MQ_TY), 256, (size_t)(MQ_TX + 2 * radius) * (MQ_TY + 2 * radius) * 8, radius);
+    case PFX_MEDIAN_SEARCH1: // ... one pixel per lane (the pre-sharing kernel)
+        if (radius < 1 || radius > PFXK_MEDIAN_TILE_MAX_RADIUS) break;
+        return run(median_kernel, tiles(MD_TX, MD_TY), MD_TX * MD_TY, (size_t)(MD_TX + 2 * radius) * (MD_TY + 2 * radius) * 8, radius);
     }
-    if (radius == 3 && (g_median_xlane & 4) && !g_median_single) { // 7x7 on the cross-lane network (pfx_tune "median_xlane" bit 2; pfx_api.cpp routes r = 3 here only then)
-        const bool direct = (w & 3u) == 0 && w >= 4 && (((uintptr_t)d_src | (uintptr_t)d_dst) & 15u) == 0;
-        const dim3 g((w + MX_W - 1) / MX_W, (h + MX_H - 1) / MX_H);
-        if (direct) median_xlane2_kernel<true, 1, 3><<<g, 256, 0, s>>>((const uint32_t*)d_src, (uint32_t*)d_dst, d_mask, (int)w, (int)h);
-        else median_xlane2_kernel<false, 1, 3><<<g, 256, 0, s>>>((const uint32_t*)d_src, (uint32_t*)d_dst, d_mask, (int)w, (int)h);
-        return hipGetLastError();
-    }
-    if (radius == 2 && (g_median_xlane & 3) && !g_median_single) { // 5x5: four windows per lane, sorted columns shared across lanes
-        const bool direct = (w & 3u) == 0 && w >= 4 && (((uintptr_t)d_src | (uintptr_t)d_dst) & 15u) == 0;
-        if ((g_median_xlane & 3) == 2) {   // two rows per lane
-            const dim3 g((w + MX_W - 1) / MX_W, (h + 2 * MX_H - 1) / (2 * MX_H));
-            if (direct) median_xlane2_kernel<true, 2><<<g, 256, 0, s>>>((const uint32_t*)d_src, (uint32_t*)d_dst, d_mask, (int)w, (int)h);
-            else median_xlane2_kernel<false, 2><<<g, 256, 0, s>>>((const uint32_t*)d_src, (uint32_t*)d_dst, d_mask, (int)w, (int)h);
-        } else {
-            const dim3 g((w + MX_W - 1) / MX_W, (h + MX_H - 1) / MX_H);
-            if (direct) median_xlane2_kernel<true, 1><<<g, 256, 0, s>>>((const uint32_t*)d_src, (uint32_t*)d_dst, d_mask, (int)w, (int)h);
-            else median_xlane2_kernel<false, 1><<<g, 256, 0, s>>>((const uint32_t*)d_src, (uint32_t*)d_dst, d_mask, (int)w, (int)h);
-        }
-        return hipGetLastError();
-    }
-    if (radius >= 2 && radius <= 4 && !g_median_single) { // 5x5 / 7x7 / 9x9: four windows per lane on shared sorted columns
-        const dim3 g((w + MS_W - 1) / MS_W, (h + MS_H - 1) / MS_H);
-        const bool direct = (w & 3u) == 0 && (((uintptr_t)d_src | (uintptr_t)d_dst) & 15u) == 0;
-#define PFX_MS(R, D) median_shared_kernel<R, D><<<g, 256, 0, s>>>((const uint32_t*)d_src, (uint32_t*)d_dst, d_mask, (int)w, (int)h)
-        if (radius == 2) { if (direct) PFX_MS(2, true); else PFX_MS(2, false); }
-        else if (radius == 3) { if (direct) PFX_MS(3, true); else PFX_MS(3, false); }
-        else { if (direct) PFX_MS(4, true); else PFX_MS(4, false); }
-#undef PFX_MS
-        return hipGetLastError();
-    }
-    if (radius == 2 || radius == 3) { // the single-window selection networks (pfx_tune "median_single": A/B and parity of the two paths)
-        const dim3 g((w + MD_TX - 1) / MD_TX, (h + MD_TY - 1) / MD_TY);
-        if (radius == 2) median_net_kernel<2><<<g, MD_TX * MD_TY, 0, s>>>((const uint32_t*)d_src, (uint32_t*)d_dst, d_mask, (int)w, (int)h);
-        else median_net_kernel<3><<<g, MD_TX * MD_TY, 0, s>>>((const uint32_t*)d_src, (uint32_t*)d_dst, d_mask, (int)w, (int)h);
-        return hipGetLastError();
-    }
-    if (radius > PFXK_MEDIAN_TILE_MAX_RADIUS) { // sliding histogram
-        const size_t lds_h = (size_t)4 * 256 * 64 * sizeof(uint16_t);
-        hipError_t eh = grant_lds_for((const void*)median_hist_kernel, lds_h);
-        if (eh) return eh;
-        const size_t runs = (size_t)((w + MH_RUN - 1) / MH_RUN) * h;
-        median_hist_kernel<<<(uint32_t)((runs + 63) / 64), 64, lds_h, s>>>((const uint32_t*)d_src, (uint32_t*)d_dst, d_mask, radius, (int)w, (int)h);
-        return hipGetLastError();
-    }
-    if (!g_median_search1) { // four pixels per lane: a third of the LDS reads per pixel
-        const size_t lds4 = (size_t)(MQ_TX + 2 * radius) * (MQ_TY + 2 * radius) * 8;
-        hipError_t e4 = grant_lds_for((const void*)median_search4_kernel, lds4);
-        if (e4) return e4;
-        median_search4_kernel<<<dim3((w + MQ_TX - 1) / MQ_TX, (h + MQ_TY - 1) / MQ_TY), 256, lds4, s>>>((const uint32_t*)d_src, (uint32_t*)d_dst, d_mask, radius, (int)w, (int)h);
-        return hipGetLastError();
-    }
-    const size_t lds = (size_t)(MD_TX + 2 * radius) * (MD_TY + 2 * radius) * 8;
-    hipError_t e = grant_lds_for((const void*)median_kernel, lds);
-    if (e) return e;
-    dim3 g((w + MD_TX - 1) / MD_TX, (h + MD_TY - 1) / MD_TY);
-    median_kernel<<<g, MD_TX * MD_TY, lds, s>>>((const uint32_t*)d_src, (uint32_t*)d_dst, d_mask, radius, (int)w, (int)h);
-    return hipGetLastError();
+    return hipErrorInvalidValue;
 }
 
 extern "C" hipError_t pfxk_pixelate(hipStream_t s, const uint8_t* d_src, uint8_t* d_dst, const uint8_t* d_mask, uint32_t bs,

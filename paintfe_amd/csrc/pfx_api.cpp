@@ -473,16 +473,7 @@ int pfx_box_blur_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t 
     }
     const float rc = ceilf(radius);
     PFX_REQUIRE(ctx, rc < 2040.0f, "box blur radius too large");
-    if (!tmp_dev) {
-        PFX_TRY(pfx_reserve(ctx, ctx->st_tmp, img_bytes(w, h)));
-        tmp_dev = ctx->st_tmp.p;
-    }
-    pfx_timer t(ctx, "box_blur");
-    // in place: the two-pass path (H into tmp, V reads tmp and only its own pixel of src); the fused kernel stages a halo tile from src
-    // while neighbouring workgroups write dst
-    PFX_HIP(ctx, pfxk_box_blur(ctx->stream, (const uint8_t*)src_dev, (uint8_t*)tmp_dev, (uint8_t*)dst_dev,
-                               (const uint8_t*)mask_dev, (int)rc, w, h, src_dev == dst_dev ? 1 : 0));
-    return PFX_OK;
+    return pfx_stencil_box(ctx, src_dev, dst_dev, w, h, (int)rc, mask_dev, tmp_dev);   // which kernels run: pfx_stencil.cpp
 }
 
 int pfx_box_blur_band_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, float radius, const void* mask_dev,
@@ -505,16 +496,7 @@ int pfx_median_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w,
     PFX_TRY(check_disjoint(ctx, src_dev, dst_dev, w, h, "pfx_median_dev"));
     const uint32_t r = std::max(radius, 1u); // noise.rs:364
     if (r > PFX_MEDIAN_MAX_RADIUS) return pfx_fail(ctx, PFX_ERR_UNSUPPORTED, "median radius %u > %d", r, PFX_MEDIAN_MAX_RADIUS);
-    const bool xlane3 = r == 3u && (pfxk_median_get_xlane() & 4);   // 7x7 on the cross-lane network (pfx_tune "median_xlane" bit 2)
-    if ((int)r >= ctx->median_bits_min && r <= 8u && !xlane3) { // bit-sliced radix select (k_median_bits.hip); scratch ~ the image size
-        PFX_TRY(pfx_reserve(ctx, ctx->st_tmp, pfxk_median_bits_scratch((int)r, w, h)));
-        pfx_timer t(ctx, "median");
-        PFX_HIP(ctx, pfxk_median_bits(ctx->stream, (const uint8_t*)src_dev, (uint8_t*)dst_dev, (const uint8_t*)mask_dev, (uint32_t*)ctx->st_tmp.p, (int)r, w, h));
-        return PFX_OK;
-    }
-    pfx_timer t(ctx, "median");
-    PFX_HIP(ctx, pfxk_median(ctx->stream, (const uint8_t*)src_dev, (uint8_t*)dst_dev, (const uint8_t*)mask_dev, (int)r, w, h));
-    return PFX_OK;
+    return pfx_stencil_median(ctx, src_dev, dst_dev, w, h, (int)r, mask_dev);   // which kernel runs: pfx_stencil.cpp
 }
 
 int pfx_pixelate_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, uint32_t block_size, const void* mask_dev)
@@ -1478,25 +1460,12 @@ int pfx_tune(pfx_ctx* ctx, const char* key, int value)
     if (std::strcmp(key, "dle_kernel") == 0) { pfxk_flatten_set_dle_plan(value, -2, -2); return PFX_OK; }   // 0 = class sorting, 1 = round-3 kernel
     if (std::strcmp(key, "dle_s1") == 0) { pfxk_flatten_set_dle_plan(-1, value, -2); return PFX_OK; }       // re-deal attempts: first one this many layers above the topmost candidate (-1: 1, 0: never)
     if (std::strcmp(key, "dle_s2") == 0) { pfxk_flatten_set_dle_plan(-1, -2, value); return PFX_OK; }       // ... then every this many layers (-1: 3, 0: only the first)
-    if (std::strcmp(key, "median_search1") == 0) { pfxk_median_set_search1(value); return PFX_OK; }
+    if (std::strncmp(key, "median_", 7) == 0 || std::strncmp(key, "box_", 4) == 0) return pfx_stencil_tune(ctx, key, value);   // the knobs live in pfx_stencil.cpp
     if (std::strcmp(key, "outline_bits") == 0) { ctx->outline_bits = value != 0; return PFX_OK; }
     if (std::strcmp(key, "brush_binning") == 0) { ctx->brush_binning = value != 0; return PFX_OK; }   // 0: long strokes on the bounding-box kernel too
-    if (std::strcmp(key, "median_xlane") == 0) { pfxk_median_set_xlane(value); return PFX_OK; } // 0: radius 2 on the per-lane shared-column network (round 3's kernel)
-    if (std::strcmp(key, "median_pair") == 0) { pfxk_median_bits_set_pair(value); return PFX_OK; } // 0: the single-column bit-plane kernel for every radius
-    if (std::strcmp(key, "median_bits_min") == 0) { ctx->median_bits_min = value; return PFX_OK; } // smallest radius on the bit-plane kernel (8: never)
-    if (std::strcmp(key, "median_single") == 0) { pfxk_median_set_single(value); return PFX_OK; }
-    if (std::strcmp(key, "box_prefix_from") == 0) { pfxk_box_set_prefix_from(value); return PFX_OK; }
-    if (std::strcmp(key, "box_px") == 0) { pfxk_box_set_force(value, -1); return PFX_OK; }
-    if (std::strcmp(key, "box_py") == 0) { pfxk_box_set_force(-1, value); return PFX_OK; }
-    if (std::strcmp(key, "box_px_switch") == 0) { pfxk_box_set_switch(value, -1); return PFX_OK; }
-    if (std::strcmp(key, "box_py_switch") == 0) { pfxk_box_set_switch(-1, value); return PFX_OK; }
     if (std::strcmp(key, "dle_adaptive") == 0) { ctx->dle_adaptive = value != 0; ctx->dle_probe_state = 0; return PFX_OK; }   // 0 = shallow stacks never take the elimination kernel
     if (std::strcmp(key, "gauss_fused_exact") == 0) { pfxk_gauss_set_fused_exact(value); return PFX_OK; }  // 0 = the bit-exact Gaussian always through the two kernels
     if (std::strcmp(key, "mesh_xcd") == 0) { pfxk_warp_set_mesh_xcd(value); return PFX_OK; }            // 0 = the fused mesh warp's plain 2-D tile order
-    if (std::strcmp(key, "box_strip") == 0) { pfxk_box_set_strip(value, 0, -1); return PFX_OK; }          // 0 = radii >= 5 through the two-pass kernels
-    if (std::strcmp(key, "box_strip_fill") == 0) { pfxk_box_set_strip(-1, value, -1); return PFX_OK; }
-    if (std::strcmp(key, "box_strip_nseg") == 0) { pfxk_box_set_strip(-1, 0, value); return PFX_OK; }
-    if (std::strcmp(key, "box_two_pass") == 0) { pfxk_box_set_two_pass(value); return PFX_OK; }
     if (std::strcmp(key, "shadow_plane") == 0) { ctx->shadow_plane_blur = value != 0; return PFX_OK; } // drop shadow: blur the alpha plane (1) or the RGBA expansion (0); identical results
     if (std::strcmp(key, "gauss_cols64") == 0) { pfxk_gauss_set_mfma_cols64(value); return PFX_OK; } // matrix-core Gaussian at 8 K blocks: 64-column (1) / 32-column (0) strips, same bits
     if (std::strcmp(key, "chain_fuse_heavy") == 0) { ctx->chain_fuse_heavy = value != 0; return PFX_OK; } // pfx_chain_dev: HSL / vibrance in a Gaussian's store too (measured: no gain)

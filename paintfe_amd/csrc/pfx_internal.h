@@ -45,7 +45,8 @@ struct pfx_ctx {
     pfx_devbuf st_in, st_out, st_mask, st_tmp, st_aux, st_aux2;
     bool outline_bits = true;  // pfx_tune "outline_bits": the outline's window search on a bit plane of alpha != 0 (0: the per-element scan)
     bool brush_binning = true; // pfx_tune "brush_binning": strokes of more than 64 stamps are dealt to 64 x 64 chunks on the host (pfx_brush_stamps_ex_dev)
-    int median_bits_min = 3;   // pfx_tune "median_bits_min": radii >= this (and <= 8) take k_median_bits.hip (r = 2: 0.35 ms against the networks' 0.22)
+    int median_bits_min = 3;   // pfx_tune "median_bits_min", the one per-context knob of pfx_stencil.cpp (see pfx_int_median_path there)
+    int last_median_path = -1, last_box_plan = -1;   // what pfx_stencil_median / _box last launched; pfx_int_stencil_last_path reads them, nothing else does
     pfx_devbuf fx_a, fx_b; // effect-bank scratch (crystallize cell table, drop-shadow planes)
     // small parameter buffers
     pfx_devbuf d_desc, d_adj, d_chunks, d_wts, d_lut, d_pts, d_misc;
@@ -170,6 +171,17 @@ int pfx_gauss_combine(pfx_ctx* ctx, bool exact, const void* src_dev, void* dst_d
 int pfx_gauss_chain(pfx_ctx* ctx, bool exact, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, float sigma, const pfxk_chain* C, bool heavy, bool* rode);
 bool pfx_gauss_plane_applies(const pfx_ctx* ctx, bool exact, uint32_t w, uint32_t h, int radius);
 int pfx_gauss_plane(pfx_ctx* ctx, const void* src_plane, void* dst_plane, uint32_t w, uint32_t h, float sigma);
+
+// ---- the median's and the box blur's host side (pfx_stencil.cpp): pfx_tune's knobs, the one decision which kernel runs, the launches ----
+struct pfx_median_case { int radius /* after max(radius, 1) */, bits_min, xlane, single, search1, pair; };   // plain ints: the knobs under their pfx_tune names less "median_"
+struct pfx_box_case { int radius /* ceil, >= 1 */, in_place; uint32_t w, h; int strip, two_pass, prefix_from, px_force, py_force, px_switch, py_switch; };
+// the decisions, pure, exported as test seams (not in include/pfx.h): a PFX_MEDIAN_* path; the plan's kind with *plan filled (pfx_kernels.h)
+extern "C" int pfx_int_median_path(const pfx_median_case* c);
+extern "C" int pfx_int_box_plan(const pfx_box_case* c, pfx_box_plan* plan);
+extern "C" int pfx_int_stencil_last_path(pfx_ctx* ctx, int which);   // for the tests, what the context's last call ran: which = 0 the median's path, 1 the box blur's kind | h_kind << 4 | px << 8 | py << 16; -1 = none yet
+int pfx_stencil_tune(pfx_ctx* ctx, const char* key, int value);   // pfx_tune's median_* and box_* keys
+int pfx_stencil_median(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, int radius, const void* mask_dev);   // arguments are the caller's to check
+int pfx_stencil_box(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, int radius, const void* mask_dev, void* tmp_dev /* NULL: st_tmp */);
 
 // blur_with_selection on device-resident images (pfx_api.cpp); mask_host may be NULL (= no selection)
 int pfx_int_blur_with_selection_dev(pfx_ctx* ctx, const void* d_src, void* d_dst, uint32_t w, uint32_t h, float sigma,

@@ -145,26 +145,21 @@ hipError_t pfxk_select_by_mask(hipStream_t s, const uint8_t* d_src, const uint8_
 hipError_t pfxk_minmax_rgb(hipStream_t s, const uint8_t* d_src, const uint8_t* d_mask, uint32_t w, uint32_t h,
                            uint32_t* d_out6);
 
-// ---- k_stencil.hip ---- box blur / median / pixelate
-void pfxk_box_set_two_pass(int on);
-void pfxk_box_set_prefix_from(int radius); // two-pass box blur: radii from which the horizontal pass uses prefix sums (0 = never)
-void pfxk_box_set_force(int px, int py); // development sweep: outputs per lane of the two passes (0 = by radius, -1: keep)
-void pfxk_box_set_switch(int px_radius, int py_radius); // two-pass box blur: radii from which a lane takes 32 columns / 128 rows (-1: keep)
-void pfxk_median_set_search1(int on); // value search (radii 5..24, and 4 with median_single) with one pixel per lane instead of four
-void pfxk_median_set_single(int on); // radii 2, 3: one window per lane (the pre-sharing selection networks)
-int pfxk_median_get_xlane(void);
-void pfxk_median_set_xlane(int on); // 1 (default): radius 2 on the network whose sorted columns are shared across lanes (median_xlane2_kernel)
-void pfxk_box_set_strip(int on /* -1 keep */, int fill_percent /* <= 0 keep */, int nseg /* -1 keep, 0 auto */);
-hipError_t pfxk_box_blur(hipStream_t s, const uint8_t* d_src, uint8_t* d_tmp, uint8_t* d_dst, const uint8_t* d_mask,
-                         int radius, uint32_t w, uint32_t h, int force_two_pass /* in-place calls: the fused kernel would race */);
+// ---- k_stencil.hip ---- box blur / median / pixelate.  Which kernel runs is chosen in pfx_stencil.cpp; the launchers take that choice and launch it
+enum { PFX_BOX_TILE = 0 /* both passes on a 64 x 64 tile */, PFX_BOX_STRIP /* fused strip walk */, PFX_BOX_TWO_PASS /* u8 intermediate in d_tmp */,
+       PFX_BOX_SLIDING = 0, PFX_BOX_PREFIX /* h_kind, the horizontal pass of PFX_BOX_TWO_PASS: sliding window | prefix sums */ };
+typedef struct pfx_box_plan { int kind, h_kind, px /* 4 | 8 | 16 columns per lane (sliding) */, py /* 16 | 32 | 64 | 128 rows per lane */; } pfx_box_plan;
+int pfxk_box_tile_max_radius(void), pfxk_box_strip_max_radius(void), pfxk_box_prefix_max_radius(void);   // the compiled limits: tile kernel, strip walk, prefix-sum pass (its LDS footprint)
+hipError_t pfxk_box_blur(hipStream_t s, const uint8_t* d_src, uint8_t* d_tmp, uint8_t* d_dst, const uint8_t* d_mask, int radius, uint32_t w, uint32_t h,
+                         const pfx_box_plan* plan, int strip_fill /* chip fill in % of one round of workgroups */, int strip_nseg /* forced segment count, 0 = auto */);
 #define PFXK_MEDIAN_TILE_MAX_RADIUS 24 /* beyond: sliding histograms */
-hipError_t pfxk_median(hipStream_t s, const uint8_t* d_src, uint8_t* d_dst, const uint8_t* d_mask, int radius,
-                       uint32_t w, uint32_t h);
-// ---- k_median_bits.hip ---- radii 2..7 as a bit-sliced radix select over bit planes of the image (scratch: pfxk_median_bits_scratch bytes)
+enum { PFX_MEDIAN_UNSUPPORTED = -1, PFX_MEDIAN_NET3 = 0, PFX_MEDIAN_XLANE, PFX_MEDIAN_XLANE_ROWS2, PFX_MEDIAN_XLANE7, PFX_MEDIAN_SHARED, PFX_MEDIAN_SINGLE_NET,
+       PFX_MEDIAN_BITS_PAIR, PFX_MEDIAN_BITS, PFX_MEDIAN_SEARCH4, PFX_MEDIAN_SEARCH1, PFX_MEDIAN_HIST };
+hipError_t pfxk_median(hipStream_t s, const uint8_t* d_src, uint8_t* d_dst, const uint8_t* d_mask, int path /* any but the two _BITS */, int radius, uint32_t w, uint32_t h);
+// ---- k_median_bits.hip ---- radii 2..8 as a bit-sliced radix select over bit planes of the image (scratch: pfxk_median_bits_scratch bytes)
 size_t pfxk_median_bits_scratch(int radius, uint32_t w, uint32_t h);
-void pfxk_median_bits_set_pair(int on); // 1 (default): radii 2..7 on the column-pair kernel (two adjacent columns per lane on shared plane registers)
-hipError_t pfxk_median_bits(hipStream_t s, const uint8_t* d_src, uint8_t* d_dst, const uint8_t* d_mask, uint32_t* d_planes, int radius,
-                            uint32_t w, uint32_t h);
+hipError_t pfxk_median_bits(hipStream_t s, const uint8_t* d_src, uint8_t* d_dst, const uint8_t* d_mask, uint32_t* d_planes, int radius, uint32_t w, uint32_t h,
+                            int pair /* radii 2..7: two adjacent columns per lane on shared plane registers (PFX_MEDIAN_BITS_PAIR); 0: one column per lane */);
 hipError_t pfxk_pixelate(hipStream_t s, const uint8_t* d_src, uint8_t* d_dst, const uint8_t* d_mask, uint32_t bs,
                          uint32_t w, uint32_t h);
 

@@ -6,8 +6,11 @@ bit-exact in `exact` mode."""
 import numpy as np
 import pytest
 
+import ctypes
+
 from . import inputs as I
 from . import oracle_lib as O
+from .test_stencil_dispatch_host import MEDIAN, PREFIX, STRIP, TILE, TWO_PASS
 
 pytestmark = pytest.mark.gpu
 
@@ -28,6 +31,21 @@ def assert_same(a, b, tol=0, what=""):
     assert a.shape == b.shape, what
     d = np.abs(a.astype(np.int16) - b.astype(np.int16))
     assert d.max() <= tol, f"{what}: max diff {int(d.max())}, {int((d.max(-1) > tol).sum())} px over tolerance {tol}"
+
+
+def median_path(gpu):
+    """the PFX_MEDIAN_* path of the context's last median (pfx_internal.h: pfx_int_stencil_last_path; the letters: tests/test_stencil_dispatch_host.py)"""
+    f = gpu.r._lib.pfx_int_stencil_last_path
+    f.argtypes, f.restype = [ctypes.c_void_p, ctypes.c_int], ctypes.c_int
+    return f(gpu.r._h, 0)
+
+
+def box_plan(gpu):
+    """(kind, h_kind, columns per lane, rows per lane) of the context's last box blur"""
+    f = gpu.r._lib.pfx_int_stencil_last_path
+    f.argtypes, f.restype = [ctypes.c_void_p, ctypes.c_int], ctypes.c_int
+    v = f(gpu.r._h, 1)
+    return v & 15, (v >> 4) & 15, (v >> 8) & 255, v >> 16
 
 
 def sparse_alpha_image(w, h, seed):
@@ -328,13 +346,16 @@ def test_median_shared_column_networks(gpu, oracle, radius, size):
     mask = (np.random.default_rng(w).random((h, w)) < 0.5).astype(np.uint8)
     ref, ref_m = oracle.median(img, radius), oracle.median(img, radius, mask)
     gpu.r.tune("median_bits_min", 9)  # the network kernels, not the bit-plane select
+    gpu.r.tune("median_xlane", 0)     # ... and radius 2 on the per-lane network this test is about, not the cross-lane one
     try:
         for single in (0, 1):
             gpu.r.tune("median_single", single)
             assert_same(gpu.median(img, radius), ref, 0, f"median r={radius} {w}x{h} single={single}")
+            assert median_path(gpu) == MEDIAN["H" if not single else ("G" if radius < 4 else "4")]
             assert_same(gpu.median(img, radius, mask), ref_m, 0, f"median r={radius} {w}x{h} masked single={single}")
     finally:
         gpu.r.tune("median_single", 0)
+        gpu.r.tune("median_xlane", 1)
         gpu.r.tune("median_bits_min", MEDIAN_BITS_MIN)
 
 
@@ -355,6 +376,7 @@ def test_median_value_search_four_pixels_per_lane(gpu, oracle, radius, size):
         for one in (0, 1):
             gpu.r.tune("median_search1", one)
             assert_same(gpu.median(img, radius), ref, 0, f"median r={radius} {w}x{h} search1={one}")
+            assert median_path(gpu) == MEDIAN["1" if one else "4"]
             assert_same(gpu.median(img, radius, mask), ref_m, 0, f"median r={radius} {w}x{h} masked search1={one}")
     finally:
         gpu.r.tune("median_search1", 0)
@@ -383,6 +405,7 @@ def test_median_bit_plane_radix_select(gpu, oracle, radius, size, pair):
     gpu.r.tune("median_pair", pair)
     try:
         assert_same(gpu.median(img, radius), oracle.median(img, radius), 0, f"median bits r={radius} {w}x{h}")
+        assert median_path(gpu) == MEDIAN["P" if pair else "b"]
         assert_same(gpu.median(img, radius, mask), oracle.median(img, radius, mask), 0, f"median bits r={radius} {w}x{h} masked")
     finally:
         gpu.r.tune("median_bits_min", MEDIAN_BITS_MIN)
@@ -988,12 +1011,14 @@ def test_box_blur_fused_equals_two_pass_and_oracle(gpu, radius, size):
         gpu.r.tune("box_two_pass", 1)
         try:
             two = gpu.box_blur(img, radius, m)
+            assert box_plan(gpu)[0] == TWO_PASS
         finally:
             gpu.r.tune("box_two_pass", 0)
         assert np.array_equal(fused, two)
         gpu.r.tune("box_strip", 1)      # the 64 x 64 tile kernel for r <= 4 (the default since round 5 is the strip walk on every radius)
         try:
             tile = gpu.box_blur(img, radius, m)
+            assert box_plan(gpu)[0] == (TILE if radius <= 4 else STRIP)
         finally:
             gpu.r.tune("box_strip", 2)
         assert np.array_equal(fused, tile)
@@ -1019,9 +1044,11 @@ def test_box_blur_two_pass_lane_runs(gpu, radius, size):
 
 def _two_pass_shapes(gpu, img, ref, radius, size):
     assert_same(gpu.box_blur(img, radius), ref, 0, f"box blur r={radius} {size} (two-pass shapes by radius)")
+    assert box_plan(gpu)[0] == TWO_PASS
     gpu.r.tune("box_prefix_from", 1)   # the prefix-sum horizontal pass (default: radii from 72) on every radius and tile shape
     try:
         assert_same(gpu.box_blur(img, radius), ref, 0, f"box blur r={radius} {size} prefix-sum horizontal pass")
+        assert box_plan(gpu)[:2] == (TWO_PASS, PREFIX)
     finally:
         gpu.r.tune("box_prefix_from", 72)
     for px, py in ((4, 16), (8, 32), (16, 64), (16, 128), (8, 16), (4, 128)):
@@ -1029,6 +1056,7 @@ def _two_pass_shapes(gpu, img, ref, radius, size):
         gpu.r.tune("box_py", py)
         try:
             assert_same(gpu.box_blur(img, radius), ref, 0, f"box blur r={radius} {size} lane runs {px}/{py}")
+            assert box_plan(gpu) == (TWO_PASS, 0, px, py)
         finally:
             gpu.r.tune("box_px", 0)
             gpu.r.tune("box_py", 0)
@@ -1049,6 +1077,7 @@ def test_box_blur_strip_walk(gpu, radius, size):
         for nseg in (0, 1, 2, 7, 40):
             gpu.r.tune("box_strip_nseg", nseg)
             assert_same(gpu.box_blur(img, radius), ref, 0, f"box blur r={radius} {size} strip walk, {nseg or 'auto'} segments")
+            assert box_plan(gpu)[0] == (STRIP if np.ceil(radius) <= gpu.r._lib.pfxk_box_strip_max_radius() else TWO_PASS)   # radius 64 is beyond the walk
         gpu.r.tune("box_strip_nseg", 3)
         assert_same(gpu.box_blur(img, radius, mask), ref_m, 0, f"box blur r={radius} {size} strip walk, masked")
     finally:
@@ -1056,6 +1085,7 @@ def test_box_blur_strip_walk(gpu, radius, size):
     gpu.r.tune("box_strip", 0)
     try:
         assert_same(gpu.box_blur(img, radius), ref, 0, f"box blur r={radius} {size} two-pass")
+        assert box_plan(gpu)[0] == (TILE if radius <= 4 else TWO_PASS)   # box_strip = 0 leaves the small radii on the tile kernel
     finally:
         gpu.r.tune("box_strip", 2)
 
@@ -1135,10 +1165,13 @@ def test_median_5x5_cross_lane_network_matches_the_oracle_and_the_per_lane_netwo
         try:
             r.tune("median_xlane", 1)
             got = gpu.median(img, 2, mask=mask)
+            assert median_path(gpu) == MEDIAN["X"]
             r.tune("median_xlane", 2)          # two rows per lane (rows 1 .. 4 of a column sorted once for both)
             got2 = gpu.median(img, 2, mask=mask)
+            assert median_path(gpu) == MEDIAN["R"]
             r.tune("median_xlane", 0)
             old = gpu.median(img, 2, mask=mask)
+            assert median_path(gpu) == MEDIAN["H"]
         finally:
             r.tune("median_xlane", 1)
         assert np.array_equal(got, want), (w, h, mask is not None, int((got != want).any(-1).sum()))
@@ -1158,6 +1191,7 @@ def test_median_7x7_cross_lane_network_matches_the_oracle(gpu, oracle):
                 img = (img // 64) * 64
             mask = None if (w + h) % 2 else ((rng.random((h, w)) < 0.5).astype(np.uint8) * 255)
             got, want = gpu.median(img, 3, mask=mask), oracle.median(img, 3, mask=mask)
+            assert median_path(gpu) == MEDIAN["7"]
             assert np.array_equal(got, want), (w, h, mask is not None, int((got != want).any(-1).sum()))
     finally:
         r.tune("median_xlane", 1)

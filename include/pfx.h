@@ -802,6 +802,31 @@ int pfx_shape_preview_dev(pfx_ctx* ctx, const pfx_shape* shape, uint32_t canvas_
 int pfx_shape_draw_dev(pfx_ctx* ctx, void* layer_dev, uint32_t canvas_w, uint32_t canvas_h, const pfx_shape* shape, uint8_t blend_mode,
                        const void* selection_dev /* may be NULL */);
 
+/* ================= content-aware fill (ref: src/ops/inpaint.rs) =================
+ * Images are w*h RGBA8, the hole mask is w*h bytes (> 0 = pixel to fill).  Both routines are in the bit-exact class: the reference's two inpaint goldens are
+ * reproduced with tolerance 0.  The one per-pixel transcendental is exp, evaluated as glibc's expf bit for bit; the ring's cos / sin are uniform over the image
+ * and computed on the host.
+ *
+ * Instant heal dabs (inpaint_instant_brush :76-192): each pixel of the mask under a dab becomes the colour-similarity-weighted mean of 32 ring samples of `src`
+ * around it, blended into `out` by the dab's hardness-aware alpha.  A dab list is applied in order, in one launch.  src and the mask are only read; `out` must
+ * not overlap either (PFX_ERR_INVALID).  Non-finite dab fields are refused.  n_dabs == 0 is a no-op (PFX_OK), like the brush calls. */
+typedef struct pfx_inpaint_dab { float cx, cy, brush_radius, sample_radius, hardness; } pfx_inpaint_dab;
+/* the 32 candidate offsets (cos(angle_i) * rr_i, sin(angle_i) * rr_i) of a sample radius, x and y interleaved (:141-147).  Host only; NULL out is a no-op. */
+void pfx_inpaint_ring_offsets(float sample_radius, float out_xy[64]);
+int pfx_inpaint_instant(pfx_ctx* ctx, const uint8_t* src, const uint8_t* hole_mask, uint8_t* out_inout, uint32_t w, uint32_t h, const pfx_inpaint_dab* dabs,
+                        uint32_t n_dabs);
+int pfx_inpaint_instant_dev(pfx_ctx* ctx, const void* src_dev, const void* hole_mask_dev, void* out_dev, uint32_t w, uint32_t h, const pfx_inpaint_dab* dabs,
+                            uint32_t n_dabs);
+/* Onion-peeling PatchMatch (fill_region_patchmatch :394-520), the reference's result bit for bit, its scan orders included: per peel the hole's boundary
+ * pixels get a random-initialised nearest-neighbour field, 2 (iterations <= 3) or 4 propagation / random-search passes, and the colour of their best source.
+ * patch_size: values below 3 count as 3, values above 11 (the tool's range) are refused.  An empty mask or a mask without a non-hole pixel gives a copy of
+ * src.  dst == src (in place) is allowed; any other overlap of dst with src or the mask is refused.  Working memory (about 5 bytes per canvas pixel) is
+ * allocated before dst is touched: PFX_ERR_OOM leaves dst as it was.  The host waits for the device once per peel. */
+int pfx_inpaint_patchmatch(pfx_ctx* ctx, const uint8_t* src, const uint8_t* hole_mask, uint8_t* dst, uint32_t w, uint32_t h, uint32_t patch_size,
+                           uint32_t iterations);
+int pfx_inpaint_patchmatch_dev(pfx_ctx* ctx, const void* src_dev, const void* hole_mask_dev, void* dst_dev, uint32_t w, uint32_t h, uint32_t patch_size,
+                               uint32_t iterations);
+
 #ifdef __cplusplus
 }
 #endif

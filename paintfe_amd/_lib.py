@@ -68,6 +68,10 @@ class Shape(C.Structure):   # pfx_shape
                 ("anti_alias", C.c_uint8), ("_pad", C.c_uint8)]
 
 
+class InpaintDab(C.Structure):   # pfx_inpaint_dab
+    _fields_ = [("cx", C.c_float), ("cy", C.c_float), ("brush_radius", C.c_float), ("sample_radius", C.c_float), ("hardness", C.c_float)]
+
+
 _lib = None
 
 

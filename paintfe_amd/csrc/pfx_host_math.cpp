@@ -316,6 +316,21 @@ void pfx_displacement_brush(float* disp, uint32_t w, uint32_t h, int mode, float
         }
 }
 
+// ref: inpaint_instant_brush's candidate ring, src/ops/inpaint.rs:88-89, :141-147 — uniform over the image, so cos / sin are the host's
+void pfx_inpaint_ring_offsets(float sample_radius, float out_xy[64])
+{
+    if (!out_xy) return;
+    const float inner_r = sample_radius * 0.25f, outer_r = sample_radius;
+    volatile float tau = 6.28318530717958647692f;   // opaque: the angles reach the run-time libm, never a compile-time evaluation of cos / sin
+    const float step = tau / 32.0f;
+    for (int i = 0; i < 32; ++i) {
+        const float angle = (float)i * step;
+        const float rr = inner_r + (outer_r - inner_r) * ((float)i / 31.0f);
+        out_xy[2 * i] = cosf(angle) * rr;
+        out_xy[2 * i + 1] = sinf(angle) * rr;
+    }
+}
+
 } // extern "C"
 
 // ref: rebuild_brush_lut, src/ui/panels/tools/behavior/raster/brush_render.rs:27-50

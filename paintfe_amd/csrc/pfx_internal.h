@@ -89,6 +89,8 @@ struct pfx_ctx {
     // GpuLiquifyPipeline's cached source texture (ref: src/gpu/compute/liquify.rs:166-176); 0 x 0 = none / invalidated
     pfx_devbuf warp_src;
     uint32_t warp_src_w = 0, warp_src_h = 0;
+    pfx_devbuf inpaint_ws;                              // PatchMatch working memory (pfx_inpaint.cpp)
+    uint32_t inpaint_peels = 0, inpaint_launches = 0;   // of the context's last PatchMatch call; pfx_int_inpaint_last reads them, nothing else does
 };
 
 // ---- error plumbing ----
@@ -182,6 +184,9 @@ extern "C" int pfx_int_stencil_last_path(pfx_ctx* ctx, int which);   // for the 
 int pfx_stencil_tune(pfx_ctx* ctx, const char* key, int value);   // pfx_tune's median_* and box_* keys
 int pfx_stencil_median(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, int radius, const void* mask_dev);   // arguments are the caller's to check
 int pfx_stencil_box(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, int radius, const void* mask_dev, void* tmp_dev /* NULL: st_tmp */);
+
+// for the tests and the profile notes, what the context's last pfx_inpaint_patchmatch[_dev] ran: which = 0 peels, 1 kernel launches (not in include/pfx.h)
+extern "C" int pfx_int_inpaint_last(pfx_ctx* ctx, int which);
 
 // blur_with_selection on device-resident images (pfx_api.cpp); mask_host may be NULL (= no selection)
 int pfx_int_blur_with_selection_dev(pfx_ctx* ctx, const void* d_src, void* d_dst, uint32_t w, uint32_t h, float sigma,

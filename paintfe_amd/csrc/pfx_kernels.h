@@ -301,6 +301,27 @@ typedef struct pfxk_shape_params { // passed by value: lands in SGPRs / scalar l
 hipError_t pfxk_shape(hipStream_t s, int form, int sdf, const pfxk_shape_params* P, uint8_t* d_out, const uint8_t* d_selection /* COMMIT only, may be NULL */,
                       uint32_t mode /* COMMIT only: BlendMode::to_u8 */, uint32_t canvas_w, uint32_t canvas_h);
 
+// ---- k_inpaint.hip ---- content-aware fill (inpaint.rs): instant heal dabs :76-192 and the onion-peeling PatchMatch :394-520; host side: pfx_inpaint.cpp
+// a dab as the kernel reads it: r = brush_radius.max(1.0), hard_t = (hardness * 0.9 + 0.1).clamp(0, 1), soft_den = 1.0 - hard_t + 1e-6, the dab's own pixel loop
+// bounds [x0, x1] x [y0, y1] (:93-96; x0 > x1 = none), ring = which 64-float set of d_rings (pfx_inpaint_ring_offsets of its sample radius)
+typedef struct pfxk_inpaint_dab { float cx, cy, r, hard_t, soft_den; uint32_t x0, x1, y0, y1, ring, pad[2]; } pfxk_inpaint_dab;
+hipError_t pfxk_inpaint_instant(hipStream_t s, const uint8_t* d_src, const uint8_t* d_mask, uint8_t* d_out, uint32_t w, uint32_t h, const pfxk_inpaint_dab* d_dabs,
+                                uint32_t n_dabs, const float* d_rings, uint32_t bx0, uint32_t by0, uint32_t bx1, uint32_t by1 /* the boxes' union, inclusive */);
+// PatchMatch geometry: the canvas, the hole's bounding box (the NNF arrays hold (bw + 2) * (bh + 2) entries: the box plus one pixel), half = max(patch, 3) / 2
+// (1..5), min_valid = max((2 half + 1)^2, 4) / 4, max_radius = max(w, h) as f32
+typedef struct pfxk_pm_geom { uint32_t w, h, x0, y0, bw, bh, half, min_valid; float max_radius; } pfxk_pm_geom;
+// d_stats[0..8): ~min x, ~min y, max x, max y of the pixels with mask != 0, then their count (zeroed first)
+hipError_t pfxk_pm_stats(hipStream_t s, const uint8_t* d_mask, uint32_t w, uint32_t h, uint32_t* d_stats);
+// stable row-major compaction over the rectangle of pixel indices y * w + x — kind 0: mask == 0, kind 1: boundary pixels of the hole (a hole pixel with a
+// 4-neighbour outside it).  phase 0: per-1024-element counts into d_counts, scanned in place, *d_total = how many; phase 1: the indices to d_list[0 .. total)
+hipError_t pfxk_pm_compact(hipStream_t s, int kind, const uint8_t* d_mask, uint32_t w, uint32_t h, uint32_t rx0, uint32_t ry0, uint32_t rw, uint32_t rh,
+                           uint32_t* d_counts, uint32_t* d_total, uint32_t* d_list, int phase);
+hipError_t pfxk_pm_nnf_reset(hipStream_t s, const pfxk_pm_geom* g, float* d_nnf_ssd);   // every SSD = f32::MAX
+// one peel over the nb boundary pixels stored at d_sources[src_count .. src_count + nb): bucket by anti-diagonal, random init, pm_iters passes (one workgroup
+// each), fill, clear the live mask.  d_diag_start: bw + bh words, d_cursor: bw + bh - 1, d_diag_list: nb
+hipError_t pfxk_pm_peel(hipStream_t s, const pfxk_pm_geom* g, uint8_t* d_img, uint8_t* d_live, const uint32_t* d_sources, uint32_t src_count, uint32_t nb,
+                        int pm_iters, int32_t* d_nnf_ox, int32_t* d_nnf_oy, float* d_nnf_ssd, uint32_t* d_diag_start, uint32_t* d_cursor, uint32_t* d_diag_list);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,22 @@ def shape_bounds(shape: Shape, canvas_w: int, canvas_h: int):
     return tuple(int(v) for v in box)
 
 
+def inpaint_ring_offsets(sample_radius: float) -> np.ndarray:
+    """the instant heal brush's 32 candidate offsets as 64 f32, x and y interleaved (inpaint.rs:141-147).  Host only."""
+    out = np.zeros(64, np.float32)
+    fn = _lib.load().pfx_inpaint_ring_offsets
+    fn.restype = None
+    fn(C.c_float(sample_radius), out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def _dab_array(dabs):
+    rows = [tuple(float(v) for v in d) for d in dabs]
+    if any(len(r) != 5 for r in rows):
+        raise ValueError("a dab is (cx, cy, brush_radius, sample_radius, hardness)")
+    return (_lib.InpaintDab * max(len(rows), 1))(*[_lib.InpaintDab(*r) for r in rows]), len(rows)
+
+
 def script_check(source: str, w: int = 64, h: int = 64):
     """Language-only evaluation of a script (no device, no image functions; ref: compile_script, scripting.rs:1489): returns
     the console lines or raises PfxError with .line / .col."""
@@ -575,6 +591,35 @@ class GpuRenderer:
 
     def rasterize_shape_dev(self, shape: Shape, w: int, h: int, box_ptr: int):
         self._check(self._lib.pfx_shape_rasterize_dev(self._h, C.byref(shape.to_c()), C.c_uint32(w), C.c_uint32(h), C.c_void_p(box_ptr)))
+
+    # ------------------------------------------------------------------ content-aware fill (ref: src/ops/inpaint.rs)
+    inpaint_ring_offsets = staticmethod(inpaint_ring_offsets)
+
+    def inpaint_instant(self, src, mask, out, dabs):
+        """inpaint_instant_brush for every dab (cx, cy, brush_radius, sample_radius, hardness) of the list in order, on a copy of `out`"""
+        s, m, o = _u8(src), _u8(mask), _u8(out).copy()
+        h, w = m.shape[:2]
+        arr, n = _dab_array(dabs)
+        self._check(self._lib.pfx_inpaint_instant(self._h, _p(s), _p(m), _p(o), C.c_uint32(w), C.c_uint32(h), arr, C.c_uint32(n)))
+        return o
+
+    def inpaint_instant_dev(self, src_ptr: int, mask_ptr: int, out_ptr: int, w: int, h: int, dabs):
+        arr, n = _dab_array(dabs)
+        self._check(self._lib.pfx_inpaint_instant_dev(self._h, C.c_void_p(src_ptr), C.c_void_p(mask_ptr), C.c_void_p(out_ptr), C.c_uint32(w), C.c_uint32(h), arr,
+                                                      C.c_uint32(n)))
+
+    def inpaint_patchmatch(self, src, mask, patch_size: int = 5, iterations: int = 3):
+        """fill_region_patchmatch: the filled image"""
+        s, m = _u8(src), _u8(mask)
+        h, w = m.shape[:2]
+        dst = np.empty_like(s)
+        self._check(self._lib.pfx_inpaint_patchmatch(self._h, _p(s), _p(m), _p(dst), C.c_uint32(w), C.c_uint32(h), C.c_uint32(patch_size), C.c_uint32(iterations)))
+        return dst
+
+    def inpaint_patchmatch_dev(self, src_ptr: int, mask_ptr: int, dst_ptr: int, w: int, h: int, patch_size: int = 5, iterations: int = 3):
+        """dst_ptr == src_ptr fills in place"""
+        self._check(self._lib.pfx_inpaint_patchmatch_dev(self._h, C.c_void_p(src_ptr), C.c_void_p(mask_ptr), C.c_void_p(dst_ptr), C.c_uint32(w), C.c_uint32(h),
+                                                         C.c_uint32(patch_size), C.c_uint32(iterations)))
 
     # ------------------------------------------------------------------ script front-end
     def resize_image(self, img, new_w: int, new_h: int, filter="bilinear"):   # transform.rs:347 (imageops::resize)

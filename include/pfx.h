@@ -827,6 +827,56 @@ int pfx_inpaint_patchmatch(pfx_ctx* ctx, const uint8_t* src, const uint8_t* hole
 int pfx_inpaint_patchmatch_dev(pfx_ctx* ctx, const void* src_dev, const void* hole_mask_dev, void* dst_dev, uint32_t w, uint32_t h, uint32_t patch_size,
                                uint32_t iterations);
 
+/* ================= bucket fill and magic wand: flood distance maps (ref: src/ui/panels/tools/behavior/raster/fill_magic.rs, tools/state.rs:574-735) =================
+ * The CPU flavour of the two tools, bit for bit (the reference's WGSL variants — 5-step AA band, pow 2.2, boundary softening — are not implemented).
+ * Images are w*h RGBA8; distance maps, masks and selections are w*h bytes.  Everything is in the bit-exact class.
+ *
+ * Per-pixel colour distance to `target` (pixel_color_distance :1048): legacy = 0 when both alphas are 0, else the largest channel difference; perceptual
+ * (perceptual_distance :93, srgb_to_linear :84) = the reference's f32 expression in its association order — the 256 powf values come from the host libm.
+ * Distance map: global scope = that distance per pixel (compute_global_distance_map :1024); contiguous scope = the bottleneck distance from the seed
+ * (compute_flood_distance_map :950): d[seed] = c[seed], elsewhere the minimum over 4- or 8-connected paths of the largest c on the path; a pixel no path
+ * reaches keeps 255.  The map is unique, whatever algorithm computes it.
+ * Refused with PFX_ERR_INVALID: a seed outside the image (the reference ignores the click, perform_flood_fill :1242), connectivity other than 4 or 8,
+ * distance_mode or global above 1, combine_mode above 3, blend_mode above 24, a distance map that overlaps an output, an RGBA8 device pointer (src_dev,
+ * canvas_out_dev, layer_dev) that is not 4-byte aligned.  Outputs are untouched on any error: every refusal comes before the first launch, and the connected
+ * flood runs in working memory and copies the map out last (the global scope writes dist_dev directly; past the checks only its launch could fail). */
+typedef struct pfx_flood {
+    uint32_t seed_x, seed_y;
+    uint8_t  target[4];
+    uint8_t  distance_mode;  /* 0 LegacyRgba, 1 Perceptual (WandDistanceMode) */
+    uint8_t  connectivity;   /* 4 or 8 (FloodConnectivity) */
+    uint8_t  global;         /* 0 contiguous, 1 global scope */
+    uint8_t  _pad;
+} pfx_flood;
+/* tolerance_threshold_u8 (:78): round(clamp(tolerance / 100, 0, 1) * 255); NaN gives 0.  Host only, no context. */
+uint8_t pfx_tolerance_threshold(float tolerance);
+int pfx_flood_distance(pfx_ctx* ctx, const uint8_t* src, uint32_t w, uint32_t h, const pfx_flood* flood, uint8_t* dist);
+int pfx_flood_distance_dev(pfx_ctx* ctx, const void* src_dev, uint32_t w, uint32_t h, const pfx_flood* flood, void* dist_dev);
+/* ThresholdRegionIndex::from_distances' cumulative boxes (state.rs:693, threshold_bbox :732): for every t in 0..255 the inclusive box x0, y0, x1, y1 of
+ * {d <= t} at boxes[4 t ..], or -1, -1, -1, -1 when the set is empty.  `boxes` is host memory; the call waits for the device. */
+int pfx_flood_bboxes_dev(pfx_ctx* ctx, const void* dist_dev, uint32_t w, uint32_t h, int32_t boxes[1024]);
+/* threshold_alpha (:415) then merge_magic_wand_masks (:486): raw = 255 where d <= threshold, with anti_aliased 128 where d == sat_add(threshold, 1), else 0;
+ * combine_mode 0 replace = raw, 1 add = max(base, raw), 2 subtract = sat(base - raw), 3 intersect = base * raw / 255.  base_mask NULL = all zero
+ * (replay_magic_wand_selection :495).  mask_out == base_mask (in place) is allowed; any other overlap is refused. */
+int pfx_wand_mask(pfx_ctx* ctx, const uint8_t* dist, const uint8_t* base_mask /* may be NULL */, uint32_t w, uint32_t h, uint8_t threshold, uint8_t anti_aliased,
+                  uint8_t combine_mode, uint8_t* mask_out);
+int pfx_wand_mask_dev(pfx_ctx* ctx, const void* dist_dev, const void* base_mask_dev /* may be NULL */, uint32_t w, uint32_t h, uint8_t threshold,
+                      uint8_t anti_aliased, uint8_t combine_mode, void* mask_out_dev);
+/* the fill tool's preview layer over the whole canvas (build_fill_preview_region :550; the fill mask is the threshold mask without the AA band, :775):
+ * fill.rgb with alpha (fill.a * 255 + 127) / 255 where d <= threshold and the selection (NULL = none) is > 0, else 0, 0, 0, 0 — the form
+ * pfx_composite_preview takes.  Every byte of canvas_out (w*h*4) is written. */
+int pfx_fill_preview(pfx_ctx* ctx, const uint8_t* dist, const uint8_t* selection /* may be NULL */, uint32_t w, uint32_t h, uint8_t threshold, const uint8_t fill[4],
+                     uint8_t* canvas_out);
+int pfx_fill_preview_dev(pfx_ctx* ctx, const void* dist_dev, const void* selection_dev /* may be NULL */, uint32_t w, uint32_t h, uint8_t threshold,
+                         const uint8_t fill[4], void* canvas_out_dev);
+/* preview and commit in one kernel (commit_fill_preview_impl :1414-1446): equals pfx_fill_preview followed by pfx_brush_commit with is_eraser = 0 */
+int pfx_fill_commit_dev(pfx_ctx* ctx, void* layer_dev, const void* dist_dev, const void* selection_dev /* may be NULL */, uint32_t w, uint32_t h, uint8_t threshold,
+                        const uint8_t fill[4], uint8_t blend_mode);
+/* the bucket tool (perform_flood_fill :1231-1273): target = the layer pixel at the seed, LegacyRgba, 4-connected, global_fill != 0 = global scope,
+ * threshold = pfx_tolerance_threshold(tolerance); `fill` is the tool's colour as bytes ((c * 255) as u8, truncating) */
+int pfx_bucket_fill(pfx_ctx* ctx, uint8_t* layer_inout, uint32_t w, uint32_t h, uint32_t seed_x, uint32_t seed_y, float tolerance, const uint8_t fill[4],
+                    uint8_t blend_mode, int global_fill, const uint8_t* selection /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,11 @@ class InpaintDab(C.Structure):   # pfx_inpaint_dab
     _fields_ = [("cx", C.c_float), ("cy", C.c_float), ("brush_radius", C.c_float), ("sample_radius", C.c_float), ("hardness", C.c_float)]
 
 
+class Flood(C.Structure):   # pfx_flood
+    _fields_ = [("seed_x", C.c_uint32), ("seed_y", C.c_uint32), ("target", C.c_uint8 * 4), ("distance_mode", C.c_uint8), ("connectivity", C.c_uint8),
+                ("global_", C.c_uint8), ("_pad", C.c_uint8)]
+
+
 _lib = None
 
 
@@ -90,5 +95,7 @@ def load() -> C.CDLL:
     lib.pfx_ctx_stream.argtypes = [C.c_void_p]
     lib.pfx_layer_memory.restype = C.c_size_t
     lib.pfx_layer_count.restype = C.c_uint32
+    lib.pfx_tolerance_threshold.restype = C.c_uint8
+    lib.pfx_tolerance_threshold.argtypes = [C.c_float]
     _lib = lib
     return lib

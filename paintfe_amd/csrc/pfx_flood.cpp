@@ -1,0 +1,284 @@
+// pfx_flood.cpp — C ABI of the bucket fill and the magic wand (k_flood.hip).  Reference: src/ui/panels/tools/behavior/raster/fill_magic.rs —
+// tolerance_threshold_u8 :78, srgb_to_linear :84, compute_flood_distance_map :950, perform_flood_fill :1231; tools/state.rs:693 from_distances.
+// The host computes what is uniform over the image with the reference's own f32 expressions (no contraction): the 256-entry srgb_to_linear table (host powf,
+// uploaded once per context) and the target's linear terms.  For the contiguous scope it runs the pass loop: one 8-byte read-back per pass (how many tiles
+// the next pass visits, whether a byte decreased) ends it, as does the cap of w * h + 2 passes (DESIGN.md "Flood distance maps": an optimal path has at most
+// w * h pixels and every pass settles the next one).  The flood runs in working memory: a failed call leaves `dist` untouched.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+
+#include "pfx_internal.h"
+
+namespace {
+
+inline size_t align256(size_t n) { return (n + 255u) & ~(size_t)255u; }
+inline uint32_t pack4(const uint8_t c[4]) { return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24); }
+
+float srgb_to_linear(float v) { return v <= 0.04045f ? v / 12.92f : powf((v + 0.055f) / 1.055f, 2.4f); }   // :84
+
+int check_flood(pfx_ctx* ctx, const void* src, uint32_t w, uint32_t h, const pfx_flood* f, const void* dist, bool dev, const char* who)
+{
+    if (!ctx) return PFX_ERR_INVALID;
+    if (!pfx_dims_ok(w, h)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: bad image size %ux%u", who, w, h);
+    if (!src || !dist || !f) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: null pointer", who);
+    if (f->connectivity != 4 && f->connectivity != 8) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: connectivity %u (4 or 8)", who, f->connectivity);
+    if (f->distance_mode > 1 || f->global > 1) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: unknown distance mode %u or scope %u", who, f->distance_mode, f->global);
+    if (f->seed_x >= w || f->seed_y >= h) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: seed (%u, %u) outside the %ux%u image", who, f->seed_x, f->seed_y, w, h);
+    const size_t px = (size_t)w * h;
+    if (pfx_ranges_overlap(dist, px, src, px * 4)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: dist overlaps src", who);
+    if (dev && ((uintptr_t)src & 3u)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: src_dev is not 4-byte aligned", who);   // the kernels read a pixel as one dword
+    return pfx_use(ctx);
+}
+
+// the threshold kernels' shared checks: `out` of out_bytes must not overlap the distance map, nor `other` (the base mask / the selection, may be NULL)
+// unless same_ok and the two are the same buffer
+int check_threshold_call(pfx_ctx* ctx, const void* dist, const void* other, const void* out, size_t out_bytes, bool same_ok, uint32_t w, uint32_t h, const char* who)
+{
+    if (!ctx) return PFX_ERR_INVALID;
+    if (!pfx_dims_ok(w, h)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: bad image size %ux%u", who, w, h);
+    if (!dist || !out) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: null pointer", who);
+    const size_t px = (size_t)w * h;
+    if (pfx_ranges_overlap(out, out_bytes, dist, px)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: the distance map overlaps the output", who);
+    if (other && !(same_ok && other == out) && pfx_ranges_overlap(out, out_bytes, other, px))
+        return pfx_fail(ctx, PFX_ERR_INVALID, "%s: the output overlaps the %s", who, same_ok ? "base mask (other than in place)" : "selection");
+    return pfx_use(ctx);
+}
+
+int flood_table(pfx_ctx* ctx)
+{
+    if (ctx->flood_lut_valid) return PFX_OK;
+    float lin[256];
+    for (int k = 0; k < 256; ++k) lin[k] = srgb_to_linear((float)k / 255.0f);
+    PFX_TRY(pfx_reserve(ctx, ctx->flood_lut, sizeof lin));
+    PFX_TRY(pfx_h2d(ctx, ctx->flood_lut.p, lin, sizeof lin));
+    PFX_TRY(pfx_sync(ctx));   // `lin` is pageable host memory about to go out of scope
+    ctx->flood_lut_valid = true;
+    return PFX_OK;
+}
+
+pfxk_flood_target make_target(const pfx_flood* f)
+{
+    pfxk_flood_target G;
+    G.rgba = pack4(f->target);
+    G.ta = (float)f->target[3] / 255.0f;
+    for (int k = 0; k < 3; ++k) G.lin[k] = srgb_to_linear((float)f->target[k] / 255.0f) * G.ta;   // :112-114
+    return G;
+}
+
+inline int sat_int(uint64_t v) { return v > (uint64_t)INT_MAX ? INT_MAX : (int)v; }
+
+} // namespace
+
+extern "C" {
+
+uint8_t pfx_tolerance_threshold(float tolerance)
+{
+    float n = tolerance / 100.0f;
+    n = n < 0.0f ? 0.0f : (n > 1.0f ? 1.0f : n);   // f32::clamp: a NaN stays a NaN
+    const float r = roundf(n * 255.0f);
+    return !(r > 0.0f) ? 0 : (r >= 255.0f ? 255 : (uint8_t)r);   // .clamp(0.0, 255.0) as u8: NaN -> 0
+}
+
+int pfx_flood_distance_dev(pfx_ctx* ctx, const void* src_dev, uint32_t w, uint32_t h, const pfx_flood* flood, void* dist_dev)
+{
+    PFX_TRY(check_flood(ctx, src_dev, w, h, flood, dist_dev, true, "pfx_flood_distance_dev"));
+    const size_t px = (size_t)w * h;
+    ctx->flood_passes = ctx->flood_launches = ctx->flood_visits = 0;
+    if (flood->distance_mode == 1) PFX_TRY(flood_table(ctx));
+    const pfxk_flood_target G = make_target(flood);
+    const float* table = flood->distance_mode == 1 ? (const float*)ctx->flood_lut.p : nullptr;
+    if (flood->global) {   // compute_global_distance_map :1024, written straight into dist_dev: past the checks above only the launch itself can fail
+        pfx_timer t(ctx, "flood_distance_global");
+        PFX_HIP(ctx, pfxk_color_distance(ctx->stream, (const uint8_t*)src_dev, (uint8_t*)dist_dev, px, flood->distance_mode, &G, table));
+        ctx->flood_launches = 1;
+        return PFX_OK;
+    }
+    // working memory, one block: 256 bytes of state (two {list length, changed} pairs, one per list) | c | d | two tile lists | the tiles' pass stamps
+    const uint32_t T = PFXK_FLOOD_TILE;
+    const size_t tiles = (size_t)((w + T - 1) / T) * ((h + T - 1) / T);
+    const size_t off_c = 256, off_d = off_c + align256(px), off_l0 = off_d + align256(px), off_l1 = off_l0 + align256(tiles * 4),
+                 off_mark = off_l1 + align256(tiles * 4), total = off_mark + align256(tiles * 4);
+    PFX_TRY(pfx_reserve(ctx, ctx->flood_ws, total));   // a failure leaves dist untouched
+    uint8_t* ws = (uint8_t*)ctx->flood_ws.p;
+    uint32_t* state = (uint32_t*)ws;
+    uint8_t *c = ws + off_c, *d = ws + off_d;
+    uint32_t* lists[2] = {(uint32_t*)(ws + off_l0), (uint32_t*)(ws + off_l1)};
+    uint32_t* mark = (uint32_t*)(ws + off_mark);
+    pfx_timer t(ctx, "flood_distance");
+    PFX_HIP(ctx, pfxk_color_distance(ctx->stream, (const uint8_t*)src_dev, c, px, flood->distance_mode, &G, table));
+    PFX_HIP(ctx, hipMemsetAsync(d, 0xff, px, ctx->stream));
+    PFX_HIP(ctx, hipMemsetAsync(mark, 0, tiles * 4, ctx->stream));
+    PFX_HIP(ctx, pfxk_flood_seed(ctx->stream, w, flood->seed_x, flood->seed_y, lists[0]));
+    ctx->flood_launches = 2;
+    // Every pass but the last lowers a byte, and after pass k the first k pixels of every optimal path hold their final value (the first pass plants the seed):
+    // at most w * h + 1 passes change something.  The cap can only be met by a defect.
+    const uint64_t max_passes = (uint64_t)px + 2u;
+    uint32_t n_cur = 1;
+    for (uint64_t pass = 0;; ++pass) {
+        if (pass >= max_passes) return pfx_fail(ctx, PFX_ERR_HIP, "pfx_flood_distance_dev: internal error: no fixed point after %llu passes", (unsigned long long)pass);
+        uint32_t* st = state + 2 * ((pass + 1) & 1);
+        uint32_t got[2] = {0, 0};
+        PFX_HIP(ctx, hipMemsetAsync(st, 0, 8, ctx->stream));
+        PFX_HIP(ctx, pfxk_flood_pass(ctx->stream, flood->connectivity, c, d, w, h, lists[pass & 1], n_cur, lists[(pass + 1) & 1], st, mark, (uint32_t)(pass + 1),
+                                     pass == 0 ? flood->seed_x : 0xffffffffu, pass == 0 ? flood->seed_y : 0xffffffffu));
+        PFX_TRY(pfx_d2h(ctx, got, st, sizeof got));
+        PFX_TRY(pfx_sync(ctx));
+        ctx->flood_passes += 1;
+        ctx->flood_launches += 1;
+        ctx->flood_visits += n_cur;
+        if ((size_t)got[0] > tiles) return pfx_fail(ctx, PFX_ERR_HIP, "pfx_flood_distance_dev: internal error: tile list overruns the tile count");   // cannot happen: a tile is listed once per pass
+        n_cur = got[0];
+        if (n_cur == 0 || got[1] == 0) break;   // nothing scheduled / a pass that wrote nothing
+    }
+    PFX_HIP(ctx, hipMemcpyAsync(dist_dev, d, px, hipMemcpyDeviceToDevice, ctx->stream));
+    return PFX_OK;
+}
+
+int pfx_flood_distance(pfx_ctx* ctx, const uint8_t* src, uint32_t w, uint32_t h, const pfx_flood* flood, uint8_t* dist)
+{
+    PFX_TRY(check_flood(ctx, src, w, h, flood, dist, false, "pfx_flood_distance"));
+    const size_t px = (size_t)w * h;
+    PFX_TRY(pfx_reserve(ctx, ctx->st_in, px * 4));
+    PFX_TRY(pfx_reserve(ctx, ctx->st_mask, px));
+    PFX_TRY(pfx_h2d(ctx, ctx->st_in.p, src, px * 4));
+    PFX_TRY(pfx_flood_distance_dev(ctx, ctx->st_in.p, w, h, flood, ctx->st_mask.p));
+    PFX_TRY(pfx_d2h(ctx, dist, ctx->st_mask.p, px));
+    return pfx_sync(ctx);
+}
+
+int pfx_flood_bboxes_dev(pfx_ctx* ctx, const void* dist_dev, uint32_t w, uint32_t h, int32_t boxes[1024])
+{
+    if (!ctx) return PFX_ERR_INVALID;
+    if (!pfx_dims_ok(w, h)) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_flood_bboxes_dev: bad image size %ux%u", w, h);
+    if (!dist_dev || !boxes) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_flood_bboxes_dev: null pointer");
+    PFX_TRY(pfx_use(ctx));
+    PFX_TRY(pfx_reserve(ctx, ctx->d_misc, 4096));
+    uint32_t per[1024];
+    {
+        pfx_timer t(ctx, "flood_bboxes");
+        PFX_HIP(ctx, hipMemsetAsync(ctx->d_misc.p, 0, 4096, ctx->stream));
+        PFX_HIP(ctx, pfxk_flood_bboxes(ctx->stream, (const uint8_t*)dist_dev, w, h, (uint32_t*)ctx->d_misc.p));
+    }
+    PFX_TRY(pfx_d2h(ctx, per, ctx->d_misc.p, sizeof per));
+    PFX_TRY(pfx_sync(ctx));
+    bool any = false;   // the prefix over t (state.rs:709-721)
+    uint32_t x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+    for (int t = 0; t < 256; ++t) {
+        if (per[t * 4] != 0u) {
+            const uint32_t bx0 = ~per[t * 4], by0 = ~per[t * 4 + 1], bx1 = per[t * 4 + 2], by1 = per[t * 4 + 3];
+            if (!any) { x0 = bx0; y0 = by0; x1 = bx1; y1 = by1; any = true; }
+            else { x0 = std::min(x0, bx0); y0 = std::min(y0, by0); x1 = std::max(x1, bx1); y1 = std::max(y1, by1); }
+        }
+        boxes[t * 4] = any ? (int32_t)x0 : -1; boxes[t * 4 + 1] = any ? (int32_t)y0 : -1;
+        boxes[t * 4 + 2] = any ? (int32_t)x1 : -1; boxes[t * 4 + 3] = any ? (int32_t)y1 : -1;
+    }
+    return PFX_OK;
+}
+
+int pfx_wand_mask_dev(pfx_ctx* ctx, const void* dist_dev, const void* base_mask_dev, uint32_t w, uint32_t h, uint8_t threshold, uint8_t anti_aliased,
+                      uint8_t combine_mode, void* mask_out_dev)
+{
+    const size_t px = (size_t)w * h;
+    PFX_TRY(check_threshold_call(ctx, dist_dev, base_mask_dev, mask_out_dev, px, true, w, h, "pfx_wand_mask_dev"));
+    if (combine_mode > 3) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_wand_mask_dev: unknown combine mode %u", combine_mode);
+    pfx_timer t(ctx, "wand_mask");
+    PFX_HIP(ctx, pfxk_wand_mask(ctx->stream, (const uint8_t*)dist_dev, (const uint8_t*)base_mask_dev, (uint8_t*)mask_out_dev, px, threshold, anti_aliased != 0, combine_mode));
+    return PFX_OK;
+}
+
+int pfx_wand_mask(pfx_ctx* ctx, const uint8_t* dist, const uint8_t* base_mask, uint32_t w, uint32_t h, uint8_t threshold, uint8_t anti_aliased, uint8_t combine_mode,
+                  uint8_t* mask_out)
+{
+    const size_t px = (size_t)w * h;
+    PFX_TRY(check_threshold_call(ctx, dist, base_mask, mask_out, px, true, w, h, "pfx_wand_mask"));
+    if (combine_mode > 3) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_wand_mask: unknown combine mode %u", combine_mode);
+    PFX_TRY(pfx_reserve(ctx, ctx->st_tmp, px));
+    PFX_TRY(pfx_reserve(ctx, ctx->st_mask, px));
+    PFX_TRY(pfx_h2d(ctx, ctx->st_tmp.p, dist, px));
+    if (base_mask) PFX_TRY(pfx_h2d(ctx, ctx->st_mask.p, base_mask, px));
+    PFX_TRY(pfx_wand_mask_dev(ctx, ctx->st_tmp.p, base_mask ? ctx->st_mask.p : nullptr, w, h, threshold, anti_aliased, combine_mode, ctx->st_mask.p));   // in place
+    PFX_TRY(pfx_d2h(ctx, mask_out, ctx->st_mask.p, px));
+    return pfx_sync(ctx);
+}
+
+int pfx_fill_preview_dev(pfx_ctx* ctx, const void* dist_dev, const void* selection_dev, uint32_t w, uint32_t h, uint8_t threshold, const uint8_t fill[4],
+                         void* canvas_out_dev)
+{
+    const size_t px = (size_t)w * h;
+    PFX_TRY(check_threshold_call(ctx, dist_dev, selection_dev, canvas_out_dev, px * 4, false, w, h, "pfx_fill_preview_dev"));
+    if (!fill) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_fill_preview_dev: null fill colour");
+    if ((uintptr_t)canvas_out_dev & 3u) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_fill_preview_dev: canvas_out_dev is not 4-byte aligned");
+    pfx_timer t(ctx, "fill_preview");
+    PFX_HIP(ctx, pfxk_fill_preview(ctx->stream, (const uint8_t*)dist_dev, (const uint8_t*)selection_dev, (uint8_t*)canvas_out_dev, px, threshold, pack4(fill)));
+    return PFX_OK;
+}
+
+int pfx_fill_preview(pfx_ctx* ctx, const uint8_t* dist, const uint8_t* selection, uint32_t w, uint32_t h, uint8_t threshold, const uint8_t fill[4],
+                     uint8_t* canvas_out)
+{
+    const size_t px = (size_t)w * h;
+    PFX_TRY(check_threshold_call(ctx, dist, selection, canvas_out, px * 4, false, w, h, "pfx_fill_preview"));
+    if (!fill) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_fill_preview: null fill colour");
+    PFX_TRY(pfx_reserve(ctx, ctx->st_tmp, px));
+    PFX_TRY(pfx_reserve(ctx, ctx->st_mask, px));
+    PFX_TRY(pfx_reserve(ctx, ctx->st_out, px * 4));
+    PFX_TRY(pfx_h2d(ctx, ctx->st_tmp.p, dist, px));
+    if (selection) PFX_TRY(pfx_h2d(ctx, ctx->st_mask.p, selection, px));
+    PFX_TRY(pfx_fill_preview_dev(ctx, ctx->st_tmp.p, selection ? ctx->st_mask.p : nullptr, w, h, threshold, fill, ctx->st_out.p));
+    PFX_TRY(pfx_d2h(ctx, canvas_out, ctx->st_out.p, px * 4));
+    return pfx_sync(ctx);
+}
+
+int pfx_fill_commit_dev(pfx_ctx* ctx, void* layer_dev, const void* dist_dev, const void* selection_dev, uint32_t w, uint32_t h, uint8_t threshold,
+                        const uint8_t fill[4], uint8_t blend_mode)
+{
+    const size_t px = (size_t)w * h;
+    PFX_TRY(check_threshold_call(ctx, dist_dev, selection_dev, layer_dev, px * 4, false, w, h, "pfx_fill_commit_dev"));
+    if (!fill) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_fill_commit_dev: null fill colour");
+    if ((uintptr_t)layer_dev & 3u) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_fill_commit_dev: layer_dev is not 4-byte aligned");
+    if (blend_mode > 24) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_fill_commit_dev: unknown blend mode %u", blend_mode);
+    pfx_timer t(ctx, "fill_commit");
+    PFX_HIP(ctx, pfxk_fill_commit(ctx->stream, (uint8_t*)layer_dev, (const uint8_t*)dist_dev, (const uint8_t*)selection_dev, px, threshold, pack4(fill), blend_mode));
+    return PFX_OK;
+}
+
+int pfx_bucket_fill(pfx_ctx* ctx, uint8_t* layer_inout, uint32_t w, uint32_t h, uint32_t seed_x, uint32_t seed_y, float tolerance, const uint8_t fill[4],
+                    uint8_t blend_mode, int global_fill, const uint8_t* selection)
+{
+    if (!ctx) return PFX_ERR_INVALID;
+    if (!pfx_dims_ok(w, h)) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_bucket_fill: bad image size %ux%u", w, h);
+    if (!layer_inout || !fill) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_bucket_fill: null pointer");
+    if (seed_x >= w || seed_y >= h) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_bucket_fill: seed (%u, %u) outside the %ux%u image", seed_x, seed_y, w, h);
+    if (blend_mode > 24) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_bucket_fill: unknown blend mode %u", blend_mode);
+    const size_t px = (size_t)w * h;
+    if (selection && pfx_ranges_overlap(layer_inout, px * 4, selection, px)) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_bucket_fill: the layer overlaps the selection");
+    PFX_TRY(pfx_use(ctx));
+    pfx_flood f{};
+    f.seed_x = seed_x; f.seed_y = seed_y;
+    memcpy(f.target, layer_inout + ((size_t)seed_y * w + seed_x) * 4, 4);   // :1252
+    f.distance_mode = 0; f.connectivity = 4; f.global = global_fill ? 1 : 0;   // :1272-1273
+    PFX_TRY(pfx_reserve(ctx, ctx->st_in, px * 4));
+    PFX_TRY(pfx_reserve(ctx, ctx->st_tmp, px));
+    PFX_TRY(pfx_reserve(ctx, ctx->st_mask, px));
+    PFX_TRY(pfx_h2d(ctx, ctx->st_in.p, layer_inout, px * 4));
+    if (selection) PFX_TRY(pfx_h2d(ctx, ctx->st_mask.p, selection, px));
+    PFX_TRY(pfx_flood_distance_dev(ctx, ctx->st_in.p, w, h, &f, ctx->st_tmp.p));
+    PFX_TRY(pfx_fill_commit_dev(ctx, ctx->st_in.p, ctx->st_tmp.p, selection ? ctx->st_mask.p : nullptr, w, h, pfx_tolerance_threshold(tolerance), fill, blend_mode));
+    PFX_TRY(pfx_d2h(ctx, layer_inout, ctx->st_in.p, px * 4));
+    return pfx_sync(ctx);
+}
+
+int pfx_int_flood_last(pfx_ctx* ctx, int which)
+{
+    if (!ctx) return -1;
+    switch (which) {
+        case 0: return sat_int(ctx->flood_passes);
+        case 1: return sat_int(ctx->flood_launches);
+        case 2: return PFXK_FLOOD_TILE;
+        case 3: return sat_int(ctx->flood_visits);
+        default: return -1;
+    }
+}
+
+} // extern "C"

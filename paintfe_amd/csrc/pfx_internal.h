@@ -91,6 +91,9 @@ struct pfx_ctx {
     uint32_t warp_src_w = 0, warp_src_h = 0;
     pfx_devbuf inpaint_ws;                              // PatchMatch working memory (pfx_inpaint.cpp)
     uint32_t inpaint_peels = 0, inpaint_launches = 0;   // of the context's last PatchMatch call; pfx_int_inpaint_last reads them, nothing else does
+    pfx_devbuf flood_ws, flood_lut;                     // flood working memory; the 256-entry srgb_to_linear table, uploaded once (pfx_flood.cpp)
+    bool flood_lut_valid = false;
+    uint64_t flood_passes = 0, flood_launches = 0, flood_visits = 0;   // of the context's last pfx_flood_distance[_dev]; pfx_int_flood_last reads them
 };
 
 // ---- error plumbing ----
@@ -187,6 +190,10 @@ int pfx_stencil_box(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w
 
 // for the tests and the profile notes, what the context's last pfx_inpaint_patchmatch[_dev] ran: which = 0 peels, 1 kernel launches (not in include/pfx.h)
 extern "C" int pfx_int_inpaint_last(pfx_ctx* ctx, int which);
+
+// for the tests and the profile notes, what the context's last pfx_flood_distance[_dev] ran: which = 0 passes, 1 kernel launches, 2 the tile edge,
+// 3 tile visits (the lengths of the passes' tile lists, summed); -1 = unknown `which` or NULL context, counts saturate at INT_MAX (not in include/pfx.h)
+extern "C" int pfx_int_flood_last(pfx_ctx* ctx, int which);
 
 // blur_with_selection on device-resident images (pfx_api.cpp); mask_host may be NULL (= no selection)
 int pfx_int_blur_with_selection_dev(pfx_ctx* ctx, const void* d_src, void* d_dst, uint32_t w, uint32_t h, float sigma,

@@ -322,6 +322,28 @@ hipError_t pfxk_pm_nnf_reset(hipStream_t s, const pfxk_pm_geom* g, float* d_nnf_
 hipError_t pfxk_pm_peel(hipStream_t s, const pfxk_pm_geom* g, uint8_t* d_img, uint8_t* d_live, const uint32_t* d_sources, uint32_t src_count, uint32_t nb,
                         int pm_iters, int32_t* d_nnf_ox, int32_t* d_nnf_oy, float* d_nnf_ssd, uint32_t* d_diag_start, uint32_t* d_cursor, uint32_t* d_diag_list);
 
+// ---- k_flood.hip ---- bucket fill / magic wand (fill_magic.rs): colour distance, tile-converging minimax flood, threshold masks, bounding boxes; host side: pfx_flood.cpp
+#define PFXK_FLOOD_TILE 64          // a workgroup's tile edge
+#define PFXK_FLOOD_TILE_ITERS 64    // cap on a tile's sweep rounds per visit; a tile that reaches it schedules itself again
+// what is uniform over the image in a colour distance: the target's bytes and, for the perceptual mode, its premultiplied linear rgb and alpha / 255
+typedef struct pfxk_flood_target { uint32_t rgba; float lin[3]; float ta; } pfxk_flood_target;
+// c[i] = pixel_color_distance(src[i], target) for n pixels; mode 0 legacy, 1 perceptual (d_table: 256 floats, srgb_to_linear(k / 255))
+hipError_t pfxk_color_distance(hipStream_t s, const uint8_t* d_src, uint8_t* d_out, size_t n, int mode, const pfxk_flood_target* T, const float* d_table);
+// d_list[0] = the seed's tile (d stays all 255: the first pass plants the seed)
+hipError_t pfxk_flood_seed(hipStream_t s, uint32_t w, uint32_t seed_x, uint32_t seed_y, uint32_t* d_list);
+// one pass: every tile of d_list[0 .. n) relaxes to its fixed point (or the round cap) and is written back.  A tile whose border pixel dropped below the
+// neighbour's pixel beside it appends that neighbour to d_next (once per pass: d_mark[tile] == stamp), itself when it hit the cap; d_state[0] counts the
+// entries of d_next, d_state[1] becomes non-zero when any byte decreased.  conn = 4 or 8.  The first pass gets the seed and lowers d[seed] to c[seed] inside its
+// tile — a decrease like any other, so a seed on a tile border schedules the tile across it; later passes get seed_x >= w
+hipError_t pfxk_flood_pass(hipStream_t s, int conn, const uint8_t* d_c, uint8_t* d_d, uint32_t w, uint32_t h, const uint32_t* d_list, uint32_t n,
+                           uint32_t* d_next, uint32_t* d_state, uint32_t* d_mark, uint32_t stamp, uint32_t seed_x, uint32_t seed_y);
+// d_table[4 t ..] = ~min x, ~min y, max x, max y of {d == t} (zeroed first: ~min x == 0 means none), atomically merged
+hipError_t pfxk_flood_bboxes(hipStream_t s, const uint8_t* d_dist, uint32_t w, uint32_t h, uint32_t* d_table);
+hipError_t pfxk_wand_mask(hipStream_t s, const uint8_t* d_dist, const uint8_t* d_base /* may be NULL */, uint8_t* d_out, size_t n, uint32_t threshold, int aa, int combine);
+hipError_t pfxk_fill_preview(hipStream_t s, const uint8_t* d_dist, const uint8_t* d_sel /* may be NULL */, uint8_t* d_out, size_t n, uint32_t threshold, uint32_t fill_rgba);
+hipError_t pfxk_fill_commit(hipStream_t s, uint8_t* d_layer, const uint8_t* d_dist, const uint8_t* d_sel /* may be NULL */, size_t n, uint32_t threshold,
+                            uint32_t fill_rgba, uint32_t mode);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,6 +147,20 @@ def _dab_array(dabs):
     return (_lib.InpaintDab * max(len(rows), 1))(*[_lib.InpaintDab(*r) for r in rows]), len(rows)
 
 
+DISTANCE_MODES = ["legacy", "perceptual"]                  # WandDistanceMode
+COMBINE_MODES = ["replace", "add", "subtract", "intersect"]   # SelectionMode, as merge_magic_wand_masks reads it (fill_magic.rs:486)
+
+
+def tolerance_threshold(tolerance: float) -> int:
+    """tolerance_threshold_u8 (fill_magic.rs:78): the tools' 0..100 tolerance as a distance threshold"""
+    return int(_lib.load().pfx_tolerance_threshold(C.c_float(tolerance)))
+
+
+def _flood(seed, target, distance_mode, connectivity, global_scope):
+    mode = DISTANCE_MODES.index(distance_mode) if isinstance(distance_mode, str) else int(distance_mode)
+    return _lib.Flood(int(seed[0]), int(seed[1]), _c4(target), mode, int(connectivity), int(bool(global_scope)), 0)
+
+
 def script_check(source: str, w: int = 64, h: int = 64):
     """Language-only evaluation of a script (no device, no image functions; ref: compile_script, scripting.rs:1489): returns
     the console lines or raises PfxError with .line / .col."""
@@ -620,6 +634,75 @@ class GpuRenderer:
         """dst_ptr == src_ptr fills in place"""
         self._check(self._lib.pfx_inpaint_patchmatch_dev(self._h, C.c_void_p(src_ptr), C.c_void_p(mask_ptr), C.c_void_p(dst_ptr), C.c_uint32(w), C.c_uint32(h),
                                                          C.c_uint32(patch_size), C.c_uint32(iterations)))
+
+    # ------------------------------------------------------------------ bucket fill and magic wand (ref: tools/behavior/raster/fill_magic.rs)
+    tolerance_threshold = staticmethod(tolerance_threshold)
+
+    def flood_distance(self, img, seed, target=None, distance_mode="legacy", connectivity: int = 4, global_scope: bool = False):
+        """compute_flood_distance_map / compute_global_distance_map: the (h, w) distance map from seed = (x, y); target None = the seed's pixel"""
+        s = _u8(img)
+        h, w = s.shape[:2]
+        if target is None and 0 <= seed[0] < w and 0 <= seed[1] < h:
+            target = s[seed[1], seed[0]]
+        f = _flood(seed, (0, 0, 0, 0) if target is None else target, distance_mode, connectivity, global_scope)
+        dist = np.empty((h, w), np.uint8)
+        self._check(self._lib.pfx_flood_distance(self._h, _p(s), C.c_uint32(w), C.c_uint32(h), C.byref(f), _p(dist)))
+        return dist
+
+    def flood_distance_dev(self, src_ptr: int, w: int, h: int, seed, target, dist_ptr: int, distance_mode="legacy", connectivity: int = 4, global_scope: bool = False):
+        f = _flood(seed, target, distance_mode, connectivity, global_scope)
+        self._check(self._lib.pfx_flood_distance_dev(self._h, C.c_void_p(src_ptr), C.c_uint32(w), C.c_uint32(h), C.byref(f), C.c_void_p(dist_ptr)))
+
+    def flood_bboxes_dev(self, dist_ptr: int, w: int, h: int) -> np.ndarray:
+        """the 256 cumulative bounding boxes (x0, y0, x1, y1; -1s = none) of {d <= t}: a (256, 4) int32 array"""
+        boxes = np.empty((256, 4), np.int32)
+        self._check(self._lib.pfx_flood_bboxes_dev(self._h, C.c_void_p(dist_ptr), C.c_uint32(w), C.c_uint32(h), _p(boxes)))
+        return boxes
+
+    def wand_mask(self, dist, threshold: int, anti_aliased: bool = False, combine="replace", base=None, out=None):
+        """the selection mask of a distance map; out may be `base` itself (in place)"""
+        d = _u8(dist)
+        h, w = d.shape[:2]
+        b = None if base is None else _u8(base)
+        o = np.empty((h, w), np.uint8) if out is None else out
+        self._check(self._lib.pfx_wand_mask(self._h, _p(d), _p(b), C.c_uint32(w), C.c_uint32(h), C.c_uint8(threshold), C.c_uint8(int(anti_aliased)),
+                                            C.c_uint8(_enum(COMBINE_MODES, combine).value), _p(o)))
+        return o
+
+    def wand_mask_dev(self, dist_ptr: int, w: int, h: int, threshold: int, out_ptr: int, anti_aliased: bool = False, combine="replace", base_ptr: int = 0):
+        self._check(self._lib.pfx_wand_mask_dev(self._h, C.c_void_p(dist_ptr), C.c_void_p(base_ptr or None), C.c_uint32(w), C.c_uint32(h), C.c_uint8(threshold),
+                                                C.c_uint8(int(anti_aliased)), C.c_uint8(_enum(COMBINE_MODES, combine).value), C.c_void_p(out_ptr)))
+
+    def fill_preview(self, dist, threshold: int, fill, selection=None):
+        """the fill tool's preview layer over the whole canvas, the form composite_preview takes; fill = 4 bytes"""
+        d = _u8(dist)
+        h, w = d.shape[:2]
+        sel = None if selection is None else _u8(selection)
+        out = np.empty((h, w, 4), np.uint8)
+        self._check(self._lib.pfx_fill_preview(self._h, _p(d), _p(sel), C.c_uint32(w), C.c_uint32(h), C.c_uint8(threshold), _c4(fill), _p(out)))
+        return out
+
+    def fill_preview_dev(self, dist_ptr: int, w: int, h: int, threshold: int, fill, canvas_ptr: int, selection_ptr: int = 0):
+        self._check(self._lib.pfx_fill_preview_dev(self._h, C.c_void_p(dist_ptr), C.c_void_p(selection_ptr or None), C.c_uint32(w), C.c_uint32(h), C.c_uint8(threshold),
+                                                   _c4(fill), C.c_void_p(canvas_ptr)))
+
+    def fill_commit_dev(self, layer_ptr: int, dist_ptr: int, w: int, h: int, threshold: int, fill, blend_mode: int = 0, selection_ptr: int = 0):
+        """fill_preview + brush_commit in one kernel, in place in the layer"""
+        self._check(self._lib.pfx_fill_commit_dev(self._h, C.c_void_p(layer_ptr), C.c_void_p(dist_ptr), C.c_void_p(selection_ptr or None), C.c_uint32(w), C.c_uint32(h),
+                                                  C.c_uint8(threshold), _c4(fill), C.c_uint8(blend_mode)))
+
+    def bucket_fill(self, layer, seed, tolerance: float, fill, blend_mode: int = 0, global_fill: bool = False, selection=None):
+        """perform_flood_fill + commit on a copy of `layer`: target = the layer pixel at seed = (x, y), LegacyRgba, 4-connected"""
+        l = _u8(layer).copy()
+        h, w = l.shape[:2]
+        sel = None if selection is None else _u8(selection)
+        self._check(self._lib.pfx_bucket_fill(self._h, _p(l), C.c_uint32(w), C.c_uint32(h), C.c_uint32(seed[0]), C.c_uint32(seed[1]), C.c_float(tolerance), _c4(fill),
+                                              C.c_uint8(blend_mode), C.c_int(int(global_fill)), _p(sel)))
+        return l
+
+    def flood_last(self, which: int) -> int:
+        """the last flood_distance's 0 passes, 1 kernel launches, 2 tile edge, 3 tile visits (pfx_int_flood_last; for tests and profiles)"""
+        return int(self._lib.pfx_int_flood_last(self._h, C.c_int(which)))
 
     # ------------------------------------------------------------------ script front-end
     def resize_image(self, img, new_w: int, new_h: int, filter="bilinear"):   # transform.rs:347 (imageops::resize)

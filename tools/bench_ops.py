@@ -37,12 +37,13 @@ def main() -> int:
     g.manual_seed(0x5EED0001)
     rows = []
 
-    def timed(name, timer_names, fn, px, alg_bytes_per_px, note=""):
+    def timed(name, timer_names, fn, px, alg_bytes_per_px, note="", reps=None, warm=True):
         if args.only and args.only not in name:
             return
         import time
+        reps = reps or args.reps
         t_warm = time.perf_counter()  # clocks ramp over the first ~30 ms of load (bench.py's PREWARM standard)
-        while True:
+        while warm:
             for _ in range(5):
                 fn()
             torch.cuda.synchronize()
@@ -50,11 +51,11 @@ def main() -> int:
                 break
         r.timing_reset()
         r.timing_enable(True)
-        for _ in range(args.reps):
+        for _ in range(reps):
             fn()
         torch.cuda.synchronize()
         r.timing_enable(False)
-        ms = sum(r.timing_read(t)[0] for t in timer_names) / args.reps
+        ms = sum(r.timing_read(t)[0] for t in timer_names) / reps
         gbs = alg_bytes_per_px * px / (ms * 1e-3) / 1e9
         rows.append({"op": name, "ms": round(ms, 4), "Mpx_s": round(px / ms / 1e3, 1), "alg_bytes_px": alg_bytes_per_px,
                      "achieved_GBs": round(gbs, 1), "hbm_frac": round(gbs / HBM_PEAK, 4), "note": note})
@@ -148,6 +149,53 @@ def main() -> int:
     timed("resize 8K -> 4K bilinear", ["resize"], lambda: r.resize_image_dev(s, w, h, half.data_ptr(), w // 2, h // 2, "bilinear"), px, 5, "4 B read + 1 B/px (quarter-size) written")
     timed("resize 8K -> 4K lanczos3", ["resize"], lambda: r.resize_image_dev(s, w, h, half.data_ptr(), w // 2, h // 2, "lanczos3"), px, 5)
     del half
+    # ---------------- bucket fill / magic wand (k_flood.hip): the 5 B/px global-scope distance next to the 5 B/px resizes above, then the connected flood
+    dist = torch.empty((h, w), dtype=torch.uint8, device=dev)
+    dp = dist.data_ptr()
+    grey = (120, 120, 120, 255)
+    timed("flood: colour distance, global scope, legacy", ["flood_distance_global"], lambda: r.flood_distance_dev(s, w, h, (0, 0), grey, dp, "legacy", 4, True), px, 5,
+          "4 B read + 1 B written per pixel, 16-byte loads")
+    timed("flood: colour distance, global scope, perceptual", ["flood_distance_global"], lambda: r.flood_distance_dev(s, w, h, (0, 0), grey, dp, "perceptual", 4, True), px, 5,
+          "f32 luma / chroma terms, one sqrt, the sRGB table in LDS")
+    fl = torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
+
+    def flood_row(name, build):
+        if args.only and args.only not in name:
+            return
+        build()
+        torch.cuda.synchronize()
+        target = tuple(int(v) for v in fl[0, 0].tolist())
+        run = lambda: r.flood_distance_dev(fl.data_ptr(), w, h, (0, 0), target, dp, "legacy", 4, False)
+        run()   # the counters, and the one warm-up call: a connected flood is thousands of launches and read-backs on the serpentine, so 3 timed calls
+        p, v, tile = r.flood_last(0), r.flood_last(3), r.flood_last(2)
+        timed(name, ["flood_distance"], run, px, 5, reps=3, warm=False, note=
+              f"contiguous, legacy, 4-connected, seed (0, 0): {p} passes, {v} tile visits of {((w + tile - 1) // tile) * ((h + tile - 1) // tile)} tiles; per pass "
+              f"{v / p:.1f} tiles x ({tile * tile} B of c + {(tile + 2) ** 2} B of d read, <= {tile * tile} B written), one 8-byte read-back; mean of 3 calls")
+
+    def build_uniform():
+        fl[...] = torch.tensor(grey, dtype=torch.uint8, device=dev)
+
+    def build_noise():   # steps of a few units around a base colour: every threshold cuts the canvas into ragged regions
+        fl[..., :3] = (120 + torch.randint(-8, 9, (h, w, 3), device=dev, generator=g)).to(torch.uint8)
+        fl[..., 3] = 255
+
+    def build_serpentine():   # tests/flood_cases.py's snake with 32-pixel bands: corridor bands joined at alternating ends through the wall bands
+        band = torch.arange(h, device=dev) // 32
+        wall = (band % 2 == 1)[:, None].expand(h, w).clone()
+        xs = torch.arange(w, device=dev)[None, :]
+        right = ((band // 2) % 2 == 0)[:, None]
+        wall &= ~torch.where(right, xs >= w - 32, xs < 32)
+        fl[...] = torch.tensor(grey, dtype=torch.uint8, device=dev)
+        fl[..., 0] = torch.where(wall, 255, 120).to(torch.uint8)
+    flood_row("flood: connected, uniform image", build_uniform)
+    flood_row("flood: connected, noise at threshold-scale contrast", build_noise)
+    flood_row("flood: connected, serpentine of 32-px bands", build_serpentine)
+    bmask = torch.empty((h, w), dtype=torch.uint8, device=dev)
+    timed("wand mask: threshold + AA band + add to a base", ["wand_mask"], lambda: r.wand_mask_dev(dp, w, h, 40, bmask.data_ptr(), True, "add", m), px, 3)
+    timed("fill preview (whole canvas)", ["fill_preview"], lambda: r.fill_preview_dev(dp, w, h, 40, (200, 30, 60, 255), d, m), px, 6)
+    timed("fill commit (preview + blend in one kernel, multiply)", ["fill_commit"], lambda: r.fill_commit_dev(d, dp, w, h, 40, (200, 30, 60, 255), 1, m), px, 10,
+          "1 + 1 B read, layer 4 B read + written where the fill lands")
+    del fl, dist, bmask
     src_h = src.cpu().numpy()
     import time
     r.execute_script_sync("map_channels(|r, g, b, a| [255 - r, g / 2, (b * 3 + a) / 4, a]);", src_h)   # warm: a process's first launch of k_script's code object loads it (~1 ms)

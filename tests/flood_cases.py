@@ -156,7 +156,14 @@ def spiral(n=129):
     return _corridor_image(order, n, 4), order
 
 
-CORRIDORS = {"snake": snake, "spiral": spiral}
+def long_snake():
+    """the snake over 4 x 4 tiles: every corridor row crosses three tile borders and comes back through the tiles it left two rows later, so a tile is listed
+    in hundreds of passes and its stamp changes as often"""
+    return snake(LONG_SNAKE_N)
+
+
+LONG_SNAKE_N = 3 * TILE + 1
+CORRIDORS = {"snake": snake, "spiral": spiral, "long_snake": long_snake}
 CORRIDOR_TARGET = (0, 0, 0, 255)
 
 
@@ -182,6 +189,60 @@ def walled(tiles_x=3, tiles_y=2, tile=TILE):
     img[40, :41] = (255, 255, 255, 255)
     img[:41, 40] = (255, 255, 255, 255)
     return img
+
+
+# ---- many tiles in flight ------------------------------------------------------------------------------------------------------------------------------------------
+# 9 x 7 whole tiles and one ragged pixel in each direction: 10 x 8 = 80 tiles, so a pass's tile list holds many tiles and the lists, the stamps and the
+# "visit only listed tiles" schedule work with more than a handful
+MANY_TILES_X, MANY_TILES_Y = 10, 8
+MANY_W, MANY_H = 9 * TILE + 1, 7 * TILE + 1
+MANY_SEEDS = {"corner": (0, 0), "centre": (MANY_W // 2, MANY_H // 2)}
+
+
+def uniform_many():
+    img = np.empty((MANY_H, MANY_W, 4), np.uint8)
+    img[...] = (90, 120, 150, 255)
+    return img
+
+
+# a half-transparent target: the opaque noise and the transparent stripes of `clear` are both about 127 from it, so the flood crosses the stripes and
+# reaches every tile (from the seed's own pixel the stripes are walls at 255 and the flood stays in one band).  In the perceptual mode the alpha term
+# decides and the map has two values, 127 in the seed's band and 128 beyond it: little to compare, but every tile is still listed and lowered
+HALF_CLEAR = (120, 120, 120, 128)
+
+# (name, w, h, image, seed, target or None) like DISTANCE_CASES; the seed of the two 80-tile images is a tile corner, the strips are 40 tiles one pixel short
+MANY_TILE_CASES = [
+    ("many-noise-tile-corner", MANY_W, MANY_H, "noise", (4 * TILE, 3 * TILE), None),
+    ("many-clear-tile-corner", MANY_W, MANY_H, "clear", (3 * TILE, 4 * TILE), HALF_CLEAR),
+    ("wide-40x1-tiles", 40 * TILE - 1, TILE - 1, "clear", (0, 30), HALF_CLEAR),
+    ("tall-1x40-tiles", TILE - 1, 40 * TILE - 1, "noise", (31, 40 * TILE - 2), (120, 120, 120, 255)),
+]
+# (mode, connectivity) pairs the many-tile cases run in, each in both scopes: both modes and both connectivities without the full cross product (a Dijkstra of
+# the model over 260 000 pixels takes a second or two)
+MANY_TILE_RUNS = [(M.LEGACY, 4), (M.PERCEPTUAL, 8)]
+
+
+@functools.lru_cache(maxsize=None)
+def many_tile_expected(case_name, mode, connectivity, global_scope):
+    """Dijkstra alone: test_flood_model_host.py holds it to the relaxation where that is quick enough"""
+    case = next(c for c in MANY_TILE_CASES if c[0] == case_name)
+    img, seed, target = case_image(case)
+    d = M.distance_map(img, seed, target, mode, connectivity, global_scope, False)
+    d.setflags(write=False)
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def uniform_many_expected(where, connectivity):
+    img = uniform_many()
+    seed = MANY_SEEDS[where]
+    d = M.distance_map(img, seed, img[seed[1], seed[0]], M.LEGACY, connectivity, False, False)
+    d.setflags(write=False)
+    return d
+
+
+def tile_count(w, h, tile=TILE):
+    return ((w + tile - 1) // tile) * ((h + tile - 1) // tile)
 
 
 # ---- threshold-stage inputs ------------------------------------------------------------------------------------------------------------------------------------

@@ -4,13 +4,20 @@ Instant sweep (canvas 131 x 77): every case must change at least 20 pixels in th
 (`outside`: the brush lies wholly off the canvas; `all_in_hole`: every ring candidate lies in the hole), which must change none.
 PatchMatch sweep (61 x 45 and 64 x 64, holes of at most about 250 pixels): patch sizes 3, 4, 5, 7, 9, 11 and iterations 3 and 6 are dealt over the hole
 shapes and the two kinds of content; `bw_split` reaches the sequential-f32 SSD branch (integer sum >= 2^24), `ring_pixel_island` leaves boundary pixels
-unfilled (a one-pixel island gives its four neighbours one valid patch pixel, below min_valid = 2 of patch 3)."""
+unfilled (a one-pixel island gives its four neighbours one valid patch pixel, below min_valid = 2 of patch 3).
+PatchMatch edges (`PATCHMATCH_EDGES`): one case per loop of k_inpaint.hip that walks block-sized pieces; each leaves the first turn of exactly the loop it is
+named for.  tests/test_inpaint_model_host.py holds every case to the condition that makes it cross its edge, so a later edit of a mask cannot un-cross it.
+Second instant canvas (301 x 203, no multiple of 64 or 4): dab lists whose union box is almost the canvas, and a chain of 65 overlapping dabs."""
+import functools
 import os
 
 import numpy as np
 
+from . import inpaint_model as M
+
 GOLDEN_W = GOLDEN_H = 64
 SWEEP_W, SWEEP_H = 131, 77
+SWEEP2_W, SWEEP2_H = 301, 203      # the second instant canvas: several 64 x 4 thread blocks in both directions, ragged in both
 
 
 def load_goldens():
@@ -106,7 +113,42 @@ def instant_cases():
     vals = np.where(hole > 0, rng.choice(np.array([1, 200, 255], np.uint8), (H, W)), 0).astype(np.uint8)
     cases.append(("mask_values_1_200_255", noise, vals, clear, [(64.0, 38.0, 14.0, 24.0, 0.5)], "changes"))
     cases.append(("five_overlapping_dabs", ramp_with_noise(W, H), hole, mixed, FIVE_DABS, "changes"))
-    return cases
+    return cases + _instant_cases_second_canvas()
+
+
+CHAIN_65 = "chain_of_65_overlapping_dabs"
+
+
+def instant_canvas(name):
+    """(w, h) of a case of instant_cases()"""
+    return (SWEEP2_W, SWEEP2_H) if name in ("walk_300_dabs", "two_far_corners", CHAIN_65) else (SWEEP_W, SWEEP_H)
+
+
+def walk_dabs():
+    """300 small dabs from the left edge to the right one, zigzagging over the whole height: the union of their pixel boxes is the canvas but for a few pixels;
+    five sample radii (the host's ring table), every hardness"""
+    radii = (9.0, 12.5, 7.0, 15.0, 10.25)
+    return [(1.5 + k * (SWEEP2_W - 3.0) / 299.0, 1.25 + float(k * 37 % (SWEEP2_H - 2)), 2.0 + 0.5 * (k % 4), radii[k % 5], (k % 5) * 0.25) for k in range(300)]
+
+
+def chain_dabs():
+    """65 dabs 3.5 pixels apart with brush radius 9 and sample radius 16: dab k's brush covers most of what dab k - 1 wrote in `out`, and its sample ring reaches
+    across the pixels of the dabs before it (the ring reads src, as the reference's does, so the list must equal the single calls in order)"""
+    return [(20.0 + 3.5 * k, 100.0 + 6.0 * np.sin(0.4 * k).item(), 9.0, 16.0 if k % 2 else 13.0, (k % 3) * 0.4) for k in range(65)]
+
+
+def _instant_cases_second_canvas():
+    W, H = SWEEP2_W, SWEEP2_H
+    y, x = np.mgrid[0:H, 0:W]
+    src = ramp_with_noise(W, H, 16)
+    squares = np.where((x // 6 + y // 6) % 2 == 0, 255, 0).astype(np.uint8)      # painted-over squares between source squares, all over the canvas
+    mixed = _noise(W, H, 17)
+    mixed[..., 3] = np.random.default_rng(18).choice(np.array([0, 64, 128, 255], np.uint8), (H, W))
+    band = _rect_mask(W, H, 0, 84, W, 118)
+    band[(x + y) % 7 == 0] = 0                                                 # source pixels inside the chain's band
+    return [("walk_300_dabs", src, squares, mixed, walk_dabs(), "changes"),
+            ("two_far_corners", src, squares, np.zeros_like(src), [(5.0, 4.5, 8.0, 14.0, 0.5), (W - 6.0, H - 5.5, 8.0, 14.0, 0.2)], "changes"),
+            (CHAIN_65, src, band, mixed, chain_dabs(), "changes")]
 
 
 FIVE_DABS = [(56.0, 32.0, 9.0, 18.0, 0.5), (61.5, 35.25, 9.0, 24.0, 0.2), (67.0, 38.0, 10.0, 18.0, 0.9), (72.25, 41.0, 8.0, 24.0, 0.5),
@@ -168,6 +210,26 @@ def _hole(shape, w, h):
         m[15:27, 30:42] = 255          # 12 x 12: 6 peels
     elif shape == "small":
         m[30:33, 20:23] = 255
+    elif shape in ("antidiag_band", "maindiag_band"):       # three diagonals wide, clipped to 45 columns
+        y, x = np.mgrid[0:h, 0:w]
+        k = x + y - 88 if shape == "antidiag_band" else x - y - 5
+        m[(k >= 0) & (k <= 2) & (x >= 25) & (x < 70)] = 255
+    elif shape == "stripe":                                 # 2 x 540: every pixel is a boundary pixel of the first peel
+        m[h // 2 - 1:h // 2 + 1, 50:590] = 255
+    elif shape == "far_corners":                            # two 3 x 3 holes
+        m[3:6, 4:7] = 255
+        m[h - 7:h - 4, w - 8:w - 5] = 255
+    elif shape == "both_corners":                           # 6 x 6 in the first corner and in the last: the box is the canvas
+        m[:6, :6] = 255
+        m[h - 6:, w - 6:] = 255
+    elif shape == "full_cross":                             # one full row band and one full column band
+        m[h // 2 - 1:h // 2 + 2, :] = 255
+        m[:, w // 2 - 1:w // 2 + 2] = 255
+    elif shape == "one_pixel":
+        m[h // 2, w // 2] = 255
+    elif shape == "two_pixels":
+        m[h // 2, w // 2] = 255
+        m[h // 2 - 1, w // 2] = 200
     else:
         raise ValueError(shape)
     return m
@@ -179,6 +241,45 @@ PATCHMATCH_SWEEP = [  # (canvas, hole shape, content, patch size, iterations)
     ((64, 64), "corner", "gradnoise", 11, 3), ((64, 64), "edge", "palette", 9, 6), ((64, 64), "two", "gradnoise", 7, 3), ((64, 64), "L", "palette", 4, 3),
     ((64, 64), "ring", "gradnoise", 5, 6), ((64, 64), "blob", "palette", 3, 6), ((64, 64), "deep", "gradnoise", 7, 3),
     ((64, 64), "small", "bw_split", 11, 3), ((64, 64), "ring_pixel_island", "palette", 3, 3), ((61, 45), "ring_pixel_island", "gradnoise", 1, 6)]
+
+
+# What the device code does in block-sized pieces (paintfe_amd/csrc/k_inpaint.hip); the edge cases are sized against these
+PM_PASS_WAVES = 16           # pm_pass_kernel: `for (i = lo + wave; i < hi; i += 16u)` — boundary pixels of one anti-diagonal handled per round
+PM_BLOCK_THREADS = 1024      # pm_bucket_kernel: `i += 1024u` / `base += 1024u` (boundary pixels and diagonals per turn); pm_scan_kernel: `base += 1024u` (blocks)
+PM_COMPACT_ELEMS = 1024      # compact_flags / pm_count_kernel: `blockIdx.x * 1024u` — rectangle elements per compaction block
+
+PATCHMATCH_EDGES = [  # (canvas, hole shape, content, patch size, iterations); the edge each crosses is spelt in EDGE_CONDITIONS
+    ((97, 83), "antidiag_band", "gradnoise", 5, 3), ((97, 83), "antidiag_band", "palette", 7, 6),
+    ((97, 83), "maindiag_band", "palette", 3, 6), ((97, 83), "maindiag_band", "gradnoise", 9, 3),
+    ((640, 24), "stripe", "gradnoise", 5, 3),
+    ((600, 520), "far_corners", "palette", 3, 3),
+    ((1100, 960), "both_corners", "palette", 7, 3),
+    ((70, 50), "full_cross", "gradnoise", 7, 6),
+    ((5, 4), "one_pixel", "gradnoise", 11, 3), ((5, 4), "one_pixel", "gradnoise", 7, 6), ((3, 9), "two_pixels", "gradnoise", 7, 3),
+    ((10, 9), "one_pixel", "palette", 11, 6), ((8, 7), "two_pixels", "gradnoise", 9, 3)]
+
+# Patch 11 wants min_valid = 121 / 4 = 30 valid patch pixels and a 5 x 4 canvas has 20: every SSD is F32_MAX and the reference leaves the pixel unfilled.  The
+# case is kept for what it runs (a query whose 121 slots are all clipped, the unfilled path); the cases after it are the ones that fill.
+def _pick(specs, canvas, shape, patch_size=None):
+    """the one spec of a list with this canvas and hole shape (and patch size, where two share them)"""
+    found = [s for s in specs if s[0] == canvas and s[1] == shape and patch_size in (None, s[3])]
+    assert len(found) == 1, (canvas, shape, patch_size, found)
+    return found[0]
+
+
+NEVER_FILLABLE = _pick(PATCHMATCH_EDGES, (5, 4), "one_pixel", 11)
+
+# a huge box and source list, then a small canvas, then a long boundary list: what test_gpu_inpaint.py runs on one context
+GEOMETRY_SEQUENCE = [_pick(PATCHMATCH_EDGES, (600, 520), "far_corners"), _pick(PATCHMATCH_SWEEP, (61, 45), "deep", 5), _pick(PATCHMATCH_EDGES, (640, 24), "stripe")]
+
+
+@functools.lru_cache(maxsize=None)
+def patchmatch_expected(spec):
+    """the model's (image, counters, peel trace) of a case, computed once per session and shared read-only by the host and the GPU tests"""
+    trace = []
+    img, k = M.patchmatch(*patchmatch_case(spec), trace=trace)
+    img.setflags(write=False)
+    return img, k, trace
 
 
 def patchmatch_case(spec):

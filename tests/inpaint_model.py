@@ -259,8 +259,9 @@ def _pass(img, mask, pixels, ox, oy, sd, half, min_valid, max_radius, it, counte
         ox[hy, hx], oy[hy, hx], sd[hy, hx] = best_ox, best_oy, best
 
 
-def patchmatch(src, hole_mask, patch_size, iterations):
-    """fill_region_patchmatch :394-520: (image, {"peels", "big_sums", "unfilled", "ssd_calls"})"""
+def patchmatch(src, hole_mask, patch_size, iterations, trace=None):
+    """fill_region_patchmatch :394-520: (image, {"peels", "big_sums", "unfilled", "ssd_calls"}).  `trace`, a list, receives every peel's boundary pixels
+    [(x, y)] in scan order: a read-only tap the tests derive structural conditions from"""
     src = np.ascontiguousarray(src, np.uint8)
     hole_mask = np.ascontiguousarray(hole_mask, np.uint8)
     h, w = hole_mask.shape
@@ -285,6 +286,8 @@ def patchmatch(src, hole_mask, patch_size, iterations):
         if not boundary:
             break
         k.peels += 1
+        if trace is not None:
+            trace.append(list(boundary))
         src_count = len(source)
         for hx, hy in boundary:
             sx, sy = source[(hx * 7919 + hy * 6271) % src_count]

@@ -51,6 +51,53 @@ def test_corridors(name, connectivity):
     assert tile_crossings >= 24
 
 
+def test_the_long_corridor_re_enters_the_tiles_it_left():
+    img, order = FC.CORRIDORS["long_snake"]()
+    assert img.shape[0] == FC.LONG_SNAKE_N and FC.tile_count(*img.shape[1::-1]) == 16
+    tiles = [(x // FC.TILE, y // FC.TILE) for x, y in order]
+    runs = [t for k, t in enumerate(tiles) if k == 0 or t != tiles[k - 1]]      # the tiles in the order the corridor visits them
+    assert len(runs) - 1 >= 40                                                   # border crossings
+    entries = {t: runs.count(t) for t in set(runs)}
+    print("border crossings", len(runs) - 1, "most entries into one tile", max(entries.values()))
+    assert len(entries) == 16 and sum(1 for v in entries.values() if v >= 16) >= 9      # every whole tile is left and entered again dozens of times
+
+
+@pytest.mark.parametrize("run", FC.MANY_TILE_RUNS, ids=["legacy-4", "perceptual-8"])
+@pytest.mark.parametrize("case", FC.MANY_TILE_CASES, ids=[c[0] for c in FC.MANY_TILE_CASES])
+def test_many_tile_cases_have_many_tiles_and_an_answer_that_is_not_trivial(case, run):
+    mode, connectivity = run
+    name, w, h, kind, seed, target = case
+    tiles_x, tiles_y = -(-w // FC.TILE), -(-h // FC.TILE)
+    if name.startswith("many-"):
+        assert (w, h) == (FC.MANY_W, FC.MANY_H) and tiles_x * tiles_y >= 63 and w % FC.TILE == 1 and h % FC.TILE == 1
+        assert (seed[0] % FC.TILE, seed[1] % FC.TILE) in ((0, 0), (FC.TILE - 1, FC.TILE - 1))      # a tile's corner pixel
+    else:
+        assert sorted((tiles_x, tiles_y)) == [1, 40] and w % FC.TILE == FC.TILE - 1 and h % FC.TILE == FC.TILE - 1
+    d = FC.many_tile_expected(name, mode, connectivity, False)
+    img, seed, target = FC.case_image(case)
+    c = M.color_distance(img, target, mode)
+    assert np.array_equal(d, M.relaxation(c, seed, connectivity))           # the model's two algorithms agree
+    assert np.array_equal(FC.many_tile_expected(name, mode, connectivity, True), c) and (d >= c).all()
+    assert len(np.unique(d)) > 1 and len(np.unique(c)) > 1
+    below = d < 255                                                          # the flood leaves the seed's tile: pixels below 255 in several tiles
+    ys, xs = np.nonzero(below)
+    reached = len(set(zip((xs // FC.TILE).tolist(), (ys // FC.TILE).tolist())))
+    print(name, run, "tiles", tiles_x * tiles_y, "tiles reached below 255:", reached, "distinct distances", len(np.unique(d)))
+    assert reached == tiles_x * tiles_y      # every tile is listed at least once
+
+
+def test_the_uniform_many_tile_image():
+    assert FC.tile_count(FC.MANY_W, FC.MANY_H) == FC.MANY_TILES_X * FC.MANY_TILES_Y >= 63
+    img = FC.uniform_many()
+    assert img.shape == (FC.MANY_H, FC.MANY_W, 4) and (img == img[0, 0]).all()      # so the model's map is 0 everywhere: c is 0, and d <= max over a path of c
+    assert not M.color_distance(img, img[0, 0], M.LEGACY).any()
+    for where, seed in FC.MANY_SEEDS.items():
+        assert 0 <= seed[0] < FC.MANY_W and 0 <= seed[1] < FC.MANY_H
+        for connectivity in (4, 8):
+            d = FC.uniform_many_expected(where, connectivity)
+            assert d.shape == (FC.MANY_H, FC.MANY_W) and not d.any()
+
+
 def ring(gap):
     """5 x 5: a wall ring around the centre; with `gap` the wall's corner pixel (1, 1) is open: a diagonal-only way out"""
     v = np.zeros((5, 5), np.uint8)

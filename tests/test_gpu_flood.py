@@ -95,6 +95,36 @@ def test_uniform_image_takes_one_pass_per_tile_step(gpu, connectivity):
 
 
 @pytest.mark.parametrize("connectivity", [4, 8])
+@pytest.mark.parametrize("where", sorted(FC.MANY_SEEDS))
+def test_uniform_image_of_80_tiles_keeps_many_tiles_in_flight(gpu, where, connectivity):
+    assert gpu.flood_last(2) == FC.TILE
+    tiles = FC.tile_count(FC.MANY_W, FC.MANY_H)
+    got = gpu.flood_distance(FC.uniform_many(), FC.MANY_SEEDS[where], None, M.LEGACY, connectivity)
+    assert np.array_equal(got, FC.uniform_many_expected(where, connectivity))      # 0 everywhere: test_flood_model_host.py
+    passes, visits = gpu.flood_last(0), gpu.flood_last(3)
+    print(where, connectivity, "passes", passes, "visits", visits, "tiles", tiles)
+    assert passes <= tiles + 2, passes
+    assert visits <= passes * tiles, (visits, passes)
+    assert visits > passes, (visits, passes)                          # more than one tile in at least one pass
+    assert visits >= tiles                                            # every tile is reached
+
+
+@pytest.mark.parametrize("global_scope", [False, True], ids=["contiguous", "global"])
+@pytest.mark.parametrize("run", FC.MANY_TILE_RUNS, ids=["legacy-4", "perceptual-8"])
+@pytest.mark.parametrize("case", FC.MANY_TILE_CASES, ids=[c[0] for c in FC.MANY_TILE_CASES])
+def test_many_tiles_equal_the_model(gpu, case, run, global_scope):
+    mode, connectivity = run
+    img, seed, target = FC.case_image(case)
+    want = FC.many_tile_expected(case[0], mode, connectivity, global_scope)
+    got = gpu.flood_distance(img, seed, target, mode, connectivity, global_scope)
+    assert np.array_equal(got, want), (case[0], int((got != want).sum()))
+    if not global_scope:
+        print(case[0], run, "passes", gpu.flood_last(0), "visits", gpu.flood_last(3))
+        assert 1 <= gpu.flood_last(0) < pass_cap(case[1], case[2])
+        assert gpu.flood_last(3) <= gpu.flood_last(0) * FC.tile_count(case[1], case[2])
+
+
+@pytest.mark.parametrize("connectivity", [4, 8])
 def test_walled_in_seed_visits_its_own_tile_only(gpu, connectivity):
     tile = gpu.flood_last(2)
     img = FC.walled(3, 2, tile)

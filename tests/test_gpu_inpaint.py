@@ -103,6 +103,54 @@ def test_patchmatch_sweep_matches_the_model(gpu, spec):
     assert np.array_equal(patchmatch_dev(gpu, src, mask, ps, iters, True), got)
 
 
+def test_a_chain_of_65_overlapping_dabs_equals_single_dab_calls_in_order(gpu):
+    name, src, mask, out, dabs, _ = next(c for c in IC.instant_cases() if c[0] == IC.CHAIN_65)
+    one_call = gpu.inpaint_instant(src, mask, out, dabs)
+    cur = out
+    for d in dabs:
+        cur = gpu.inpaint_instant(src, mask, cur, [d])
+    assert np.array_equal(one_call, cur)
+    assert not np.array_equal(one_call, gpu.inpaint_instant(src, mask, out, dabs[::-1]))      # the order matters on this input
+
+
+def _peels(gpu):
+    return int(gpu._lib.pfx_int_inpaint_last(gpu._h, C.c_int(0)))
+
+
+@pytest.mark.parametrize("spec", IC.PATCHMATCH_EDGES, ids=IC.patchmatch_id)
+def test_patchmatch_edges_match_the_model(gpu, spec):
+    """one case per block-sized loop of k_inpaint.hip (tests/inpaint_cases.py says which; tests/test_inpaint_model_host.py holds each to its condition)"""
+    src, mask, ps, iters = IC.patchmatch_case(spec)
+    want, k, _ = IC.patchmatch_expected(spec)
+    print(IC.patchmatch_id(spec), k)
+    got = gpu.inpaint_patchmatch(src, mask, ps, iters)
+    assert np.array_equal(got, want), f"{int((got != want).any(-1).sum())} px differ from the model"
+    assert _peels(gpu) == k["peels"]
+    assert np.array_equal(patchmatch_dev(gpu, src, mask, ps, iters, False), got)
+    assert np.array_equal(patchmatch_dev(gpu, src, mask, ps, iters, True), got)
+
+
+def test_one_context_through_changing_geometry():
+    """a huge box and source list, then a small canvas, then a long boundary list, on ONE context: the working block has grown and every offset inside it moves
+    from call to call, so anything read from it before it is written would show.  Each result equals a fresh context's and the model's."""
+    from paintfe_amd import GpuRenderer
+    one = GpuRenderer(0)
+    try:
+        for spec in IC.GEOMETRY_SEQUENCE:
+            src, mask, ps, iters = IC.patchmatch_case(spec)
+            want, k, _ = IC.patchmatch_expected(spec)
+            got = one.inpaint_patchmatch(src, mask, ps, iters)
+            assert np.array_equal(got, want), (IC.patchmatch_id(spec), int((got != want).any(-1).sum()))
+            assert _peels(one) == k["peels"]
+            fresh = GpuRenderer(0)
+            try:
+                assert np.array_equal(fresh.inpaint_patchmatch(src, mask, ps, iters), got), IC.patchmatch_id(spec)
+            finally:
+                fresh.close()
+    finally:
+        one.close()
+
+
 @pytest.mark.parametrize("fill", [0, 255], ids=["empty_mask", "all_hole"])
 def test_patchmatch_without_a_hole_or_without_a_source_copies_src(gpu, fill):
     src, _, ps, iters = IC.patchmatch_case(IC.PATCHMATCH_SWEEP[0])

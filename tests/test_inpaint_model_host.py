@@ -42,7 +42,7 @@ def test_instant_sweep_cases_change_pixels(case):
     name, src, mask, out, dabs, expect = case
     img, changed = M.instant_list(src, mask, out, dabs)
     print(name, "pixels changed:", changed)
-    assert src.shape == (IC.SWEEP_H, IC.SWEEP_W, 4)
+    assert src.shape == IC.instant_canvas(name)[::-1] + (4,)
     if expect == "nothing":
         assert changed == 0 and np.array_equal(img, out)
     else:
@@ -58,6 +58,112 @@ def test_instant_sweep_holds_what_it_is_named_for():
     assert not cases["transparent_out_noise"][3].any()
     five = cases["five_overlapping_dabs"][4]
     assert len(five) == 5 and len({d[3] for d in five}) == 2
+
+
+def test_second_instant_canvas_holds_what_it_is_named_for():
+    cases = {c[0]: c for c in IC.instant_cases()}
+    W, H = IC.SWEEP2_W, IC.SWEEP2_H
+    assert W % 64 and W % 4 and H % 4 and W > 4 * 64 and H > 4 * 4 and {IC.instant_canvas(n) for n in cases} == {(IC.SWEEP_W, IC.SWEEP_H), (W, H)}
+
+    def boxes(dabs):   # the dabs' pixel loop bounds (inpaint.rs:93-96) through the model's own conversions
+        out = []
+        for cx, cy, r, _, _ in dabs:
+            cx, cy, r = M.f32(cx), M.f32(cy), max(M.f32(r), M.f32(1.0))
+            out.append((M.as_u32(max(cx - r, M.f32(0.0))), M.as_u32(max(cy - r, M.f32(0.0))), min(M.as_u32(np.ceil(cx + r)), W - 1), min(M.as_u32(np.ceil(cy + r)), H - 1)))
+        return np.array(out)
+
+    walk = boxes(cases["walk_300_dabs"][4])
+    assert len(walk) == 300 and len({d[3] for d in cases["walk_300_dabs"][4]}) == 5
+    assert walk[:, 0].min() == 0 and walk[:, 1].min() == 0 and walk[:, 2].max() == W - 1 and walk[:, 3].max() >= H - 3      # the union box is almost the canvas
+    far = boxes(cases["two_far_corners"][4])
+    union = (far[:, 2].max() - far[:, 0].min() + 1) * (far[:, 3].max() - far[:, 1].min() + 1)
+    own = ((far[:, 2] - far[:, 0] + 1) * (far[:, 3] - far[:, 1] + 1)).sum()
+    assert len(far) == 2 and union >= 0.95 * W * H and own < 0.02 * union      # almost every thread of the launch has no dab
+    name, src, mask, out, dabs, _ = cases[IC.CHAIN_65]
+    chain = boxes(dabs)
+    assert len(dabs) == 65
+    for a, b, d in zip(chain, chain[1:], dabs[1:]):      # dab k's pixel box overlaps dab k - 1's, and its sample ring (radius > the spacing) reaches back over it
+        assert b[0] <= a[2] and b[1] <= a[3] and a[1] <= b[3] and d[3] > 3.5 + d[2]
+    step_by_step = out
+    written = np.zeros(mask.shape, bool)
+    rewritten = 0
+    for d in dabs:
+        nxt, _ = M.instant(src, mask, step_by_step, *d)
+        touched = (nxt != step_by_step).any(-1)
+        rewritten += int((touched & written).sum())
+        written |= touched
+        step_by_step = nxt
+    assert rewritten >= 20                                                      # later dabs change pixels earlier dabs wrote
+    assert not np.array_equal(step_by_step, M.instant_list(src, mask, out, dabs[::-1])[0])      # so the order matters
+
+
+EDGE_CONDITIONS = {      # hole shape -> (what must hold, spelt for the failure message; a function of the mask and the model's first peel)
+    "antidiag_band": ("more than 2 rounds of 16 waves on one anti-diagonal of the first peel",
+                      lambda mask, first, box: np.bincount([x + y for x, y in first]).max() > 2 * IC.PM_PASS_WAVES),
+    "maindiag_band": ("diagonals of one or two pixels between empty diagonals inside the box",
+                      lambda mask, first, box: np.bincount([x + y for x, y in first]).max() <= 2 and
+                      (np.bincount([x + y - box[0] - box[1] for x, y in first], minlength=box[2] + box[3] - 1) == 0).sum() >= 20),
+    "stripe": ("a first peel of more than 1024 boundary pixels", lambda mask, first, box: len(first) > IC.PM_BLOCK_THREADS),
+    "far_corners": ("more than 1024 diagonals in the box, hundreds of compaction blocks",
+                    lambda mask, first, box: box[2] + box[3] - 1 > IC.PM_BLOCK_THREADS and -(-box[2] * box[3] // IC.PM_COMPACT_ELEMS) >= 200),
+    # the peels' own compaction (over the box) takes the second turn of pm_scan_kernel, and boundary pixels get their list offsets from it: box element
+    # (y - y0) * bw + (x - x0) lies in a block at or past 1024, so a lost carry drops them onto the first hole's list entries
+    "both_corners": ("more than 1024 compaction blocks over the box and over the canvas, first-peel boundary pixels in a block at or past 1024",
+                     lambda mask, first, box: -(-box[2] * box[3] // IC.PM_COMPACT_ELEMS) > IC.PM_BLOCK_THREADS and
+                     -(-mask.size // IC.PM_COMPACT_ELEMS) > IC.PM_BLOCK_THREADS and
+                     0 < sum(((y - box[1]) * box[2] + (x - box[0])) // IC.PM_COMPACT_ELEMS >= IC.PM_BLOCK_THREADS for x, y in first) < len(first)),
+    "full_cross": ("the box is the canvas", lambda mask, first, box: box == (0, 0, mask.shape[1], mask.shape[0])),
+    "one_pixel": ("the patch is larger than the canvas", None),
+    "two_pixels": ("the patch is larger than the canvas", None),
+}
+
+
+@pytest.mark.parametrize("spec", IC.PATCHMATCH_EDGES, ids=IC.patchmatch_id)
+def test_patchmatch_edge_cases_cross_their_edges(spec):
+    (w, h), shape, content, ps, iters = spec
+    src, mask, _, _ = IC.patchmatch_case(spec)
+    img, k, trace = IC.patchmatch_expected(spec)
+    hole = mask > 0
+    ys, xs = np.nonzero(hole)
+    box = (int(xs.min()), int(ys.min()), int(xs.max() - xs.min() + 1), int(ys.max() - ys.min() + 1))      # x0, y0, bw, bh
+    first = trace[0]
+    diag = int(np.bincount([x + y for x, y in first]).max())
+    print(IC.patchmatch_id(spec), k, "hole", int(hole.sum()), "first peel", len(first), "largest diagonal", diag, "bw + bh - 1 =", box[2] + box[3] - 1,
+          "box blocks", -(-box[2] * box[3] // IC.PM_COMPACT_ELEMS), "canvas blocks", -(-w * h // IC.PM_COMPACT_ELEMS))
+    what, holds = EDGE_CONDITIONS[shape]
+    if shape in ("one_pixel", "two_pixels"):
+        assert max(ps, 3) > min(w, h), what      # no patch of the canvas is whole: every query and every candidate is clipped
+    else:
+        assert holds(mask, first, box), what
+    assert k["peels"] >= 1 and len(trace) == k["peels"] and sum(len(t) for t in trace) == int(hole.sum())
+    changed = int((img[hole] != src[hole]).any(-1).sum())
+    assert np.array_equal(img[~hole], src[~hole])
+    if spec == IC.NEVER_FILLABLE:
+        assert changed == 0 and k["unfilled"] == 1      # min_valid 30 on a canvas of 20 pixels: see inpaint_cases.NEVER_FILLABLE
+    else:
+        assert changed >= 1
+
+
+def test_patchmatch_edges_hold_what_they_are_named_for():
+    specs = IC.PATCHMATCH_EDGES
+    assert {s[3] for s in specs} >= {3, 5, 7, 9, 11} and {s[4] for s in specs} == {3, 6}
+    band = [s for s in specs if s[1] == "antidiag_band"]
+    assert {s[3] for s in band} == {5, 7} and {s[4] for s in band} == {3, 6}      # forward and backward passes alike: 2 passes and 4
+    assert len({IC.patchmatch_id(s) for s in specs} | {IC.patchmatch_id(s) for s in IC.PATCHMATCH_SWEEP}) == len(specs) + len(IC.PATCHMATCH_SWEEP)
+    tiny = [s for s in specs if s[1] in ("one_pixel", "two_pixels")]
+    assert {s[0] for s in tiny} >= {(5, 4), (3, 9)} and {s[3] for s in tiny} >= {7, 11}
+    assert any(s[3] ** 2 > 64 and s != IC.NEVER_FILLABLE for s in tiny)      # a fill through the second half of the wave's 2 x 64 patch slots
+    a, b, c = IC.GEOMETRY_SEQUENCE
+    assert a[1] == "far_corners" and b in IC.PATCHMATCH_SWEEP and c[1] == "stripe"
+    assert (IC.PM_PASS_WAVES, IC.PM_BLOCK_THREADS, IC.PM_COMPACT_ELEMS) == (16, 1024, 1024)
+
+
+def test_the_peel_trace_changes_nothing():
+    spec = IC.PATCHMATCH_SWEEP[2]
+    plain_img, plain_k = M.patchmatch(*IC.patchmatch_case(spec))
+    trace = []
+    img, k = M.patchmatch(*IC.patchmatch_case(spec), trace=trace)
+    assert np.array_equal(img, plain_img) and k == plain_k and len(trace) == k["peels"]
 
 
 def test_patchmatch_sweep_holds_what_it_is_named_for():

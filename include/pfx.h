@@ -877,6 +877,63 @@ int pfx_fill_commit_dev(pfx_ctx* ctx, void* layer_dev, const void* dist_dev, con
 int pfx_bucket_fill(pfx_ctx* ctx, uint8_t* layer_inout, uint32_t w, uint32_t h, uint32_t seed_x, uint32_t seed_y, float tolerance, const uint8_t fill[4],
                     uint8_t blend_mode, int global_fill, const uint8_t* selection /* may be NULL */);
 
+/* ================= pfx_select: selection masks, the CanvasState / tools flavour (ref: src/canvas/selection.rs:66-116, src/canvas/canvas_state.rs:1632-1887,
+ * src/ui/panels/tools/behavior/raster/perspective_gradient.rs:2-86, src/ops/adjustments.rs:1448-1591) =================
+ * Produces and edits the w*h-byte selection masks the other operators take.  Everything is integer or single-rounded f32 arithmetic: the bit-exact class.
+ * (The script flavour — select_rect, fill_selected, ... of pfx_script_execute — has other rules and is not touched by this section.)
+ *
+ * Combine rule of rectangle, ellipse and lasso (apply_selection_shape :1713, the lasso merge :40-86; one rule for every byte value of the base): where the
+ * shape covers a pixel the result is 255 (replace, add), 0 (subtract) or base (intersect); elsewhere it is base (add, subtract) or 0 (replace, intersect).
+ * combine_mode as in pfx_wand_mask: 0 replace, 1 add, 2 subtract, 3 intersect.  base_mask NULL = an all-zero base.  mask_out == base_mask (in place) is
+ * allowed; any other overlap is refused.  Every byte of mask_out is written.
+ * Refused with PFX_ERR_INVALID: combine_mode above 3, an overlap as above, a lasso coordinate that is not finite or beyond 1e9 in magnitude (the reference's
+ * sort is then order-dependent or its intermediate overflows), a feather radius that is not finite, an expand / contract radius above 46340 (the reference's
+ * i32 square overflows), a layer_dev that is not 4-byte aligned or overlaps the mask.  Refused with PFX_ERR_UNSUPPORTED: more than 8192 lasso points (one
+ * row's crossings are sorted in 32 KB of on-chip memory) and a feather radius above 512 — the reference has no cap, but its pass count is radius / 2 and a
+ * hostile radius would be billions of passes on a shared device.  Outputs are untouched on any error: every refusal comes before the first launch, and the
+ * feather runs in working memory and copies out last. */
+/* inclusive min / max (SelectionShape::Rectangle, contains :70-80, bounds :96-106): max is clamped to the canvas, min > max selects nothing (no error) */
+int pfx_select_rect(pfx_ctx* ctx, const uint8_t* base_mask /* may be NULL */, uint32_t w, uint32_t h, uint32_t min_x, uint32_t min_y, uint32_t max_x, uint32_t max_y,
+                    uint8_t combine_mode, uint8_t* mask_out);
+int pfx_select_rect_dev(pfx_ctx* ctx, const void* base_mask_dev /* may be NULL */, uint32_t w, uint32_t h, uint32_t min_x, uint32_t min_y, uint32_t max_x,
+                        uint32_t max_y, uint8_t combine_mode, void* mask_out_dev);
+/* ((x - cx) / rx)^2 + ((y - cy) / ry)^2 <= 1 in f32, one rounding per operation (contains :82-89), evaluated only inside the reference's bounding box
+ * floor(max(c - r, 0)) .. min(ceil(c + r) as u32, dim - 1) (bounds :107-113); rx <= 0 or ry <= 0 selects nothing, and so does a NaN */
+int pfx_select_ellipse(pfx_ctx* ctx, const uint8_t* base_mask /* may be NULL */, uint32_t w, uint32_t h, float cx, float cy, float rx, float ry, uint8_t combine_mode,
+                       uint8_t* mask_out);
+int pfx_select_ellipse_dev(pfx_ctx* ctx, const void* base_mask_dev /* may be NULL */, uint32_t w, uint32_t h, float cx, float cy, float rx, float ry,
+                           uint8_t combine_mode, void* mask_out_dev);
+/* the lasso's scanline fill (apply_lasso_selection :2-38): per row the crossings of y + 0.5 with the closed polygon, sorted, filled pairwise from
+ * trunc(max(n0, 0)) to trunc(max(n1 + 1, 0)) exclusive.  points_xy: n_points (x, y) pairs in HOST memory in both forms; fewer than 3 points are accepted
+ * (same arithmetic, usually an empty shape) */
+int pfx_select_lasso(pfx_ctx* ctx, const uint8_t* base_mask /* may be NULL */, uint32_t w, uint32_t h, const float* points_xy, uint32_t n_points, uint8_t combine_mode,
+                     uint8_t* mask_out);
+int pfx_select_lasso_dev(pfx_ctx* ctx, const void* base_mask_dev /* may be NULL */, uint32_t w, uint32_t h, const float* points_xy, uint32_t n_points,
+                         uint8_t combine_mode, void* mask_out_dev);
+/* translate_selection (:1677): out[x, y] = mask[x - dx, y - dy] where that is inside the image, else 0.  Not in place: any overlap is refused */
+int pfx_selection_translate(pfx_ctx* ctx, const uint8_t* mask, uint32_t w, uint32_t h, int32_t dx, int32_t dy, uint8_t* mask_out);
+int pfx_selection_translate_dev(pfx_ctx* ctx, const void* mask_dev, uint32_t w, uint32_t h, int32_t dx, int32_t dy, void* mask_out_dev);
+/* feather_selection (adjustments.rs:1448): max(trunc(radius / 2), 1) passes of a horizontal then a vertical box over [p - r, p + r] cut at the image edge,
+ * r = max(trunc(radius), 1), each `sum / count` truncating through u8 (a negative radius: r = 1, one pass).  radius at most 512 (see above).
+ * feather, expand and contract allow mask_out == mask (in place) and refuse any other overlap */
+int pfx_selection_feather(pfx_ctx* ctx, const uint8_t* mask, uint32_t w, uint32_t h, float radius, uint8_t* mask_out);
+int pfx_selection_feather_dev(pfx_ctx* ctx, const void* mask_dev, uint32_t w, uint32_t h, float radius, void* mask_out_dev);
+/* expand_selection (:1500): a pixel <= 127 becomes 255 when a pixel > 127 of the image lies within dx^2 + dy^2 <= r^2, r = max(radius, 0); others keep their value.
+ * contract_selection (:1547): a pixel != 0 becomes 0 when a pixel == 0 of the image lies within the disc; outside the image is not zero (the canvas edge does
+ * not erode).  radius at most 46340; radius <= 0 is the identity */
+int pfx_selection_expand(pfx_ctx* ctx, const uint8_t* mask, uint32_t w, uint32_t h, int32_t radius, uint8_t* mask_out);
+int pfx_selection_expand_dev(pfx_ctx* ctx, const void* mask_dev, uint32_t w, uint32_t h, int32_t radius, void* mask_out_dev);
+int pfx_selection_contract(pfx_ctx* ctx, const uint8_t* mask, uint32_t w, uint32_t h, int32_t radius, uint8_t* mask_out);
+int pfx_selection_contract_dev(pfx_ctx* ctx, const void* mask_dev, uint32_t w, uint32_t h, int32_t radius, void* mask_out_dev);
+/* selection_mask_bounds (:1632): the inclusive box x0, y0, x1, y1 of {mask != 0}, or -1, -1, -1, -1 when the mask is empty.  `box` is host memory; the call
+ * waits for the device */
+int pfx_selection_bounds_dev(pfx_ctx* ctx, const void* mask_dev, uint32_t w, uint32_t h, int32_t box[4]);
+/* fill_selected_pixels (:1844) / delete_selected_pixels (:1806) on an RGBA8 layer, in place, through a mask that may be grey: 0 leaves the pixel, 255 writes
+ * the colour (0, 0, 0, 0 for delete), otherwise t = sel / 255 and every channel becomes round(old * (1 - t) + new * t) (fill) or alpha becomes
+ * round(a * (1 - t)) with rgb kept (delete) — f32, unfused, half away from zero.  Not the script's fill_selected / delete_selected */
+int pfx_selection_fill_dev(pfx_ctx* ctx, void* layer_dev, const void* mask_dev, uint32_t w, uint32_t h, const uint8_t color[4]);
+int pfx_selection_delete_dev(pfx_ctx* ctx, void* layer_dev, const void* mask_dev, uint32_t w, uint32_t h);
+
 #ifdef __cplusplus
 }
 #endif

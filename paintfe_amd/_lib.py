@@ -97,5 +97,7 @@ def load() -> C.CDLL:
     lib.pfx_layer_count.restype = C.c_uint32
     lib.pfx_tolerance_threshold.restype = C.c_uint8
     lib.pfx_tolerance_threshold.argtypes = [C.c_float]
+    lib.pfx_int_select_span.restype = C.c_int
+    lib.pfx_int_select_span.argtypes = [C.c_uint32, C.c_uint32]
     _lib = lib
     return lib

@@ -94,6 +94,9 @@ struct pfx_ctx {
     pfx_devbuf flood_ws, flood_lut;                     // flood working memory; the 256-entry srgb_to_linear table, uploaded once (pfx_flood.cpp)
     bool flood_lut_valid = false;
     uint64_t flood_passes = 0, flood_launches = 0, flood_visits = 0;   // of the context's last pfx_flood_distance[_dev]; pfx_int_flood_last reads them
+    pfx_devbuf select_ws, select_span, select_pts;      // selection masks (pfx_select.cpp): working memory; the disc's row spans of radius select_span_r; the lasso's points
+    uint32_t select_span_r = 0;
+    uint32_t select_passes = 0, select_launches = 0;    // of the context's last feather / expand / contract; pfx_int_select_last reads them
 };
 
 // ---- error plumbing ----
@@ -194,6 +197,13 @@ extern "C" int pfx_int_inpaint_last(pfx_ctx* ctx, int which);
 // for the tests and the profile notes, what the context's last pfx_flood_distance[_dev] ran: which = 0 passes, 1 kernel launches, 2 the tile edge,
 // 3 tile visits (the lengths of the passes' tile lists, summed); -1 = unknown `which` or NULL context, counts saturate at INT_MAX (not in include/pfx.h)
 extern "C" int pfx_int_flood_last(pfx_ctx* ctx, int which);
+
+// for the tests and the profile notes, the selection kernels' shape and what the context's last feather / expand / contract ran: which = 0 the pixels of a
+// row-walking workgroup's step (a row segment is a multiple of it), 1 the rows of the feather's smallest vertical band, 2 the shape kernel's bytes per lane,
+// 3 the lasso's point cap, 4 passes, 5 kernel launches; -1 = unknown `which` or NULL context (not in include/pfx.h)
+extern "C" int pfx_int_select_last(pfx_ctx* ctx, int which);
+// floor(sqrt(r^2 - k^2)) as the grow / shrink kernels' span table holds it; -1 = k > r or r beyond the cap
+extern "C" int pfx_int_select_span(uint32_t r, uint32_t k);
 
 // blur_with_selection on device-resident images (pfx_api.cpp); mask_host may be NULL (= no selection)
 int pfx_int_blur_with_selection_dev(pfx_ctx* ctx, const void* d_src, void* d_dst, uint32_t w, uint32_t h, float sigma,

@@ -344,6 +344,32 @@ hipError_t pfxk_fill_preview(hipStream_t s, const uint8_t* d_dist, const uint8_t
 hipError_t pfxk_fill_commit(hipStream_t s, uint8_t* d_layer, const uint8_t* d_dist, const uint8_t* d_sel /* may be NULL */, size_t n, uint32_t threshold,
                             uint32_t fill_rgba, uint32_t mode);
 
+// ---- k_select.hip ---- selection masks (selection.rs, canvas_state.rs:1632-1887, perspective_gradient.rs:2-86, adjustments.rs:1448-1591); host side: pfx_select.cpp
+#define PFXK_SELECT_SEG 256           // pixels a row-walking workgroup takes per step; a row segment is pfxk_select_segment(r) of them
+#define PFXK_SELECT_BAND 32           // rows of the feather's vertical band at r <= 8; pfxk_select_band(r) beyond
+#define PFXK_SELECT_VEC 4             // mask bytes per lane of the shape kernel when base and output are that aligned
+#define PFXK_SELECT_LASSO_MAX 8192    // polygon points = the most crossings of one row: 32 KB of LDS
+#define PFXK_SELECT_FEATHER_MAX 512   // the feather's radius cap (the prefix ring of the H pass is sized for it)
+#define PFXK_SELECT_MORPH_MAX 46340   // grow / shrink: the reference's i32 r * r overflows beyond
+// a shape inside its bounding box (inclusive; x0 > x1 or y0 > y1 = empty): kind 0 rectangle, 1 ellipse ((x - cx) / rx)^2 + ((y - cy) / ry)^2 <= 1
+typedef struct pfxk_select_shape { uint32_t kind, x0, y0, x1, y1; float cx, cy, rx, ry; } pfxk_select_shape;
+// out = combine(base, shape) over every byte; mode 0 replace, 1 add, 2 subtract, 3 intersect; d_base may be NULL (all zero) or d_out itself
+hipError_t pfxk_select_shape_combine(hipStream_t s, const uint8_t* d_base, uint8_t* d_out, uint32_t w, uint32_t h, const pfxk_select_shape* S, int mode);
+// the scanline polygon fill fused with the combine rule; d_points_xy: n_points (x, y) pairs, 8-byte aligned; d_base as above
+hipError_t pfxk_select_lasso(hipStream_t s, const float* d_points_xy, uint32_t n_points, const uint8_t* d_base, uint8_t* d_out, uint32_t w, uint32_t h, int mode);
+hipError_t pfxk_select_translate(hipStream_t s, const uint8_t* d_src, uint8_t* d_out, uint32_t w, uint32_t h, int32_t dx, int32_t dy);   // not in place
+// d_box[0 .. 4) = ~min x, ~min y, max x, max y of {mask != 0} (zeroed first: ~min x == 0 means none), atomically merged
+hipError_t pfxk_select_bounds(hipStream_t s, const uint8_t* d_mask, uint32_t w, uint32_t h, uint32_t* d_box);
+hipError_t pfxk_select_fill(hipStream_t s, uint8_t* d_layer, const uint8_t* d_mask, uint32_t w, uint32_t h, uint32_t color_rgba, int erase);
+uint32_t pfxk_select_segment(uint32_t r);   // the row segment a workgroup owns at radius r: its halo of 2 r stays below half of it
+uint32_t pfxk_select_band(uint32_t r);      // likewise the band of the feather's vertical pass
+// grow (expand != 0) or shrink by the disc of radius r in 1 .. PFXK_SELECT_MORPH_MAX: d_rowdist is w * h u16 of working memory, d_span r + 1 entries
+// floor(sqrt(r^2 - k^2)); d_out may be d_mask
+hipError_t pfxk_select_morph(hipStream_t s, int expand, const uint8_t* d_mask, uint16_t* d_rowdist, const uint16_t* d_span, uint8_t* d_out, uint32_t w,
+                             uint32_t h, uint32_t r);
+// one feather pass, r in 1 .. PFXK_SELECT_FEATHER_MAX: horizontal d_src -> d_tmp, vertical d_tmp -> d_dst (d_dst may be d_src; d_tmp is neither)
+hipError_t pfxk_select_feather_pass(hipStream_t s, const uint8_t* d_src, uint8_t* d_tmp, uint8_t* d_dst, uint32_t w, uint32_t h, uint32_t r);
+
 #ifdef __cplusplus
 }
 #endif

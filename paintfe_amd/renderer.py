@@ -156,6 +156,11 @@ def tolerance_threshold(tolerance: float) -> int:
     return int(_lib.load().pfx_tolerance_threshold(C.c_float(tolerance)))
 
 
+def select_span(r: int, k: int) -> int:
+    """floor(sqrt(r^2 - k^2)), an entry of the span table the expand / contract kernels walk (-1: k > r or r above 46340); host only"""
+    return int(_lib.load().pfx_int_select_span(C.c_uint32(r), C.c_uint32(k)))
+
+
 def _flood(seed, target, distance_mode, connectivity, global_scope):
     mode = DISTANCE_MODES.index(distance_mode) if isinstance(distance_mode, str) else int(distance_mode)
     return _lib.Flood(int(seed[0]), int(seed[1]), _c4(target), mode, int(connectivity), int(bool(global_scope)), 0)
@@ -703,6 +708,90 @@ class GpuRenderer:
     def flood_last(self, which: int) -> int:
         """the last flood_distance's 0 passes, 1 kernel launches, 2 tile edge, 3 tile visits (pfx_int_flood_last; for tests and profiles)"""
         return int(self._lib.pfx_int_flood_last(self._h, C.c_int(which)))
+
+    # ------------------------------------------------------------------ selection masks (ref: canvas/selection.rs, canvas_state.rs:1632-1887, adjustments.rs:1448-1591)
+    def _select(self, fn, size, args, combine, base, out):
+        w, h = int(size[0]), int(size[1])
+        b = None if base is None else _u8(base)
+        o = np.empty((h, w), np.uint8) if out is None else out
+        self._check(fn(self._h, _p(b), C.c_uint32(w), C.c_uint32(h), *args, C.c_uint8(_enum(COMBINE_MODES, combine).value), _p(o)))
+        return o
+
+    def _select_dev(self, fn, w, h, args, combine, base_ptr, out_ptr):
+        self._check(fn(self._h, C.c_void_p(base_ptr or None), C.c_uint32(w), C.c_uint32(h), *args, C.c_uint8(_enum(COMBINE_MODES, combine).value), C.c_void_p(out_ptr)))
+
+    def select_rect(self, size, min_x: int, min_y: int, max_x: int, max_y: int, combine="replace", base=None, out=None):
+        """apply_selection_shape with a rectangle (inclusive corners) on a (w, h) canvas: the (h, w) mask; out may be `base` itself (in place)"""
+        return self._select(self._lib.pfx_select_rect, size, [C.c_uint32(v) for v in (min_x, min_y, max_x, max_y)], combine, base, out)
+
+    def select_rect_dev(self, w: int, h: int, min_x: int, min_y: int, max_x: int, max_y: int, out_ptr: int, combine="replace", base_ptr: int = 0):
+        self._select_dev(self._lib.pfx_select_rect_dev, w, h, [C.c_uint32(v) for v in (min_x, min_y, max_x, max_y)], combine, base_ptr, out_ptr)
+
+    def select_ellipse(self, size, cx: float, cy: float, rx: float, ry: float, combine="replace", base=None, out=None):
+        return self._select(self._lib.pfx_select_ellipse, size, [C.c_float(v) for v in (cx, cy, rx, ry)], combine, base, out)
+
+    def select_ellipse_dev(self, w: int, h: int, cx: float, cy: float, rx: float, ry: float, out_ptr: int, combine="replace", base_ptr: int = 0):
+        self._select_dev(self._lib.pfx_select_ellipse_dev, w, h, [C.c_float(v) for v in (cx, cy, rx, ry)], combine, base_ptr, out_ptr)
+
+    def select_lasso(self, size, points, combine="replace", base=None, out=None):
+        """apply_lasso_selection: points = (n, 2) floats, the closed polygon's (x, y) vertices"""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
+        return self._select(self._lib.pfx_select_lasso, size, [_p(pts), C.c_uint32(len(pts))], combine, base, out)
+
+    def select_lasso_dev(self, w: int, h: int, points, out_ptr: int, combine="replace", base_ptr: int = 0):
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)   # host memory in this form too
+        self._select_dev(self._lib.pfx_select_lasso_dev, w, h, [_p(pts), C.c_uint32(len(pts))], combine, base_ptr, out_ptr)
+
+    def _selection_op(self, fn, mask, arg, out):
+        m = _u8(mask)
+        h, w = m.shape[:2]
+        o = np.empty((h, w), np.uint8) if out is None else out
+        self._check(fn(self._h, _p(m), C.c_uint32(w), C.c_uint32(h), *arg, _p(o)))
+        return o
+
+    def selection_translate(self, mask, dx: int, dy: int, out=None):
+        """translate_selection: out[x, y] = mask[x - dx, y - dy] or 0; out may not be `mask`"""
+        return self._selection_op(self._lib.pfx_selection_translate, mask, [C.c_int32(dx), C.c_int32(dy)], out)
+
+    def selection_translate_dev(self, mask_ptr: int, w: int, h: int, dx: int, dy: int, out_ptr: int):
+        self._check(self._lib.pfx_selection_translate_dev(self._h, C.c_void_p(mask_ptr), C.c_uint32(w), C.c_uint32(h), C.c_int32(dx), C.c_int32(dy), C.c_void_p(out_ptr)))
+
+    def selection_feather(self, mask, radius: float, out=None):
+        """feather_selection; out may be `mask` itself (in place), as for expand and contract"""
+        return self._selection_op(self._lib.pfx_selection_feather, mask, [C.c_float(radius)], out)
+
+    def selection_feather_dev(self, mask_ptr: int, w: int, h: int, radius: float, out_ptr: int):
+        self._check(self._lib.pfx_selection_feather_dev(self._h, C.c_void_p(mask_ptr), C.c_uint32(w), C.c_uint32(h), C.c_float(radius), C.c_void_p(out_ptr)))
+
+    def selection_expand(self, mask, radius: int, out=None):
+        return self._selection_op(self._lib.pfx_selection_expand, mask, [C.c_int32(radius)], out)
+
+    def selection_expand_dev(self, mask_ptr: int, w: int, h: int, radius: int, out_ptr: int):
+        self._check(self._lib.pfx_selection_expand_dev(self._h, C.c_void_p(mask_ptr), C.c_uint32(w), C.c_uint32(h), C.c_int32(radius), C.c_void_p(out_ptr)))
+
+    def selection_contract(self, mask, radius: int, out=None):
+        return self._selection_op(self._lib.pfx_selection_contract, mask, [C.c_int32(radius)], out)
+
+    def selection_contract_dev(self, mask_ptr: int, w: int, h: int, radius: int, out_ptr: int):
+        self._check(self._lib.pfx_selection_contract_dev(self._h, C.c_void_p(mask_ptr), C.c_uint32(w), C.c_uint32(h), C.c_int32(radius), C.c_void_p(out_ptr)))
+
+    def selection_bounds_dev(self, mask_ptr: int, w: int, h: int) -> np.ndarray:
+        """selection_mask_bounds: the inclusive box x0, y0, x1, y1 of mask != 0 as a (4,) int32 array; four -1 = empty"""
+        box = np.empty(4, np.int32)
+        self._check(self._lib.pfx_selection_bounds_dev(self._h, C.c_void_p(mask_ptr), C.c_uint32(w), C.c_uint32(h), _p(box)))
+        return box
+
+    def selection_fill_dev(self, layer_ptr: int, mask_ptr: int, w: int, h: int, color):
+        """fill_selected_pixels, in place in the RGBA8 layer; color = 4 bytes"""
+        self._check(self._lib.pfx_selection_fill_dev(self._h, C.c_void_p(layer_ptr), C.c_void_p(mask_ptr), C.c_uint32(w), C.c_uint32(h), _c4(color)))
+
+    def selection_delete_dev(self, layer_ptr: int, mask_ptr: int, w: int, h: int):
+        self._check(self._lib.pfx_selection_delete_dev(self._h, C.c_void_p(layer_ptr), C.c_void_p(mask_ptr), C.c_uint32(w), C.c_uint32(h)))
+
+    def select_last(self, which: int) -> int:
+        """0 pixels per step of a row-walking workgroup, 1 rows of the feather's smallest band, 2 bytes per lane of the shape kernel, 3 the lasso's point cap,
+        4 / 5 passes / kernel launches of the last feather, expand or contract (pfx_int_select_last; for tests and profiles)"""
+        return int(self._lib.pfx_int_select_last(self._h, C.c_int(which)))
 
     # ------------------------------------------------------------------ script front-end
     def resize_image(self, img, new_w: int, new_h: int, filter="bilinear"):   # transform.rs:347 (imageops::resize)

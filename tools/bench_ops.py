@@ -196,6 +196,30 @@ def main() -> int:
     timed("fill commit (preview + blend in one kernel, multiply)", ["fill_commit"], lambda: r.fill_commit_dev(d, dp, w, h, 40, (200, 30, 60, 255), 1, m), px, 10,
           "1 + 1 B read, layer 4 B read + written where the fill lands")
     del fl, dist, bmask
+    # ---------------- selection masks (k_select.hip): an 8K mask; the disc the feather / expand / contract rows work on is a quarter of the canvas
+    yy, xx = torch.meshgrid(torch.arange(h, device=dev), torch.arange(w, device=dev), indexing="ij")
+    sel = (((xx - w // 2) ** 2 + (yy - h // 2) ** 2) <= (h // 3) ** 2).to(torch.uint8) * 255
+    del yy, xx
+    sel_out = torch.empty_like(sel)
+    sp, so = sel.data_ptr(), sel_out.data_ptr()
+    ang = np.arange(2000) * (2 * np.pi / 2000)
+    rad = np.where(np.arange(2000) % 2 == 0, 0.45, 0.25) * h
+    lasso = np.stack([w / 2 + rad * np.cos(ang), h / 2 + rad * np.sin(ang)], axis=1).astype(np.float32)
+    timed("select: rectangle, add to a base", ["select_rect"], lambda: r.select_rect_dev(w, h, w // 4, h // 4, 3 * w // 4, 3 * h // 4, so, "add", m), px, 2, "1 B read + 1 B written per pixel")
+    timed("select: ellipse, intersect with a base", ["select_ellipse"], lambda: r.select_ellipse_dev(w, h, w / 2, h / 2, w / 3, h / 3, so, "intersect", m), px, 2,
+          "two IEEE divides per pixel inside the box")
+    timed("select: lasso, 2 000-point star, replace", ["select_lasso"], lambda: r.select_lasso_dev(w, h, lasso, so), px, 1,
+          "a workgroup per row: 2 000 edges, an LDS bitonic sort of the crossings, 1 B written per pixel; the timer starts after the points' upload")
+    timed("selection: translate by (64, -3)", ["selection_translate"], lambda: r.selection_translate_dev(sp, w, h, 64, -3, so), px, 2)
+    timed("selection: feather 10 (5 passes)", ["selection_feather"], lambda: r.selection_feather_dev(sp, w, h, 10.0, so), px, 22,
+          "5 x (H + V), 1 B read + 1 B written each, + the copy out")
+    timed("selection: expand 20", ["selection_expand"], lambda: r.selection_expand_dev(sp, w, h, 20, so), px, 6,
+          "row distances: 1 B read, 2 B written and read back; the column walk reads up to 41 u16 per pixel the rule does not skip (from cache), 1 B written")
+    timed("selection: contract 20", ["selection_contract"], lambda: r.selection_contract_dev(sp, w, h, 20, so), px, 6)
+    timed("selection: bounds", ["selection_bounds"], lambda: r.selection_bounds_dev(sp, w, h), px, 1, "the call waits for the device: 16 bytes read back")
+    timed("selection: fill through a grey mask", ["selection_fill"], lambda: r.selection_fill_dev(d, sp, w, h, (200, 30, 60, 255)), px, 9, "an upper bound: 1 B read everywhere, 4 B read + written only inside the disc (0.29 of the canvas)")
+    timed("selection: delete through a grey mask", ["selection_delete"], lambda: r.selection_delete_dev(d, sp, w, h), px, 9)
+    del sel, sel_out
     src_h = src.cpu().numpy()
     import time
     r.execute_script_sync("map_channels(|r, g, b, a| [255 - r, g / 2, (b * 3 + a) / 4, a]);", src_h)   # warm: a process's first launch of k_script's code object loads it (~1 ms)

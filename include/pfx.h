@@ -934,6 +934,39 @@ int pfx_selection_bounds_dev(pfx_ctx* ctx, const void* mask_dev, uint32_t w, uin
 int pfx_selection_fill_dev(pfx_ctx* ctx, void* layer_dev, const void* mask_dev, uint32_t w, uint32_t h, const uint8_t color[4]);
 int pfx_selection_delete_dev(pfx_ctx* ctx, void* layer_dev, const void* mask_dev, uint32_t w, uint32_t h);
 
+/* ================= removal by colour: colour to alpha and the colour remover (ref: src/ops/color_removal.rs) =================
+ * The Colour to Alpha dialog (color_to_alpha_core :32-150) and the Color Remover tool, the "smart contiguous eraser" (compute_color_removal :161-418 followed
+ * by apply_color_removal :421).  Images are w*h RGBA8; masks and selections are w*h bytes, 0 = unselected, anything else = selected (the reference also takes
+ * a smaller mask; this surface does not).  Everything is in the bit-exact class: u8 -> f32, one rounding per written operation, IEEE division, round() half
+ * away from zero.  dst is src with the changed pixels replaced — the dialog's returned image, or img.clone() then apply_color_removal for the tool; every
+ * byte of dst is written.  dst == src (in place) is allowed; any other overlap of dst with src or the mask is refused.
+ * Refused with PFX_ERR_INVALID: a NULL struct, a float of either struct that is not finite, a seed outside the image (as in pfx_flood_distance; the
+ * reference ignores the click), contiguous above 1, an RGBA8 device pointer that is not 4-byte aligned, the overlaps above.  Refused with
+ * PFX_ERR_UNSUPPORTED: smoothness above 1024 — the reference has no cap, but the launch count grows with it on a shared device (the tool offers 0..20).
+ * PFX_OK with dst a copy of src, like the reference's empty change list: a seed pixel with alpha 0 (:185), a selection that is 0 at the seed (:175-181).
+ * Outputs are untouched on any error: every refusal comes before the first launch, all working memory is allocated before dst is touched, and only the last
+ * launch writes dst.  The colour remover waits for the device once for the clicked pixel and, in the contiguous scope, once per flood pass. */
+typedef struct pfx_color_to_alpha {      /* ColorToAlphaSettings :6-30; the defaults there: target 255, 0, 0; 18; 35; 1; 0.35; 0; 1; 0.15 */
+    uint8_t target[3], _pad;
+    float tolerance, softness;           /* 0..255: full removal within tolerance, fading out over softness (softness / 255 is at least 0.001) */
+    float strength, spill_suppression, alpha_floor, alpha_ceiling, protect_luminance;   /* clamped to 0..1; alpha_ceiling to alpha_floor..1 */
+} pfx_color_to_alpha;
+int pfx_color_to_alpha_core(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_t w, uint32_t h, const pfx_color_to_alpha* settings, const uint8_t* mask /* may be NULL */);
+int pfx_color_to_alpha_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, const pfx_color_to_alpha* settings, const void* mask_dev /* may be NULL */);
+/* The tool in three steps.  1, the core: contiguous = the 4-connected component of the seed over pixels that are selected and either fully transparent or
+ * within (tolerance * 2.55)^2 of the seed's rgb in squared distance (the flood runs through transparent pixels); global = every selected pixel within that
+ * distance with alpha != 0.  2, rings: `smoothness` one-pixel rings around the core, a 4-connected breadth-first dilation that never enters an unselected
+ * pixel (a geodesic distance, not a masked L1 distance).  3, colour to alpha against the seed's colour with rgb recovery, fading linearly over the rings.
+ * (The struct cannot share the entry point's name in C: it carries the reference's, ColorRemovalRequest.) */
+typedef struct pfx_color_removal_req {   /* ColorRemovalRequest, tools/state.rs:1723 */
+    uint32_t seed_x, seed_y;
+    float    tolerance;                  /* 0..100, the tool's slider; a negative value acts like its magnitude */
+    uint32_t smoothness;                 /* rings, at most 1024 */
+    uint8_t  contiguous, _pad[3];        /* 1 contiguous, 0 global scope */
+} pfx_color_removal_req;
+int pfx_color_removal(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_t w, uint32_t h, const pfx_color_removal_req* req, const uint8_t* selection /* may be NULL */);
+int pfx_color_removal_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, const pfx_color_removal_req* req, const void* selection_dev /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

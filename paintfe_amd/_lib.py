@@ -77,6 +77,16 @@ class Flood(C.Structure):   # pfx_flood
                 ("global_", C.c_uint8), ("_pad", C.c_uint8)]
 
 
+class ColorToAlpha(C.Structure):   # pfx_color_to_alpha
+    _fields_ = [("target", C.c_uint8 * 3), ("_pad", C.c_uint8), ("tolerance", C.c_float), ("softness", C.c_float), ("strength", C.c_float),
+                ("spill_suppression", C.c_float), ("alpha_floor", C.c_float), ("alpha_ceiling", C.c_float), ("protect_luminance", C.c_float)]
+
+
+class ColorRemoval(C.Structure):   # pfx_color_removal_req
+    _fields_ = [("seed_x", C.c_uint32), ("seed_y", C.c_uint32), ("tolerance", C.c_float), ("smoothness", C.c_uint32), ("contiguous", C.c_uint8),
+                ("_pad", C.c_uint8 * 3)]
+
+
 _lib = None
 
 

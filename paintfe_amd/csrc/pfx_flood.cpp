@@ -3,7 +3,8 @@
 // The host computes what is uniform over the image with the reference's own f32 expressions (no contraction): the 256-entry srgb_to_linear table (host powf,
 // uploaded once per context) and the target's linear terms.  For the contiguous scope it runs the pass loop: one 8-byte read-back per pass (how many tiles
 // the next pass visits, whether a byte decreased) ends it, as does the cap of w * h + 2 passes (DESIGN.md "Flood distance maps": an optimal path has at most
-// w * h pixels and every pass settles the next one).  The flood runs in working memory: a failed call leaves `dist` untouched.
+// w * h pixels and every pass settles the next one).  The flood runs in working memory: a failed call leaves `dist` untouched.  The pass loop itself
+// (pfx_flood_converge) takes a device cost map: the colour remover's core flood (pfx_colorkey.cpp) runs it over its passability map.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -70,6 +71,60 @@ inline int sat_int(uint64_t v) { return v > (uint64_t)INT_MAX ? INT_MAX : (int)v
 
 } // namespace
 
+// working memory, one block: 256 bytes of state (two {list length, changed} pairs, one per list) | c | d | two tile lists | the tiles' pass stamps
+int pfx_flood_work_reserve(pfx_ctx* ctx, uint32_t w, uint32_t h, pfx_flood_work* W)
+{
+    const uint32_t T = PFXK_FLOOD_TILE;
+    const size_t px = (size_t)w * h, tiles = (size_t)((w + T - 1) / T) * ((h + T - 1) / T);
+    const size_t off_c = 256, off_d = off_c + align256(px), off_l0 = off_d + align256(px), off_l1 = off_l0 + align256(tiles * 4),
+                 off_mark = off_l1 + align256(tiles * 4), total = off_mark + align256(tiles * 4);
+    PFX_TRY(pfx_reserve(ctx, ctx->flood_ws, total));
+    uint8_t* ws = (uint8_t*)ctx->flood_ws.p;
+    W->state = (uint32_t*)ws;
+    W->c = ws + off_c;
+    W->d = ws + off_d;
+    W->lists[0] = (uint32_t*)(ws + off_l0);
+    W->lists[1] = (uint32_t*)(ws + off_l1);
+    W->mark = (uint32_t*)(ws + off_mark);
+    W->tiles = tiles;
+    return PFX_OK;
+}
+
+// The pass loop over the cost map in W->c; the map ends in W->d.  Adds to the context's flood counters (the caller zeroes them).
+int pfx_flood_converge(pfx_ctx* ctx, const pfx_flood_work* W, uint32_t w, uint32_t h, uint32_t seed_x, uint32_t seed_y, int connectivity, const char* who)
+{
+    const size_t px = (size_t)w * h, tiles = W->tiles;
+    uint32_t* state = W->state;
+    uint8_t *c = W->c, *d = W->d;
+    uint32_t* const* lists = W->lists;
+    uint32_t* mark = W->mark;
+    PFX_HIP(ctx, hipMemsetAsync(d, 0xff, px, ctx->stream));
+    PFX_HIP(ctx, hipMemsetAsync(mark, 0, tiles * 4, ctx->stream));
+    PFX_HIP(ctx, pfxk_flood_seed(ctx->stream, w, seed_x, seed_y, lists[0]));
+    ctx->flood_launches += 1;
+    // Every pass but the last lowers a byte, and after pass k the first k pixels of every optimal path hold their final value (the first pass plants the seed):
+    // at most w * h + 1 passes change something.  The cap can only be met by a defect.
+    const uint64_t max_passes = (uint64_t)px + 2u;
+    uint32_t n_cur = 1;
+    for (uint64_t pass = 0;; ++pass) {
+        if (pass >= max_passes) return pfx_fail(ctx, PFX_ERR_HIP, "%s: internal error: no fixed point after %llu passes", who, (unsigned long long)pass);
+        uint32_t* st = state + 2 * ((pass + 1) & 1);
+        uint32_t got[2] = {0, 0};
+        PFX_HIP(ctx, hipMemsetAsync(st, 0, 8, ctx->stream));
+        PFX_HIP(ctx, pfxk_flood_pass(ctx->stream, connectivity, c, d, w, h, lists[pass & 1], n_cur, lists[(pass + 1) & 1], st, mark, (uint32_t)(pass + 1),
+                                     pass == 0 ? seed_x : 0xffffffffu, pass == 0 ? seed_y : 0xffffffffu));
+        PFX_TRY(pfx_d2h(ctx, got, st, sizeof got));
+        PFX_TRY(pfx_sync(ctx));
+        ctx->flood_passes += 1;
+        ctx->flood_launches += 1;
+        ctx->flood_visits += n_cur;
+        if ((size_t)got[0] > tiles) return pfx_fail(ctx, PFX_ERR_HIP, "%s: internal error: tile list overruns the tile count", who);   // cannot happen: a tile is listed once per pass
+        n_cur = got[0];
+        if (n_cur == 0 || got[1] == 0) break;   // nothing scheduled / a pass that wrote nothing
+    }
+    return PFX_OK;
+}
+
 extern "C" {
 
 uint8_t pfx_tolerance_threshold(float tolerance)
@@ -94,44 +149,13 @@ int pfx_flood_distance_dev(pfx_ctx* ctx, const void* src_dev, uint32_t w, uint32
         ctx->flood_launches = 1;
         return PFX_OK;
     }
-    // working memory, one block: 256 bytes of state (two {list length, changed} pairs, one per list) | c | d | two tile lists | the tiles' pass stamps
-    const uint32_t T = PFXK_FLOOD_TILE;
-    const size_t tiles = (size_t)((w + T - 1) / T) * ((h + T - 1) / T);
-    const size_t off_c = 256, off_d = off_c + align256(px), off_l0 = off_d + align256(px), off_l1 = off_l0 + align256(tiles * 4),
-                 off_mark = off_l1 + align256(tiles * 4), total = off_mark + align256(tiles * 4);
-    PFX_TRY(pfx_reserve(ctx, ctx->flood_ws, total));   // a failure leaves dist untouched
-    uint8_t* ws = (uint8_t*)ctx->flood_ws.p;
-    uint32_t* state = (uint32_t*)ws;
-    uint8_t *c = ws + off_c, *d = ws + off_d;
-    uint32_t* lists[2] = {(uint32_t*)(ws + off_l0), (uint32_t*)(ws + off_l1)};
-    uint32_t* mark = (uint32_t*)(ws + off_mark);
+    pfx_flood_work W;
+    PFX_TRY(pfx_flood_work_reserve(ctx, w, h, &W));   // a failure leaves dist untouched
     pfx_timer t(ctx, "flood_distance");
-    PFX_HIP(ctx, pfxk_color_distance(ctx->stream, (const uint8_t*)src_dev, c, px, flood->distance_mode, &G, table));
-    PFX_HIP(ctx, hipMemsetAsync(d, 0xff, px, ctx->stream));
-    PFX_HIP(ctx, hipMemsetAsync(mark, 0, tiles * 4, ctx->stream));
-    PFX_HIP(ctx, pfxk_flood_seed(ctx->stream, w, flood->seed_x, flood->seed_y, lists[0]));
-    ctx->flood_launches = 2;
-    // Every pass but the last lowers a byte, and after pass k the first k pixels of every optimal path hold their final value (the first pass plants the seed):
-    // at most w * h + 1 passes change something.  The cap can only be met by a defect.
-    const uint64_t max_passes = (uint64_t)px + 2u;
-    uint32_t n_cur = 1;
-    for (uint64_t pass = 0;; ++pass) {
-        if (pass >= max_passes) return pfx_fail(ctx, PFX_ERR_HIP, "pfx_flood_distance_dev: internal error: no fixed point after %llu passes", (unsigned long long)pass);
-        uint32_t* st = state + 2 * ((pass + 1) & 1);
-        uint32_t got[2] = {0, 0};
-        PFX_HIP(ctx, hipMemsetAsync(st, 0, 8, ctx->stream));
-        PFX_HIP(ctx, pfxk_flood_pass(ctx->stream, flood->connectivity, c, d, w, h, lists[pass & 1], n_cur, lists[(pass + 1) & 1], st, mark, (uint32_t)(pass + 1),
-                                     pass == 0 ? flood->seed_x : 0xffffffffu, pass == 0 ? flood->seed_y : 0xffffffffu));
-        PFX_TRY(pfx_d2h(ctx, got, st, sizeof got));
-        PFX_TRY(pfx_sync(ctx));
-        ctx->flood_passes += 1;
-        ctx->flood_launches += 1;
-        ctx->flood_visits += n_cur;
-        if ((size_t)got[0] > tiles) return pfx_fail(ctx, PFX_ERR_HIP, "pfx_flood_distance_dev: internal error: tile list overruns the tile count");   // cannot happen: a tile is listed once per pass
-        n_cur = got[0];
-        if (n_cur == 0 || got[1] == 0) break;   // nothing scheduled / a pass that wrote nothing
-    }
-    PFX_HIP(ctx, hipMemcpyAsync(dist_dev, d, px, hipMemcpyDeviceToDevice, ctx->stream));
+    PFX_HIP(ctx, pfxk_color_distance(ctx->stream, (const uint8_t*)src_dev, W.c, px, flood->distance_mode, &G, table));
+    ctx->flood_launches = 1;
+    PFX_TRY(pfx_flood_converge(ctx, &W, w, h, flood->seed_x, flood->seed_y, flood->connectivity, "pfx_flood_distance_dev"));
+    PFX_HIP(ctx, hipMemcpyAsync(dist_dev, W.d, px, hipMemcpyDeviceToDevice, ctx->stream));
     return PFX_OK;
 }
 

@@ -97,6 +97,9 @@ struct pfx_ctx {
     pfx_devbuf select_ws, select_span, select_pts;      // selection masks (pfx_select.cpp): working memory; the disc's row spans of radius select_span_r; the lasso's points
     uint32_t select_span_r = 0;
     uint32_t select_passes = 0, select_launches = 0;    // of the context's last feather / expand / contract; pfx_int_select_last reads them
+    pfx_devbuf colorkey_ws;                             // the colour remover's two u16 level maps, smoothness above one ring chunk only (pfx_colorkey.cpp)
+    uint64_t colorkey_flood_passes = 0;                 // of the context's last pfx_color_removal[_dev]; pfx_int_colorkey_last reads them
+    uint32_t colorkey_ring_launches = 0, colorkey_launches = 0;
 };
 
 // ---- error plumbing ----
@@ -194,9 +197,19 @@ int pfx_stencil_box(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w
 // for the tests and the profile notes, what the context's last pfx_inpaint_patchmatch[_dev] ran: which = 0 peels, 1 kernel launches (not in include/pfx.h)
 extern "C" int pfx_int_inpaint_last(pfx_ctx* ctx, int which);
 
-// for the tests and the profile notes, what the context's last pfx_flood_distance[_dev] ran: which = 0 passes, 1 kernel launches, 2 the tile edge,
-// 3 tile visits (the lengths of the passes' tile lists, summed); -1 = unknown `which` or NULL context, counts saturate at INT_MAX (not in include/pfx.h)
+// for the tests and the profile notes, what the context's last pfx_flood_distance[_dev] (or the contiguous pfx_color_removal[_dev], which runs the same pass
+// loop) ran: which = 0 passes, 1 kernel launches, 2 the tile edge, 3 tile visits (the lengths of the passes' tile lists, summed); -1 = unknown `which` or NULL
+// context, counts saturate at INT_MAX (not in include/pfx.h)
 extern "C" int pfx_int_flood_last(pfx_ctx* ctx, int which);
+// the connected flood's working memory carved from ctx->flood_ws, and its pass loop over a device cost map (pfx_flood.cpp): fill W->c, converge, read W->d.
+// converge adds to ctx->flood_passes / _launches / _visits; the caller zeroes them first
+struct pfx_flood_work { uint32_t* state; uint8_t *c, *d; uint32_t* lists[2]; uint32_t* mark; size_t tiles; };
+int pfx_flood_work_reserve(pfx_ctx* ctx, uint32_t w, uint32_t h, pfx_flood_work* W);
+int pfx_flood_converge(pfx_ctx* ctx, const pfx_flood_work* W, uint32_t w, uint32_t h, uint32_t seed_x, uint32_t seed_y, int connectivity, const char* who);
+
+// for the tests and the profile notes, what the context's last pfx_color_removal[_dev] ran: which = 0 flood passes (0 in the global scope), 1 ring launches,
+// 2 the ring kernel's tile edge, 3 its chunk (levels per launch), 4 kernel launches in all; -1 = unknown `which` or NULL context (not in include/pfx.h)
+extern "C" int pfx_int_colorkey_last(pfx_ctx* ctx, int which);
 
 // for the tests and the profile notes, the selection kernels' shape and what the context's last feather / expand / contract ran: which = 0 the pixels of a
 // row-walking workgroup's step (a row segment is a multiple of it), 1 the rows of the feather's smallest vertical band, 2 the shape kernel's bytes per lane,

@@ -370,6 +370,26 @@ hipError_t pfxk_select_morph(hipStream_t s, int expand, const uint8_t* d_mask, u
 // one feather pass, r in 1 .. PFXK_SELECT_FEATHER_MAX: horizontal d_src -> d_tmp, vertical d_tmp -> d_dst (d_dst may be d_src; d_tmp is neither)
 hipError_t pfxk_select_feather_pass(hipStream_t s, const uint8_t* d_src, uint8_t* d_tmp, uint8_t* d_dst, uint32_t w, uint32_t h, uint32_t r);
 
+// ---- k_colorkey.hip ---- removal by colour (src/ops/color_removal.rs): colour to alpha, and the colour remover's passability map, ring levels and write-out; host side: pfx_colorkey.cpp
+#define PFXK_COLORKEY_TILE 64              // the ring kernel's tile edge
+#define PFXK_COLORKEY_CHUNK 32             // ring levels one launch adds: the tile's halo, 128 x 128 state bytes = 16 KB of LDS
+#define PFXK_COLORKEY_MAX_SMOOTHNESS 1024  // the host's cap: 32 ring launches
+#define PFXK_COLORKEY_NONE 0xffffu         // a level map's "not reached"
+// the dialog's settings as the reference prepares them (:51-58), all in 0 .. 1 but target (0 .. 255) and target_luma
+typedef struct pfxk_cta { float target[3], tolerance, softness, strength, spill, alpha_floor, alpha_ceiling, protect, target_luma; } pfxk_cta;
+// the tool's click: the seed's colour as floats and bytes, (tolerance * 2.55)^2, smoothness and smoothness as f32 + 1.0, the scope
+typedef struct pfxk_ckey { float seed[3]; uint32_t seed_rgb; float tol_sq; uint32_t smoothness; float fade_den; uint32_t global; } pfxk_ckey;
+// color_to_alpha_core :64-133 over n pixels; d_mask may be NULL; d_dst may be d_src
+hipError_t pfxk_color_to_alpha(hipStream_t s, const uint8_t* d_src, uint8_t* d_dst, const uint8_t* d_mask, size_t n, const pfxk_cta* S);
+// c[i] = 0 where the flood may pass (selected and: alpha 0 or within the tolerance), else 255; in the global scope 0 marks the core itself (alpha 0 is not core, :249)
+hipError_t pfxk_ckey_passable(hipStream_t s, const uint8_t* d_src, const uint8_t* d_sel /* may be NULL */, uint8_t* d_out, size_t n, const pfxk_ckey* P);
+// smoothness 0: step 3 (:344-415) where d_core is 0, a copy of src elsewhere; d_dst may be d_src
+hipError_t pfxk_ckey_apply_core(hipStream_t s, const uint8_t* d_src, const uint8_t* d_core, uint8_t* d_dst, size_t n, const pfxk_ckey* P);
+// k more ring levels (1 .. PFXK_COLORKEY_CHUNK) on top of `base` known ones.  The known levels come from d_lin (u16, base > 0) or, with d_lin NULL and base 0,
+// from d_core (0 = level 0).  With d_lout the new map is written there (not d_lin); with d_lout NULL this is the last launch and step 3 writes d_dst (may be d_src)
+hipError_t pfxk_ckey_rings(hipStream_t s, const uint8_t* d_core, const uint16_t* d_lin, const uint8_t* d_sel /* may be NULL */, uint16_t* d_lout, const uint8_t* d_src,
+                           uint8_t* d_dst, uint32_t w, uint32_t h, uint32_t base, uint32_t k, const pfxk_ckey* P);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,20 @@ def _flood(seed, target, distance_mode, connectivity, global_scope):
     return _lib.Flood(int(seed[0]), int(seed[1]), _c4(target), mode, int(connectivity), int(bool(global_scope)), 0)
 
 
+def _color_to_alpha(target, tolerance, softness, strength, spill_suppression, alpha_floor, alpha_ceiling, protect_luminance):
+    s = _lib.ColorToAlpha()
+    s.target[:] = [int(v) for v in target[:3]]
+    s.tolerance, s.softness, s.strength, s.spill_suppression = tolerance, softness, strength, spill_suppression
+    s.alpha_floor, s.alpha_ceiling, s.protect_luminance = alpha_floor, alpha_ceiling, protect_luminance
+    return s
+
+
+def _color_removal(seed, tolerance, smoothness, contiguous):
+    r = _lib.ColorRemoval()
+    r.seed_x, r.seed_y, r.tolerance, r.smoothness, r.contiguous = int(seed[0]), int(seed[1]), tolerance, int(smoothness), int(contiguous)
+    return r
+
+
 def script_check(source: str, w: int = 64, h: int = 64):
     """Language-only evaluation of a script (no device, no image functions; ref: compile_script, scripting.rs:1489): returns
     the console lines or raises PfxError with .line / .col."""
@@ -792,6 +806,34 @@ class GpuRenderer:
         """0 pixels per step of a row-walking workgroup, 1 rows of the feather's smallest band, 2 bytes per lane of the shape kernel, 3 the lasso's point cap,
         4 / 5 passes / kernel launches of the last feather, expand or contract (pfx_int_select_last; for tests and profiles)"""
         return int(self._lib.pfx_int_select_last(self._h, C.c_int(which)))
+
+    # ------------------------------------------------------------------ removal by colour (ref: src/ops/color_removal.rs)
+    def color_to_alpha(self, img, target, tolerance: float = 18.0, softness: float = 35.0, strength: float = 1.0, spill_suppression: float = 0.35,
+                       alpha_floor: float = 0.0, alpha_ceiling: float = 1.0, protect_luminance: float = 0.15, mask=None, out=None):
+        """color_to_alpha_core: the image with `target` = (r, g, b) keyed out; the defaults are ColorToAlphaSettings::default()'s; out may be `img` itself"""
+        s = _color_to_alpha(target, tolerance, softness, strength, spill_suppression, alpha_floor, alpha_ceiling, protect_luminance)
+        return self._img_call(self._lib.pfx_color_to_alpha_core, img, C.byref(s), mask=mask, out=out)
+
+    def color_to_alpha_dev(self, src_ptr: int, dst_ptr: int, w: int, h: int, target, tolerance: float = 18.0, softness: float = 35.0, strength: float = 1.0,
+                           spill_suppression: float = 0.35, alpha_floor: float = 0.0, alpha_ceiling: float = 1.0, protect_luminance: float = 0.15, mask_ptr: int = 0):
+        """dst_ptr == src_ptr works in place"""
+        s = _color_to_alpha(target, tolerance, softness, strength, spill_suppression, alpha_floor, alpha_ceiling, protect_luminance)
+        self._check(self._lib.pfx_color_to_alpha_dev(self._h, C.c_void_p(src_ptr), C.c_void_p(dst_ptr), C.c_uint32(w), C.c_uint32(h), C.byref(s), C.c_void_p(mask_ptr or None)))
+
+    def color_removal(self, img, seed, tolerance: float, smoothness: int = 3, contiguous: bool = True, selection=None, out=None):
+        """compute_color_removal + apply_color_removal on a copy of `img`: the Color Remover clicked at seed = (x, y); out may be `img` itself"""
+        r = _color_removal(seed, tolerance, smoothness, contiguous)
+        return self._img_call(self._lib.pfx_color_removal, img, C.byref(r), mask=selection, out=out)
+
+    def color_removal_dev(self, src_ptr: int, dst_ptr: int, w: int, h: int, seed, tolerance: float, smoothness: int = 3, contiguous: bool = True, selection_ptr: int = 0):
+        """dst_ptr == src_ptr works in place"""
+        r = _color_removal(seed, tolerance, smoothness, contiguous)
+        self._check(self._lib.pfx_color_removal_dev(self._h, C.c_void_p(src_ptr), C.c_void_p(dst_ptr), C.c_uint32(w), C.c_uint32(h), C.byref(r), C.c_void_p(selection_ptr or None)))
+
+    def colorkey_last(self, which: int) -> int:
+        """the last color_removal's 0 flood passes, 1 ring launches, 2 the ring kernel's tile edge, 3 its chunk (levels per launch), 4 kernel launches
+        (pfx_int_colorkey_last; for tests and profiles)"""
+        return int(self._lib.pfx_int_colorkey_last(self._h, C.c_int(which)))
 
     # ------------------------------------------------------------------ script front-end
     def resize_image(self, img, new_w: int, new_h: int, filter="bilinear"):   # transform.rs:347 (imageops::resize)

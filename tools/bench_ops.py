@@ -220,6 +220,42 @@ def main() -> int:
     timed("selection: fill through a grey mask", ["selection_fill"], lambda: r.selection_fill_dev(d, sp, w, h, (200, 30, 60, 255)), px, 9, "an upper bound: 1 B read everywhere, 4 B read + written only inside the disc (0.29 of the canvas)")
     timed("selection: delete through a grey mask", ["selection_delete"], lambda: r.selection_delete_dev(d, sp, w, h), px, 9)
     del sel, sel_out
+    # ---------------- removal by colour (k_colorkey.hip): colour to alpha is a streaming pass like HSL; the colour remover is the passability map, the connected
+    # flood's passes (contiguous scope) and ceil(smoothness / 32) ring launches, the last one writing the image.  The HSL row and the bucket tool's flood of the
+    # same image are repeated under this section's name so that one `--only colorkey` run holds them side by side
+    timed("colorkey: colour to alpha, defaults", ["color_to_alpha"], lambda: r.color_to_alpha_dev(s, d, w, h, (128, 128, 128)), px, 8, "up to five IEEE divisions per changed pixel")
+    timed("colorkey: colour to alpha, masked", ["color_to_alpha"], lambda: r.color_to_alpha_dev(s, d, w, h, (128, 128, 128), mask_ptr=m), px, 9)
+    timed("colorkey orientation: hsl(30,-20,10)", ["adjust"], lambda: r.adjust_dev(s, d, w, h, "hsl", [30.0, -20.0, 10.0]), px, 8, "the same 8 B/px")
+    ck = torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
+    ckd = torch.empty((h, w), dtype=torch.uint8, device=dev)
+
+    def build_ck_photo():   # smooth ramps of a few units per hundred pixels under +-4 noise: a tolerance cuts ragged regions, the rings have an edge to follow
+        yy, xx = torch.meshgrid(torch.arange(h, device=dev), torch.arange(w, device=dev), indexing="ij")
+        base = torch.stack([120 + 40 * torch.sin(xx / 900.0) * torch.cos(yy / 700.0), 110 + 50 * torch.cos(xx / 1300.0 + yy / 500.0), 90 + 30 * torch.sin((xx + yy) / 1100.0)], dim=2)
+        ck[..., :3] = (base + torch.randint(-4, 5, (h, w, 3), device=dev, generator=g)).clamp(0, 255).to(torch.uint8)
+        ck[..., 3] = 255
+
+    def build_ck_uniform():
+        ck[...] = torch.tensor(grey, dtype=torch.uint8, device=dev)
+
+    for image, build in (("photo-like", build_ck_photo), ("uniform", build_ck_uniform)):
+        if args.only and "colorkey" not in args.only:   # the images cost more than a skipped row
+            break
+        build()
+        torch.cuda.synchronize()
+        seed_px = tuple(int(v) for v in ck[h // 2, w // 2].tolist())
+        flood = lambda: r.flood_distance_dev(ck.data_ptr(), w, h, (w // 2, h // 2), seed_px, ckd.data_ptr(), "legacy", 4, False)
+        flood()
+        timed(f"colorkey orientation: bucket tool's connected flood, {image}", ["flood_distance"], flood, px, 5, reps=3, warm=False,
+              note=f"the flood of profiles/flood.md on this image from its centre: {r.flood_last(0)} passes, {r.flood_last(3)} tile visits (it floods on a 0..255 distance, the remover on passable / not)")
+        for contiguous in (True, False):
+            for smooth in (0, 3, 20, 64):
+                run = lambda: r.color_removal_dev(ck.data_ptr(), d, w, h, (w // 2, h // 2), 8.0, smooth, contiguous)
+                run()
+                timed(f"colorkey: remover, {image}, {'contiguous' if contiguous else 'global'}, smoothness {smooth}", ["color_removal"], run, px, 14, reps=3, warm=False,
+                      note=f"seed at the centre, tolerance 8: {r.colorkey_last(0)} flood passes, {r.colorkey_last(1)} ring launches, {r.colorkey_last(4)} launches; 14 B/px = the map (4 + 1) "
+                           f"and the last launch (1 + 4 + 4), the flood's and the earlier ring launches' traffic not counted; the timer starts after the seed's read-back; mean of 3 calls")
+    del ck, ckd
     src_h = src.cpu().numpy()
     import time
     r.execute_script_sync("map_channels(|r, g, b, a| [255 - r, g / 2, (b * 3 + a) / 4, a]);", src_h)   # warm: a process's first launch of k_script's code object loads it (~1 ms)

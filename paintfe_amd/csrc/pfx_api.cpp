@@ -19,59 +19,35 @@ static_assert((int)PFX_ADJ_CHANNEL_MIXER == (int)PFXK_ADJ_CHANNEL_MIXER, "layer 
 
 namespace {
 
-inline size_t img_bytes(uint32_t w, uint32_t h) { return (size_t)w * h * 4; }
-
 // FAST instantiation of the compositor (k_flatten.hip): requires opacity.clamp(0,1) in [2^-40, 1] for every layer, so
 // that (a) every division operand of blend_pixel_static stays in the normal range where v_div_scale / v_div_fixup
 // are identities and (b) top_a > 0 for every non-skipped pixel (out_a > 0: no zero check, no clamp).  Anything else
 // (zero, negative, tiny or NaN opacity) runs the plain instantiation with IEEE '/', clamps and zero checks.
 inline bool opacity_allows_fast_div(float opacity) { return opacity >= 9.094947017729282e-13f; /* 2^-40 */ }
 
-int check_img(pfx_ctx* ctx, const void* src, const void* dst, uint32_t w, uint32_t h, const char* who)
+// The filter family's declaration: a w x h src and dst.  In a `_dev` call dst shares no byte with src — a kernel that reads a halo while other workgroups write
+// the same memory would race silently — unless the header allows in place (same_ok) and the two are the same pointer; the host tier works on staged copies.
+// The mask is not declared: these calls have never looked at where it lies.
+int check_img(pfx_ctx* ctx, const char* who, bool dev, const void* src, const void* dst, uint32_t w, uint32_t h, bool same_ok = false)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    if (!src || !dst) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: null image pointer", who);
-    if (w == 0 || h == 0) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: zero-sized image", who);
-    if ((uint64_t)w * h > 256000000ull) // TiledImage::new clamps beyond 256 M px (ref: tiled_image.rs:15-26)
-        return pfx_fail(ctx, PFX_ERR_INVALID, "%s: %ux%u exceeds the 256 Mpx document limit", who, w, h);
-    return pfx_use(ctx);
+    PFX_TRY(pfx_check_dims(ctx, who, w, h));
+    return pfx_check_args(ctx, who, dev, {{src, pfx_img_bytes(w, h), PFX_ARG_IN, "src"}, {dst, pfx_img_bytes(w, h), dev ? PFX_ARG_OUT : PFX_ARG_STAGED_OUT, "dst"}},
+                          same_ok ? src : nullptr);
+}
+// the same for a call that works in one image (the selection is not declared either)
+int check_inout(pfx_ctx* ctx, const char* who, const void* pixels, uint32_t w, uint32_t h)
+{
+    PFX_TRY(pfx_check_dims(ctx, who, w, h));
+    return pfx_check_args(ctx, who, false, {{pixels, pfx_img_bytes(w, h), PFX_ARG_OUT, "the image"}});
 }
 
-// Aliasing rule of the `_dev` entry points (include/pfx.h): src == dst is allowed where the header says so; buffers that overlap in
-// any other way, or at all for a neighbourhood operation, are refused — a kernel that reads a halo while other workgroups write the
-// same memory would race silently.
-int check_disjoint(pfx_ctx* ctx, const void* src, const void* dst, uint32_t w, uint32_t h, const char* who, bool same_ok = false)
-{
-    if (src == dst) return same_ok ? PFX_OK : pfx_fail(ctx, PFX_ERR_INVALID, "%s: src and dst must be different buffers", who);
-    if (pfx_ranges_overlap(src, img_bytes(w, h), dst, img_bytes(w, h))) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: src and dst overlap", who);
-    return PFX_OK;
-}
-// the same for a source whose extent differs from the destination's (the warps sample an sw x sh image into a w x h one)
-int check_disjoint2(pfx_ctx* ctx, const void* src, uint32_t sw, uint32_t sh, const void* dst, uint32_t w, uint32_t h, const char* who)
-{
-    if (pfx_ranges_overlap(src, img_bytes(sw, sh), dst, img_bytes(w, h))) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: src and dst overlap", who);
-    return PFX_OK;
-}
-
-// stage host src (+ optional mask) into the context's device buffers
+// the filter family's staging: src in st_in, room for dst in st_out, the optional mask in st_mask
 int stage_in(pfx_ctx* ctx, const uint8_t* src, const uint8_t* mask, uint32_t w, uint32_t h, const void** d_mask)
 {
-    PFX_TRY(pfx_reserve(ctx, ctx->st_in, img_bytes(w, h)));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_out, img_bytes(w, h)));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_in.p, src, img_bytes(w, h)));
-    *d_mask = nullptr;
-    if (mask) {
-        PFX_TRY(pfx_reserve(ctx, ctx->st_mask, (size_t)w * h));
-        PFX_TRY(pfx_h2d(ctx, ctx->st_mask.p, mask, (size_t)w * h));
-        *d_mask = ctx->st_mask.p;
-    }
-    return PFX_OK;
-}
-
-int finish_out(pfx_ctx* ctx, uint8_t* dst, uint32_t w, uint32_t h)
-{
-    PFX_TRY(pfx_d2h(ctx, dst, ctx->st_out.p, img_bytes(w, h)));
-    return pfx_sync(ctx);
+    void* d;
+    PFX_TRY(pfx_stage(ctx, ctx->st_in, src, pfx_img_bytes(w, h), &d));
+    PFX_TRY(pfx_stage(ctx, ctx->st_out, nullptr, pfx_img_bytes(w, h), &d));
+    return pfx_stage_opt(ctx, ctx->st_mask, mask, (size_t)w * h, d_mask);
 }
 
 // host-side parameter preparation for the pointwise bank: everything that is uniform per call is folded here with
@@ -281,7 +257,7 @@ int flatten_common(pfx_ctx* ctx, const void* const* layer_ptrs, const void* cons
     // a workgroup would read pixels another one has already replaced
     if (!from_store && layer_ptrs && dst_dev)
         for (uint32_t l = 0; l < n_layers; ++l)
-            if (layer_ptrs[l] && layer_ptrs[l] != dst_dev && pfx_ranges_overlap(layer_ptrs[l], img_bytes(w, h), dst_dev, img_bytes(w, h)))
+            if (layer_ptrs[l] && layer_ptrs[l] != dst_dev && pfx_ranges_overlap(layer_ptrs[l], pfx_img_bytes(w, h), dst_dev, pfx_img_bytes(w, h)))
                 return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_flatten_dev: dst partially overlaps layer %u (it may be a layer, or disjoint from all)", l);
     uint32_t n_desc = 0, active_pos = 0xFFFFFFFFu;
     const uint8_t* active_pixels = nullptr;
@@ -399,6 +375,16 @@ int flatten_common(pfx_ctx* ctx, const void* const* layer_ptrs, const void* cons
     return PFX_OK;
 }
 
+// the displacement warp's declaration: an sw x sh source sampled into a w x h output through a w x h field.  The SOURCE's extent counts, it may be larger
+// than the output; the field is only required (these calls have never looked at where it lies)
+int check_warp(pfx_ctx* ctx, const char* who, bool dev, const void* src, uint32_t sw, uint32_t sh, const void* disp, uint32_t w, uint32_t h, const void* dst)
+{
+    PFX_TRY(pfx_check_dims(ctx, who, w, h));
+    PFX_TRY(pfx_check_dims(ctx, who, sw, sh));
+    return pfx_check_args(ctx, who, dev, {{src, pfx_img_bytes(sw, sh), PFX_ARG_IN, "src"}, {disp, 0, PFX_ARG_IN, "the displacement field"},
+                                          {dst, pfx_img_bytes(w, h), dev ? PFX_ARG_OUT : PFX_ARG_STAGED_OUT, "dst"}});
+}
+
 int brush_prepare(pfx_ctx* ctx, const pfx_brush* b, pfxk_brush& B, bool& skip)
 {
     PFX_REQUIRE(ctx, b != nullptr, "null brush");
@@ -456,8 +442,7 @@ int pfx_gaussian_blur_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint
 int pfx_gaussian_blur_band_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, float sigma, void* tmp_dev,
                                uint32_t first_row)
 {
-    PFX_TRY(check_img(ctx, src_dev, dst_dev, w, h, "pfx_gaussian_blur_dev"));
-    PFX_TRY(check_disjoint(ctx, src_dev, dst_dev, w, h, "pfx_gaussian_blur_dev", true)); // in place: the two-pass kernels (through tmp)
+    PFX_TRY(check_img(ctx, "pfx_gaussian_blur_dev", true, src_dev, dst_dev, w, h, true)); // in place: the two-pass kernels (through tmp)
     PFX_REQUIRE(ctx, (uint64_t)first_row + h <= 0x7fffffffull, "pfx_gaussian_blur_band_dev: band outside any image");   // the kernels carry image rows in 32-bit signed integers
     return pfx_gauss_blur(ctx, ctx->exact, src_dev, dst_dev, w, h, sigma, tmp_dev, first_row);   // which kernels run: pfx_gauss.cpp
 }
@@ -465,10 +450,9 @@ int pfx_gaussian_blur_band_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev,
 int pfx_box_blur_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, float radius,
                      const void* mask_dev, void* tmp_dev)
 {
-    PFX_TRY(check_img(ctx, src_dev, dst_dev, w, h, "pfx_box_blur_dev"));
-    PFX_TRY(check_disjoint(ctx, src_dev, dst_dev, w, h, "pfx_box_blur_dev", true));
+    PFX_TRY(check_img(ctx, "pfx_box_blur_dev", true, src_dev, dst_dev, w, h, true));
     if (radius < 0.5f) { // blur.rs:234: returns flat.clone()
-        PFX_HIP(ctx, hipMemcpyAsync(dst_dev, src_dev, img_bytes(w, h), hipMemcpyDeviceToDevice, ctx->stream));
+        PFX_HIP(ctx, hipMemcpyAsync(dst_dev, src_dev, pfx_img_bytes(w, h), hipMemcpyDeviceToDevice, ctx->stream));
         return PFX_OK;
     }
     const float rc = ceilf(radius);
@@ -492,8 +476,7 @@ int pfx_median_band_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32
 
 int pfx_median_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, uint32_t radius, const void* mask_dev)
 {
-    PFX_TRY(check_img(ctx, src_dev, dst_dev, w, h, "pfx_median_dev"));
-    PFX_TRY(check_disjoint(ctx, src_dev, dst_dev, w, h, "pfx_median_dev"));
+    PFX_TRY(check_img(ctx, "pfx_median_dev", true, src_dev, dst_dev, w, h));
     const uint32_t r = std::max(radius, 1u); // noise.rs:364
     if (r > PFX_MEDIAN_MAX_RADIUS) return pfx_fail(ctx, PFX_ERR_UNSUPPORTED, "median radius %u > %d", r, PFX_MEDIAN_MAX_RADIUS);
     return pfx_stencil_median(ctx, src_dev, dst_dev, w, h, (int)r, mask_dev);   // which kernel runs: pfx_stencil.cpp
@@ -501,8 +484,7 @@ int pfx_median_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w,
 
 int pfx_pixelate_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, uint32_t block_size, const void* mask_dev)
 {
-    PFX_TRY(check_img(ctx, src_dev, dst_dev, w, h, "pfx_pixelate_dev"));
-    PFX_TRY(check_disjoint(ctx, src_dev, dst_dev, w, h, "pfx_pixelate_dev"));
+    PFX_TRY(check_img(ctx, "pfx_pixelate_dev", true, src_dev, dst_dev, w, h));
     pfx_timer t(ctx, "pixelate");
     PFX_HIP(ctx, pfxk_pixelate(ctx->stream, (const uint8_t*)src_dev, (uint8_t*)dst_dev, (const uint8_t*)mask_dev,
                                std::max(block_size, 2u), w, h)); // distort.rs:334
@@ -512,8 +494,7 @@ int pfx_pixelate_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t 
 int pfx_adjust_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, int op, const float* params,
                    uint32_t n_params, const uint8_t* lut_host, const void* mask_dev, int sparse_mode)
 {
-    PFX_TRY(check_img(ctx, src_dev, dst_dev, w, h, "pfx_adjust_dev"));
-    PFX_TRY(check_disjoint(ctx, src_dev, dst_dev, w, h, "pfx_adjust_dev", true)); // in place is fine (pointwise); a partial overlap races
+    PFX_TRY(check_img(ctx, "pfx_adjust_dev", true, src_dev, dst_dev, w, h, true)); // in place is fine (pointwise); a partial overlap races
     PFX_REQUIRE(ctx, sparse_mode >= PFX_DENSE && sparse_mode <= PFX_IN_PLACE, "unknown sparse mode");
     pfxk_params P;
     bool needs_lut = false;
@@ -560,7 +541,7 @@ static int prepare_rhai(pfx_ctx* ctx, int op, const float* p, uint32_t n, pfxk_p
 
 int pfx_rhai_adjust_dev(pfx_ctx* ctx, void* pixels_dev, uint32_t w, uint32_t h, int op, const float* p, uint32_t n)
 {
-    PFX_TRY(check_img(ctx, pixels_dev, pixels_dev, w, h, "pfx_rhai_adjust_dev"));
+    PFX_TRY(check_inout(ctx, "pfx_rhai_adjust_dev", pixels_dev, w, h));
     pfxk_params P;
     uint8_t lut[256];
     bool needs_lut = false;
@@ -613,10 +594,9 @@ static int chain_prepare(pfx_ctx* ctx, const pfx_chain_op* ops, uint32_t first, 
 
 int pfx_chain_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, const pfx_chain_op* ops, uint32_t n_ops)
 {
-    PFX_TRY(check_img(ctx, src_dev, dst_dev, w, h, "pfx_chain_dev"));
-    PFX_TRY(check_disjoint(ctx, src_dev, dst_dev, w, h, "pfx_chain_dev", true));
+    PFX_TRY(check_img(ctx, "pfx_chain_dev", true, src_dev, dst_dev, w, h, true));
     PFX_REQUIRE(ctx, ops != nullptr || n_ops == 0, "pfx_chain_dev: null op list");
-    const size_t bytes = img_bytes(w, h);
+    const size_t bytes = pfx_img_bytes(w, h);
     // stages: [stencil op +] a run of pointwise ops that one launch can carry (PFXK_CHAIN_MAX ops, PFXK_CHAIN_LUTS tables)
     std::vector<chain_stage> stages;
     uint32_t n_stencil = 0;
@@ -686,10 +666,8 @@ int pfx_chain_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, 
 int pfx_warp_displacement_band_dev(pfx_ctx* ctx, const void* src_dev, uint32_t sw, uint32_t sh, const void* disp_band_dev, uint32_t w,
                                    uint32_t band_rows, void* dst_band_dev, uint32_t first_row)
 {
-    PFX_TRY(check_img(ctx, src_dev, dst_band_dev, w, band_rows, "pfx_warp_displacement_dev"));
-    PFX_REQUIRE(ctx, disp_band_dev && pfx_dims_ok(sw, sh), "pfx_warp_displacement_dev: bad arguments");
+    PFX_TRY(check_warp(ctx, "pfx_warp_displacement_dev", true, src_dev, sw, sh, disp_band_dev, w, band_rows, dst_band_dev));
     PFX_REQUIRE(ctx, (uint64_t)first_row + band_rows <= 0x7fffffffull, "pfx_warp_displacement_dev: band outside any image");
-    PFX_TRY(check_disjoint2(ctx, src_dev, sw, sh, dst_band_dev, w, band_rows, "pfx_warp_displacement_dev")); // the SOURCE's extent: it may be larger than the output
     pfx_timer t(ctx, "warp_displacement");
     PFX_HIP(ctx, pfxk_warp_displacement(ctx->stream, (const uint8_t*)src_dev, sw, sh, (const float*)disp_band_dev, w, band_rows, (uint8_t*)dst_band_dev, first_row));
     return PFX_OK;
@@ -705,9 +683,9 @@ int pfx_warp_displacement_dev(pfx_ctx* ctx, const void* src_dev, uint32_t sw, ui
 // the reference computes it (transform.rs:1056-1069), accumulation in k_warp.hip
 int pfx_displacement_brushes_dev(pfx_ctx* ctx, void* disp_dev, uint32_t w, uint32_t h, const pfx_disp_dab* dabs, uint32_t n_dabs)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, disp_dev && w && h && (uint64_t)w * h <= 256000000ull && (n_dabs == 0 || dabs), "pfx_displacement_brushes_dev: bad arguments");
-    PFX_TRY(pfx_use(ctx));
+    PFX_TRY(pfx_check_dims(ctx, "pfx_displacement_brushes_dev", w, h));
+    PFX_TRY(pfx_check_args(ctx, "pfx_displacement_brushes_dev", true, {{disp_dev, (size_t)w * h * 8, PFX_ARG_OUT, "disp_dev"}}));
+    PFX_REQUIRE(ctx, n_dabs == 0 || dabs, "pfx_displacement_brushes_dev: null dab list");
     if (n_dabs == 0) return PFX_OK;
     auto f2i = [](float v) -> int32_t { return v != v ? 0 : (v >= 2147483648.0f ? 2147483647 : (v <= -2147483648.0f ? (-2147483647 - 1) : (int32_t)v)); };
     std::vector<pfxk_disp_dab> k(n_dabs);
@@ -779,9 +757,8 @@ static int upload_points(pfx_ctx* ctx, const float* orig, const float* def, uint
 int pfx_mesh_displacement_dev(pfx_ctx* ctx, const float* orig_pts_xy, const float* deformed_pts_xy, uint32_t cols, uint32_t rows,
                               uint32_t w, uint32_t h, void* disp_dev)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, disp_dev && pfx_dims_ok(w, h), "pfx_mesh_displacement_dev: bad arguments");
-    PFX_TRY(pfx_use(ctx));
+    PFX_TRY(pfx_check_dims(ctx, "pfx_mesh_displacement_dev", w, h));
+    PFX_TRY(pfx_check_args(ctx, "pfx_mesh_displacement_dev", true, {{disp_dev, (size_t)w * h * 8, PFX_ARG_OUT, "disp_dev"}}));
     const float *d_orig, *d_def;
     PFX_TRY(upload_points(ctx, orig_pts_xy, deformed_pts_xy, cols, rows, &d_orig, &d_def));
     pfx_timer t(ctx, "mesh_displacement");
@@ -792,9 +769,9 @@ int pfx_mesh_displacement_dev(pfx_ctx* ctx, const float* orig_pts_xy, const floa
 int pfx_warp_mesh_catmull_rom_band_dev(pfx_ctx* ctx, const void* src_dev, const float* orig_pts_xy, const float* deformed_pts_xy,
                                        uint32_t cols, uint32_t rows, uint32_t w, uint32_t h, void* dst_band_dev, uint32_t first_row, uint32_t band_rows)
 {
-    PFX_TRY(check_img(ctx, src_dev, dst_band_dev, w, h, "pfx_warp_mesh_catmull_rom_dev"));
+    PFX_TRY(pfx_check_dims(ctx, "pfx_warp_mesh_catmull_rom_dev", w, h));
+    PFX_TRY(pfx_check_args(ctx, "pfx_warp_mesh_catmull_rom_dev", true, {{src_dev, pfx_img_bytes(w, h), PFX_ARG_IN, "src"}, {dst_band_dev, pfx_img_bytes(w, band_rows), PFX_ARG_OUT, "dst"}}));
     PFX_REQUIRE(ctx, band_rows >= 1 && (uint64_t)first_row + band_rows <= h, "pfx_warp_mesh_catmull_rom_dev: band outside the image");
-    PFX_REQUIRE(ctx, !pfx_ranges_overlap(src_dev, (size_t)w * h * 4, dst_band_dev, (size_t)w * band_rows * 4), "pfx_warp_mesh_catmull_rom_dev: src and dst overlap");
     const float *d_orig, *d_def;
     PFX_TRY(upload_points(ctx, orig_pts_xy, deformed_pts_xy, cols, rows, &d_orig, &d_def));
     pfx_timer t(ctx, "warp_mesh");
@@ -812,8 +789,7 @@ int pfx_warp_mesh_catmull_rom_dev(pfx_ctx* ctx, const void* src_dev, const float
 // computes scatter, colour jitter and tip rotation on the CPU once per stamp; so does this, then the stamp list goes to the kernel.
 static uint32_t stamp_hash(float x, float y, uint32_t counter) // :846-857
 {
-    auto u = [](float v) -> uint32_t { return !(v > 0.0f) ? 0u : (v >= 4294967296.0f ? 0xffffffffu : (uint32_t)v); };
-    uint32_t hsh = u(x * 100.0f) * 374761393u + u(y * 100.0f) * 668265263u + counter * 1013904223u;
+    uint32_t hsh = pfx_f32_as_u32(x * 100.0f) * 374761393u + pfx_f32_as_u32(y * 100.0f) * 668265263u + counter * 1013904223u;
     hsh ^= hsh >> 13;
     hsh *= 1274126177u;
     hsh ^= hsh >> 16;
@@ -852,7 +828,7 @@ static void host_hsl_to_rgb(float hh, float s, float l, float& r, float& g, floa
 int pfx_brush_stamps_ex_dev(pfx_ctx* ctx, void* target_dev, uint32_t w, uint32_t h, const pfx_brush* brush, const pfx_brush_dynamics* dyn,
                             const float* points_xy, uint32_t n_points, const void* selection_dev)
 {
-    PFX_TRY(check_img(ctx, target_dev, target_dev, w, h, "pfx_brush_stamps_dev"));
+    PFX_TRY(check_inout(ctx, "pfx_brush_stamps_dev", target_dev, w, h));
     if (n_points == 0) return PFX_OK;
     PFX_REQUIRE(ctx, points_xy != nullptr, "null stamp list");
     const bool image_tip = dyn && dyn->tip_mask;
@@ -915,15 +891,14 @@ int pfx_brush_stamps_ex_dev(pfx_ctx* ctx, void* target_dev, uint32_t w, uint32_t
         // the stamp's pixel box, with the reference's float operations (:209-215 round tip, :584-587 image tip; `as u32` saturates, NaN -> 0): the kernel tests
         // pixels against it and the binning below deals the stamp to the chunks it touches
         {
-            auto f2u = [](float v) -> uint32_t { return (v > 0.0f) ? ((v >= 4294967296.0f) ? 0xffffffffu : (uint32_t)v) : 0u; };
             const uint32_t wm1 = w - 1u, hm1 = h - 1u;
             if (image_tip) {
                 const float eh = S.rotated ? half * 1.41421356237309504880f : half;
-                S.x0 = f2u(fmaxf(S.cx - eh, 0.0f)); S.y0 = f2u(fmaxf(S.cy - eh, 0.0f));
-                S.x1 = std::min(f2u(S.cx + eh), wm1); S.y1 = std::min(f2u(S.cy + eh), hm1);
+                S.x0 = pfx_f32_as_u32(fmaxf(S.cx - eh, 0.0f)); S.y0 = pfx_f32_as_u32(fmaxf(S.cy - eh, 0.0f));
+                S.x1 = std::min(pfx_f32_as_u32(S.cx + eh), wm1); S.y1 = std::min(pfx_f32_as_u32(S.cy + eh), hm1);
             } else {
-                S.x0 = f2u(fmaxf(floorf(S.cx - B.draw_radius), 0.0f)); S.x1 = std::min(f2u(ceilf(S.cx + B.draw_radius)), wm1);
-                S.y0 = f2u(fmaxf(floorf(S.cy - B.draw_radius), 0.0f)); S.y1 = std::min(f2u(ceilf(S.cy + B.draw_radius)), hm1);
+                S.x0 = pfx_f32_as_u32(fmaxf(floorf(S.cx - B.draw_radius), 0.0f)); S.x1 = std::min(pfx_f32_as_u32(ceilf(S.cx + B.draw_radius)), wm1);
+                S.y0 = pfx_f32_as_u32(fmaxf(floorf(S.cy - B.draw_radius), 0.0f)); S.y1 = std::min(pfx_f32_as_u32(ceilf(S.cy + B.draw_radius)), hm1);
             }
             if (S.x0 > S.x1 || S.y0 > S.y1) { S.x0 = 1u; S.x1 = 0u; S.y0 = 1u; S.y1 = 0u; }   // touches no pixel
             S.pad[0] = S.pad[1] = 0u;
@@ -1010,8 +985,7 @@ int pfx_brush_stamps_dev(pfx_ctx* ctx, void* target_dev, uint32_t w, uint32_t h,
 
 int pfx_tiled_roundtrip_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h)
 {
-    PFX_TRY(check_img(ctx, src_dev, dst_dev, w, h, "pfx_tiled_roundtrip_dev"));
-    PFX_TRY(check_disjoint(ctx, src_dev, dst_dev, w, h, "pfx_tiled_roundtrip_dev", true));
+    PFX_TRY(check_img(ctx, "pfx_tiled_roundtrip_dev", true, src_dev, dst_dev, w, h, true));
     pfx_timer t(ctx, "tiled_roundtrip");
     PFX_HIP(ctx, pfxk_tiled_roundtrip(ctx->stream, (const uint8_t*)src_dev, (uint8_t*)dst_dev, w, h));
     return PFX_OK;
@@ -1020,11 +994,11 @@ int pfx_tiled_roundtrip_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, ui
 // ======================================================================= host-buffer tier
 int pfx_gaussian_blur_core(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_t w, uint32_t h, float sigma, const uint8_t* mask)
 {
-    PFX_TRY(check_img(ctx, src, dst, w, h, "pfx_gaussian_blur_core"));
+    PFX_TRY(check_img(ctx, "pfx_gaussian_blur_core", false, src, dst, w, h));
     const void* d_mask;
     PFX_TRY(stage_in(ctx, src, mask, w, h, &d_mask));
     PFX_TRY(pfx_int_blur_with_selection_dev(ctx, ctx->st_in.p, ctx->st_out.p, w, h, sigma, mask, d_mask));
-    return finish_out(ctx, dst, w, h);
+    return pfx_unstage(ctx, dst, ctx->st_out, pfx_img_bytes(w, h));
 }
 
 } // extern "C"
@@ -1055,22 +1029,22 @@ int pfx_int_blur_with_selection_dev(pfx_ctx* ctx, const void* d_src, void* d_dst
             min_y = std::min(min_y, y); max_y = std::max(max_y, y);
         }
         if (min_x > max_x || min_y > max_y) { // nothing selected: flat.clone()
-            PFX_HIP(ctx, hipMemcpyAsync(out.p, in.p, img_bytes(w, h), hipMemcpyDeviceToDevice, ctx->stream));
+            PFX_HIP(ctx, hipMemcpyAsync(out.p, in.p, pfx_img_bytes(w, h), hipMemcpyDeviceToDevice, ctx->stream));
         } else {
             const float padf = ceilf(sigma * 3.0f);
-            const uint32_t pad = !(padf > 0.0f) ? 0u : (padf >= 4294967296.0f ? 0xffffffffu : (uint32_t)padf);
+            const uint32_t pad = pfx_f32_as_u32(padf);
             const uint32_t cx0 = min_x > pad ? min_x - pad : 0, cy0 = min_y > pad ? min_y - pad : 0;
             const uint32_t cx1 = (uint32_t)std::min<uint64_t>((uint64_t)max_x + 1 + pad, w);
             const uint32_t cy1 = (uint32_t)std::min<uint64_t>((uint64_t)max_y + 1 + pad, h);
             const uint32_t cw = cx1 - cx0, ch = cy1 - cy0;
-            PFX_TRY(pfx_reserve(ctx, ctx->st_aux, img_bytes(cw, ch)));
-            PFX_TRY(pfx_reserve(ctx, ctx->st_aux2, img_bytes(w, h)));
+            PFX_TRY(pfx_reserve(ctx, ctx->st_aux, pfx_img_bytes(cw, ch)));
+            PFX_TRY(pfx_reserve(ctx, ctx->st_aux2, pfx_img_bytes(w, h)));
             PFX_HIP(ctx, hipMemcpy2DAsync(ctx->st_aux.p, (size_t)cw * 4, (const uint8_t*)in.p + ((size_t)cy0 * w + cx0) * 4,
                                           (size_t)w * 4, (size_t)cw * 4, ch, hipMemcpyDeviceToDevice, ctx->stream));
             // blurred crop -> st_aux2 (the H pass reads its source while the V pass writes the destination)
             PFX_TRY(pfx_gaussian_blur_dev(ctx, ctx->st_aux.p, ctx->st_aux2.p, cw, ch, sigma, nullptr));
             // paste the blurred crop over a copy of the source, then select by mask
-            PFX_HIP(ctx, hipMemcpyAsync(out.p, in.p, img_bytes(w, h), hipMemcpyDeviceToDevice, ctx->stream));
+            PFX_HIP(ctx, hipMemcpyAsync(out.p, in.p, pfx_img_bytes(w, h), hipMemcpyDeviceToDevice, ctx->stream));
             PFX_HIP(ctx, hipMemcpy2DAsync((uint8_t*)out.p + ((size_t)cy0 * w + cx0) * 4, (size_t)w * 4, ctx->st_aux2.p,
                                           (size_t)cw * 4, (size_t)cw * 4, ch, hipMemcpyDeviceToDevice, ctx->stream));
             PFX_HIP(ctx, pfxk_select_by_mask(ctx->stream, (const uint8_t*)in.p, (const uint8_t*)out.p,
@@ -1089,20 +1063,20 @@ int pfx_blur_rgba(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_t w, ui
 
 int pfx_box_blur_core(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_t w, uint32_t h, float radius, const uint8_t* mask)
 {
-    PFX_TRY(check_img(ctx, src, dst, w, h, "pfx_box_blur_core"));
+    PFX_TRY(check_img(ctx, "pfx_box_blur_core", false, src, dst, w, h));
     const void* d_mask;
     PFX_TRY(stage_in(ctx, src, mask, w, h, &d_mask));
     PFX_TRY(pfx_box_blur_dev(ctx, ctx->st_in.p, ctx->st_out.p, w, h, radius, d_mask, nullptr));
-    return finish_out(ctx, dst, w, h);
+    return pfx_unstage(ctx, dst, ctx->st_out, pfx_img_bytes(w, h));
 }
 
 int pfx_median_core(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_t w, uint32_t h, uint32_t radius, const uint8_t* mask)
 {
-    PFX_TRY(check_img(ctx, src, dst, w, h, "pfx_median_core"));
+    PFX_TRY(check_img(ctx, "pfx_median_core", false, src, dst, w, h));
     const void* d_mask;
     PFX_TRY(stage_in(ctx, src, mask, w, h, &d_mask));
     PFX_TRY(pfx_median_dev(ctx, ctx->st_in.p, ctx->st_out.p, w, h, radius, d_mask));
-    return finish_out(ctx, dst, w, h);
+    return pfx_unstage(ctx, dst, ctx->st_out, pfx_img_bytes(w, h));
 }
 
 int pfx_median_rgba(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_t w, uint32_t h, uint32_t radius)
@@ -1112,21 +1086,21 @@ int pfx_median_rgba(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_t w, 
 
 int pfx_pixelate_core(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_t w, uint32_t h, uint32_t block_size, const uint8_t* mask)
 {
-    PFX_TRY(check_img(ctx, src, dst, w, h, "pfx_pixelate_core"));
+    PFX_TRY(check_img(ctx, "pfx_pixelate_core", false, src, dst, w, h));
     const void* d_mask;
     PFX_TRY(stage_in(ctx, src, mask, w, h, &d_mask));
     PFX_TRY(pfx_pixelate_dev(ctx, ctx->st_in.p, ctx->st_out.p, w, h, block_size, d_mask));
-    return finish_out(ctx, dst, w, h);
+    return pfx_unstage(ctx, dst, ctx->st_out, pfx_img_bytes(w, h));
 }
 
 int pfx_adjust(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_t w, uint32_t h, int op, const float* params,
                uint32_t n_params, const uint8_t* lut, const uint8_t* mask, int sparse_mode)
 {
-    PFX_TRY(check_img(ctx, src, dst, w, h, "pfx_adjust"));
+    PFX_TRY(check_img(ctx, "pfx_adjust", false, src, dst, w, h));
     const void* d_mask;
     PFX_TRY(stage_in(ctx, src, mask, w, h, &d_mask));
     PFX_TRY(pfx_adjust_dev(ctx, ctx->st_in.p, ctx->st_out.p, w, h, op, params, n_params, lut, d_mask, sparse_mode));
-    return finish_out(ctx, dst, w, h);
+    return pfx_unstage(ctx, dst, ctx->st_out, pfx_img_bytes(w, h));
 }
 
 int pfx_brightness_contrast_rgba(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_t w, uint32_t h, float brightness, float contrast)
@@ -1148,17 +1122,16 @@ int pfx_invert_rgba(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_t w, 
 
 int pfx_rhai_adjust(pfx_ctx* ctx, uint8_t* pixels_inout, uint32_t w, uint32_t h, int op, const float* params, uint32_t n_params)
 {
-    PFX_TRY(check_img(ctx, pixels_inout, pixels_inout, w, h, "pfx_rhai_adjust"));
-    const void* d_mask;
-    PFX_TRY(stage_in(ctx, pixels_inout, nullptr, w, h, &d_mask));
-    PFX_TRY(pfx_rhai_adjust_dev(ctx, ctx->st_in.p, w, h, op, params, n_params));
-    PFX_TRY(pfx_d2h(ctx, pixels_inout, ctx->st_in.p, img_bytes(w, h)));
-    return pfx_sync(ctx);
+    PFX_TRY(check_inout(ctx, "pfx_rhai_adjust", pixels_inout, w, h));
+    void* d_pixels;
+    PFX_TRY(pfx_stage(ctx, ctx->st_in, pixels_inout, pfx_img_bytes(w, h), &d_pixels));
+    PFX_TRY(pfx_rhai_adjust_dev(ctx, d_pixels, w, h, op, params, n_params));
+    return pfx_unstage(ctx, pixels_inout, ctx->st_in, pfx_img_bytes(w, h));
 }
 
 int pfx_auto_levels(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_t w, uint32_t h, const uint8_t* mask)
 {
-    PFX_TRY(check_img(ctx, src, dst, w, h, "pfx_auto_levels"));
+    PFX_TRY(check_img(ctx, "pfx_auto_levels", false, src, dst, w, h));
     const void* d_mask;
     PFX_TRY(stage_in(ctx, src, mask, w, h, &d_mask));
     PFX_TRY(pfx_reserve(ctx, ctx->d_misc, 64));
@@ -1174,7 +1147,7 @@ int pfx_auto_levels(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_t w, 
     for (int i = 0; i < 256; ++i) luts[768 + i] = (uint8_t)i;
     // auto_levels writes through from_rgba_image (adjustments.rs:230-232) => FROM_FLAT
     PFX_TRY(pfx_adjust_dev(ctx, ctx->st_in.p, ctx->st_out.p, w, h, PFX_OP_LUT_RGBA, nullptr, 0, luts, d_mask, PFX_FROM_FLAT));
-    return finish_out(ctx, dst, w, h);
+    return pfx_unstage(ctx, dst, ctx->st_out, pfx_img_bytes(w, h));
 }
 
 int pfx_composite_region(pfx_ctx* ctx, uint32_t w, uint32_t h, const pfx_layer_info* layers, uint32_t n_layers, uint32_t x,
@@ -1183,10 +1156,10 @@ int pfx_composite_region(pfx_ctx* ctx, uint32_t w, uint32_t h, const pfx_layer_i
     if (!ctx) return PFX_ERR_INVALID;
     PFX_REQUIRE(ctx, dst_region && pfx_dims_ok(w, h) && pfx_rect_inside(x, y, rw, rh, w, h), "pfx_composite: bad arguments");
     PFX_TRY(pfx_use(ctx));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_out, img_bytes(w, h)));
+    PFX_TRY(pfx_reserve(ctx, ctx->st_out, pfx_img_bytes(w, h)));
     if (rw == w && rh == h) {
         PFX_TRY(flatten_common(ctx, nullptr, nullptr, layers, n_layers, w, h, true, ctx->st_out.p));
-        return finish_out(ctx, dst_region, w, h);
+        return pfx_unstage(ctx, dst_region, ctx->st_out, pfx_img_bytes(w, h));
     }
     // dirty rectangle (composite_dirty_readback, renderer.rs:588): only its pixels are composited, into a compact rw x rh image
     const pfxk_region rg{x, y, rw, rh};
@@ -1210,18 +1183,18 @@ int pfx_composite_preview(pfx_ctx* ctx, uint32_t w, uint32_t h, const pfx_layer_
     PFX_REQUIRE(ctx, preview != nullptr, "pfx_composite_preview: null preview description");
     PFX_TRY(pfx_use(ctx));
     const size_t nchunks = (size_t)((w + 63) / 64) * ((h + 63) / 64);
-    PFX_TRY(pfx_reserve(ctx, ctx->st_out, img_bytes(w, h)));
-    PFX_TRY(pfx_reserve(ctx, ctx->fx_b, img_bytes(w, h) + nchunks));
-    PFX_TRY(pfx_h2d(ctx, ctx->fx_b.p, preview_pixels, img_bytes(w, h)));
+    PFX_TRY(pfx_reserve(ctx, ctx->st_out, pfx_img_bytes(w, h)));
+    PFX_TRY(pfx_reserve(ctx, ctx->fx_b, pfx_img_bytes(w, h) + nchunks));
+    PFX_TRY(pfx_h2d(ctx, ctx->fx_b.p, preview_pixels, pfx_img_bytes(w, h)));
     preview_arg pv;
     pv.d_pixels = ctx->fx_b.p;
     if (preview_chunk_present) {
-        PFX_TRY(pfx_h2d(ctx, (uint8_t*)ctx->fx_b.p + img_bytes(w, h), preview_chunk_present, nchunks));
-        pv.d_chunk_present = (const uint8_t*)ctx->fx_b.p + img_bytes(w, h);
+        PFX_TRY(pfx_h2d(ctx, (uint8_t*)ctx->fx_b.p + pfx_img_bytes(w, h), preview_chunk_present, nchunks));
+        pv.d_chunk_present = (const uint8_t*)ctx->fx_b.p + pfx_img_bytes(w, h);
     }
     pv.info = *preview;
     PFX_TRY(flatten_common(ctx, nullptr, nullptr, layers, n_layers, w, h, true, ctx->st_out.p, &pv));
-    return finish_out(ctx, dst, w, h);
+    return pfx_unstage(ctx, dst, ctx->st_out, pfx_img_bytes(w, h));
 }
 
 int pfx_flatten_preview_dev(pfx_ctx* ctx, const void* const* layer_ptrs_dev, const void* const* mask_ptrs_dev, const pfx_layer_info* layers,
@@ -1240,43 +1213,38 @@ int pfx_flatten_preview_dev(pfx_ctx* ctx, const void* const* layer_ptrs_dev, con
 
 int pfx_blend_pixels(pfx_ctx* ctx, const uint8_t* base, const uint8_t* top, uint8_t* dst, size_t n_pixels, uint8_t blend_mode, float opacity)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, base && top && dst && n_pixels, "pfx_blend_pixels: bad arguments");
-    PFX_TRY(pfx_use(ctx));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_in, n_pixels * 4));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_aux, n_pixels * 4));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_out, n_pixels * 4));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_in.p, base, n_pixels * 4));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_aux.p, top, n_pixels * 4));
-    PFX_HIP(ctx, pfxk_blend_arrays(ctx->stream, (const uint8_t*)ctx->st_in.p, (const uint8_t*)ctx->st_aux.p, (uint8_t*)ctx->st_out.p,
-                                   n_pixels, blend_mode > 24 ? 0u : blend_mode, opacity, opacity_allows_fast_div(opacity) ? 1 : 0));
-    PFX_TRY(pfx_d2h(ctx, dst, ctx->st_out.p, n_pixels * 4));
-    return pfx_sync(ctx);
+    const size_t bytes = n_pixels * 4;
+    PFX_TRY(pfx_check_args(ctx, "pfx_blend_pixels", false, {{base, bytes, PFX_ARG_IN, "base"}, {top, bytes, PFX_ARG_IN, "top"}, {dst, bytes, PFX_ARG_STAGED_OUT, "dst"}}));
+    PFX_REQUIRE(ctx, n_pixels, "pfx_blend_pixels: no pixels");
+    void *d_base, *d_top, *d_dst;
+    PFX_TRY(pfx_stage(ctx, ctx->st_in, base, bytes, &d_base));
+    PFX_TRY(pfx_stage(ctx, ctx->st_aux, top, bytes, &d_top));
+    PFX_TRY(pfx_stage(ctx, ctx->st_out, nullptr, bytes, &d_dst));
+    PFX_HIP(ctx, pfxk_blend_arrays(ctx->stream, (const uint8_t*)d_base, (const uint8_t*)d_top, (uint8_t*)d_dst, n_pixels, blend_mode > 24 ? 0u : blend_mode, opacity,
+                                   opacity_allows_fast_div(opacity) ? 1 : 0));
+    return pfx_unstage(ctx, dst, ctx->st_out, bytes);
 }
 
 int pfx_warp_displacement(pfx_ctx* ctx, const uint8_t* src, uint32_t sw, uint32_t sh, const float* disp_xy, uint32_t w, uint32_t h, uint8_t* dst)
 {
-    PFX_TRY(check_img(ctx, src, dst, w, h, "pfx_warp_displacement"));
-    PFX_REQUIRE(ctx, disp_xy && pfx_dims_ok(sw, sh), "pfx_warp_displacement: bad arguments");
-    PFX_TRY(pfx_reserve(ctx, ctx->st_in, img_bytes(sw, sh)));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_out, img_bytes(w, h)));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_tmp, (size_t)w * h * 8));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_in.p, src, img_bytes(sw, sh)));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_tmp.p, disp_xy, (size_t)w * h * 8));
-    PFX_TRY(pfx_warp_displacement_dev(ctx, ctx->st_in.p, sw, sh, ctx->st_tmp.p, w, h, ctx->st_out.p));
-    return finish_out(ctx, dst, w, h);
+    PFX_TRY(check_warp(ctx, "pfx_warp_displacement", false, src, sw, sh, disp_xy, w, h, dst));
+    void *d_src, *d_disp, *d_dst;
+    PFX_TRY(pfx_stage(ctx, ctx->st_in, src, pfx_img_bytes(sw, sh), &d_src));
+    PFX_TRY(pfx_stage(ctx, ctx->st_out, nullptr, pfx_img_bytes(w, h), &d_dst));
+    PFX_TRY(pfx_stage(ctx, ctx->st_tmp, disp_xy, (size_t)w * h * 8, &d_disp));
+    PFX_TRY(pfx_warp_displacement_dev(ctx, d_src, sw, sh, d_disp, w, h, d_dst));
+    return pfx_unstage(ctx, dst, ctx->st_out, pfx_img_bytes(w, h));
 }
 
 // GpuLiquifyPipeline keeps the source texture across warp_into calls until invalidate_source (ref: src/gpu/compute/liquify.rs:166-176):
 // an interactive Liquify session re-sends only the displacement field
 int pfx_warp_set_source(pfx_ctx* ctx, const uint8_t* src, uint32_t sw, uint32_t sh)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, src && pfx_dims_ok(sw, sh), "pfx_warp_set_source: bad arguments");
-    PFX_TRY(pfx_use(ctx));
+    PFX_TRY(pfx_check_dims(ctx, "pfx_warp_set_source", sw, sh));
+    PFX_TRY(pfx_check_args(ctx, "pfx_warp_set_source", false, {{src, pfx_img_bytes(sw, sh), PFX_ARG_IN, "src"}}));
     ctx->warp_src_w = ctx->warp_src_h = 0;
-    PFX_TRY(pfx_reserve(ctx, ctx->warp_src, img_bytes(sw, sh)));
-    PFX_TRY(pfx_h2d(ctx, ctx->warp_src.p, src, img_bytes(sw, sh)));
+    PFX_TRY(pfx_reserve(ctx, ctx->warp_src, pfx_img_bytes(sw, sh)));
+    PFX_TRY(pfx_h2d(ctx, ctx->warp_src.p, src, pfx_img_bytes(sw, sh)));
     PFX_TRY(pfx_sync(ctx)); // the host buffer may be released after the call
     ctx->warp_src_w = sw; ctx->warp_src_h = sh;
     return PFX_OK;
@@ -1291,49 +1259,46 @@ int pfx_warp_invalidate_source(pfx_ctx* ctx)
 
 int pfx_warp_displacement_cached(pfx_ctx* ctx, const float* disp_xy, uint32_t w, uint32_t h, uint8_t* dst)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, disp_xy && dst && pfx_dims_ok(w, h), "pfx_warp_displacement_cached: bad arguments");
+    PFX_TRY(pfx_check_dims(ctx, "pfx_warp_displacement_cached", w, h));
+    PFX_TRY(pfx_check_args(ctx, "pfx_warp_displacement_cached", false, {{disp_xy, 0, PFX_ARG_IN, "disp_xy"}, {dst, pfx_img_bytes(w, h), PFX_ARG_STAGED_OUT, "dst"}}));
     PFX_REQUIRE(ctx, ctx->warp_src_w != 0, "pfx_warp_displacement_cached: no source (pfx_warp_set_source, or it was invalidated)");
-    PFX_TRY(pfx_use(ctx));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_out, img_bytes(w, h)));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_tmp, (size_t)w * h * 8));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_tmp.p, disp_xy, (size_t)w * h * 8));
-    PFX_TRY(pfx_warp_displacement_dev(ctx, ctx->warp_src.p, ctx->warp_src_w, ctx->warp_src_h, ctx->st_tmp.p, w, h, ctx->st_out.p));
-    return finish_out(ctx, dst, w, h);
+    void *d_disp, *d_dst;
+    PFX_TRY(pfx_stage(ctx, ctx->st_out, nullptr, pfx_img_bytes(w, h), &d_dst));
+    PFX_TRY(pfx_stage(ctx, ctx->st_tmp, disp_xy, (size_t)w * h * 8, &d_disp));
+    PFX_TRY(pfx_warp_displacement_dev(ctx, ctx->warp_src.p, ctx->warp_src_w, ctx->warp_src_h, d_disp, w, h, d_dst));
+    return pfx_unstage(ctx, dst, ctx->st_out, pfx_img_bytes(w, h));
 }
 
 int pfx_mesh_displacement(pfx_ctx* ctx, const float* orig_pts_xy, const float* deformed_pts_xy, uint32_t cols, uint32_t rows,
                           uint32_t w, uint32_t h, float* disp_xy_out)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, disp_xy_out && pfx_dims_ok(w, h), "pfx_mesh_displacement: bad arguments");
-    PFX_TRY(pfx_use(ctx));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_tmp, (size_t)w * h * 8));
-    PFX_TRY(pfx_mesh_displacement_dev(ctx, orig_pts_xy, deformed_pts_xy, cols, rows, w, h, ctx->st_tmp.p));
-    PFX_TRY(pfx_d2h(ctx, disp_xy_out, ctx->st_tmp.p, (size_t)w * h * 8));
-    return pfx_sync(ctx);
+    PFX_TRY(pfx_check_dims(ctx, "pfx_mesh_displacement", w, h));
+    PFX_TRY(pfx_check_args(ctx, "pfx_mesh_displacement", false, {{disp_xy_out, (size_t)w * h * 8, PFX_ARG_STAGED_OUT, "disp_xy_out"}}));
+    void* d_disp;
+    PFX_TRY(pfx_stage(ctx, ctx->st_tmp, nullptr, (size_t)w * h * 8, &d_disp));
+    PFX_TRY(pfx_mesh_displacement_dev(ctx, orig_pts_xy, deformed_pts_xy, cols, rows, w, h, d_disp));
+    return pfx_unstage(ctx, disp_xy_out, ctx->st_tmp, (size_t)w * h * 8);
 }
 
 int pfx_warp_mesh_catmull_rom(pfx_ctx* ctx, const uint8_t* src, const float* orig_pts_xy, const float* deformed_pts_xy,
                               uint32_t cols, uint32_t rows, uint32_t w, uint32_t h, uint8_t* dst)
 {
-    PFX_TRY(check_img(ctx, src, dst, w, h, "pfx_warp_mesh_catmull_rom"));
+    PFX_TRY(check_img(ctx, "pfx_warp_mesh_catmull_rom", false, src, dst, w, h));
     PFX_REQUIRE(ctx, orig_pts_xy != nullptr, "warp_mesh_catmull_rom needs the original grid (transform.rs:1743)");
     const void* d_mask;
     PFX_TRY(stage_in(ctx, src, nullptr, w, h, &d_mask));
     PFX_TRY(pfx_warp_mesh_catmull_rom_dev(ctx, ctx->st_in.p, orig_pts_xy, deformed_pts_xy, cols, rows, w, h, ctx->st_out.p));
-    return finish_out(ctx, dst, w, h);
+    return pfx_unstage(ctx, dst, ctx->st_out, pfx_img_bytes(w, h));
 }
 
 int pfx_brush_stamps_ex(pfx_ctx* ctx, uint8_t* target_inout, uint32_t w, uint32_t h, const pfx_brush* brush, const pfx_brush_dynamics* dyn,
                         const float* points_xy, uint32_t n_points, const uint8_t* selection)
 {
-    PFX_TRY(check_img(ctx, target_inout, target_inout, w, h, "pfx_brush_stamps"));
+    PFX_TRY(check_inout(ctx, "pfx_brush_stamps", target_inout, w, h));
     const void* d_sel;
     PFX_TRY(stage_in(ctx, target_inout, selection, w, h, &d_sel));
     PFX_TRY(pfx_brush_stamps_ex_dev(ctx, ctx->st_in.p, w, h, brush, dyn, points_xy, n_points, d_sel));
-    PFX_TRY(pfx_d2h(ctx, target_inout, ctx->st_in.p, img_bytes(w, h)));
-    return pfx_sync(ctx);
+    return pfx_unstage(ctx, target_inout, ctx->st_in, pfx_img_bytes(w, h));
 }
 
 int pfx_brush_stamps(pfx_ctx* ctx, uint8_t* target_inout, uint32_t w, uint32_t h, const pfx_brush* brush, const float* points_xy,
@@ -1345,7 +1310,7 @@ int pfx_brush_stamps(pfx_ctx* ctx, uint8_t* target_inout, uint32_t w, uint32_t h
 int pfx_brush_line_ex(pfx_ctx* ctx, uint8_t* target_inout, uint32_t w, uint32_t h, const pfx_brush* brush, const pfx_brush_dynamics* dyn, float x0,
                       float y0, float x1, float y1, const uint8_t* selection)
 {
-    PFX_TRY(check_img(ctx, target_inout, target_inout, w, h, "pfx_brush_line"));   // before the "no stamps" early return: bad arguments are bad whatever the line
+    PFX_TRY(check_inout(ctx, "pfx_brush_line", target_inout, w, h));   // before the "no stamps" early return: bad arguments are bad whatever the line
     PFX_REQUIRE(ctx, brush != nullptr, "pfx_brush_line: null brush");
     std::vector<float> pts;
     pfx_host_line_points(x0, y0, x1, y1, w, h, pts);
@@ -1363,14 +1328,13 @@ int pfx_brush_line(pfx_ctx* ctx, uint8_t* target_inout, uint32_t w, uint32_t h, 
 uint32_t pfx_brush_tip_rescale(const uint8_t* src, uint32_t src_size, float brush_size, float hardness, uint8_t* out)
 {
     if (!src || !out || src_size == 0) return 0;
-    auto u32 = [](float v) -> uint32_t { return !(v > 0.0f) ? 0u : (v >= 4294967296.0f ? 0xffffffffu : (uint32_t)v); };
     auto u8 = [](float v) -> uint8_t { return !(v > 0.0f) ? 0 : (v >= 255.0f ? 255 : (uint8_t)(int)v); };
-    const uint32_t dst = std::max(u32(ceilf(brush_size)), 1u);
+    const uint32_t dst = std::max(pfx_f32_as_u32(ceilf(brush_size)), 1u);
     const float scale = (float)src_size / (float)dst;
     for (uint32_t dy = 0; dy < dst; ++dy)
         for (uint32_t dx = 0; dx < dst; ++dx) {
             const float sx = (float)dx * scale, sy = (float)dy * scale;
-            const uint32_t sx0 = u32(floorf(sx)), sy0 = u32(floorf(sy));
+            const uint32_t sx0 = pfx_f32_as_u32(floorf(sx)), sy0 = pfx_f32_as_u32(floorf(sy));
             const uint32_t sx1 = std::min(sx0 + 1, src_size - 1), sy1 = std::min(sy0 + 1, src_size - 1);
             const float fx = sx - (float)sx0, fy = sy - (float)sy0;
             const float v00 = src[sy0 * src_size + sx0], v10 = src[sy0 * src_size + sx1], v01 = src[sy1 * src_size + sx0], v11 = src[sy1 * src_size + sx1];
@@ -1409,36 +1373,35 @@ uint32_t pfx_brush_tip_rescale(const uint8_t* src, uint32_t src_size, float brus
 int pfx_brush_commit(pfx_ctx* ctx, uint8_t* layer_inout, const uint8_t* preview, uint32_t w, uint32_t h, uint8_t blend_mode,
                      int is_eraser, const uint8_t* selection)
 {
-    PFX_TRY(check_img(ctx, layer_inout, layer_inout, w, h, "pfx_brush_commit"));
-    PFX_REQUIRE(ctx, preview != nullptr, "null preview");
+    PFX_TRY(pfx_check_dims(ctx, "pfx_brush_commit", w, h));
+    PFX_TRY(pfx_check_args(ctx, "pfx_brush_commit", false, {{layer_inout, pfx_img_bytes(w, h), PFX_ARG_STAGED_OUT, "layer_inout"}, {preview, pfx_img_bytes(w, h), PFX_ARG_IN, "preview"}}));
     const void* d_sel;
     PFX_TRY(stage_in(ctx, layer_inout, selection, w, h, &d_sel));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_out.p, preview, img_bytes(w, h)));
+    PFX_TRY(pfx_h2d(ctx, ctx->st_out.p, preview, pfx_img_bytes(w, h)));
     PFX_HIP(ctx, pfxk_brush_commit(ctx->stream, (uint8_t*)ctx->st_in.p, (const uint8_t*)ctx->st_out.p, (const uint8_t*)d_sel, w, h,
                                    blend_mode > 24 ? 0u : blend_mode, is_eraser));
-    PFX_TRY(pfx_d2h(ctx, layer_inout, ctx->st_in.p, img_bytes(w, h)));
-    return pfx_sync(ctx);
+    return pfx_unstage(ctx, layer_inout, ctx->st_in, pfx_img_bytes(w, h));
 }
 
 int pfx_tiled_roundtrip(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_t w, uint32_t h)
 {
-    PFX_TRY(check_img(ctx, src, dst, w, h, "pfx_tiled_roundtrip"));
+    PFX_TRY(check_img(ctx, "pfx_tiled_roundtrip", false, src, dst, w, h));
     const void* d_mask;
     PFX_TRY(stage_in(ctx, src, nullptr, w, h, &d_mask));
     PFX_TRY(pfx_tiled_roundtrip_dev(ctx, ctx->st_in.p, ctx->st_out.p, w, h));
-    return finish_out(ctx, dst, w, h);
+    return pfx_unstage(ctx, dst, ctx->st_out, pfx_img_bytes(w, h));
 }
 
 int pfx_chunk_populated(pfx_ctx* ctx, const uint8_t* src, uint32_t w, uint32_t h, uint8_t* populated)
 {
-    PFX_TRY(check_img(ctx, src, populated, w, h, "pfx_chunk_populated"));
-    const void* d_mask;
-    PFX_TRY(stage_in(ctx, src, nullptr, w, h, &d_mask));
+    PFX_TRY(pfx_check_dims(ctx, "pfx_chunk_populated", w, h));
     const size_t nchunks = (size_t)((w + 63) / 64) * ((h + 63) / 64);
-    PFX_TRY(pfx_reserve(ctx, ctx->d_chunks, nchunks));
-    PFX_HIP(ctx, pfxk_chunk_populated(ctx->stream, (const uint8_t*)ctx->st_in.p, w, h, (uint8_t*)ctx->d_chunks.p));
-    PFX_TRY(pfx_d2h(ctx, populated, ctx->d_chunks.p, nchunks));
-    return pfx_sync(ctx);
+    PFX_TRY(pfx_check_args(ctx, "pfx_chunk_populated", false, {{src, pfx_img_bytes(w, h), PFX_ARG_IN, "src"}, {populated, nchunks, PFX_ARG_STAGED_OUT, "populated"}}));
+    void *d_src, *d_chunks;
+    PFX_TRY(pfx_stage(ctx, ctx->st_in, src, pfx_img_bytes(w, h), &d_src));
+    PFX_TRY(pfx_stage(ctx, ctx->d_chunks, nullptr, nchunks, &d_chunks));
+    PFX_HIP(ctx, pfxk_chunk_populated(ctx->stream, (const uint8_t*)d_src, w, h, (uint8_t*)d_chunks));
+    return pfx_unstage(ctx, populated, ctx->d_chunks, nchunks);
 }
 
 int pfx_tune(pfx_ctx* ctx, const char* key, int value)

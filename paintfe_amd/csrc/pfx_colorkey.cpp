@@ -5,28 +5,21 @@
 // it — then launches: the passability map, the connected flood's passes (contiguous scope only; pfx_flood_converge, one 8-byte read-back per pass), and
 // ceil(smoothness / 32) ring launches, the last of which writes dst (smoothness 0: one streaming launch).  All working memory is reserved before the first
 // launch, and nothing but the last launch (or the no-op's copy) writes dst: a failed call leaves it untouched.
-#include <climits>
 #include <cmath>
 
 #include "pfx_internal.h"
 
 namespace {
 
-inline size_t align256(size_t n) { return (n + 255u) & ~(size_t)255u; }
 inline float clampf(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }   // f32::clamp for finite arguments
-inline int sat_int(uint64_t v) { return v > (uint64_t)INT_MAX ? INT_MAX : (int)v; }
 
 // what the four entry points share: dst == src (in place) is allowed, any other overlap of dst with src or the mask is refused
 int check_images(pfx_ctx* ctx, const void* src, const void* dst, const void* mask, const void* params, uint32_t w, uint32_t h, bool dev, const char* who)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    if (!pfx_dims_ok(w, h)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: bad image size %ux%u", who, w, h);
-    if (!src || !dst || !params) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: null pointer", who);
+    PFX_TRY(pfx_check_dims(ctx, who, w, h));
     const size_t px = (size_t)w * h;
-    if (dev && (((uintptr_t)src | (uintptr_t)dst) & 3u)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: an RGBA8 device pointer is not 4-byte aligned", who);   // the kernels read a pixel as one dword
-    if (dst != src && pfx_ranges_overlap(dst, px * 4, src, px * 4)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: dst overlaps src (other than in place)", who);
-    if (mask && pfx_ranges_overlap(dst, px * 4, mask, px)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: dst overlaps the mask", who);
-    return PFX_OK;
+    return pfx_check_args(ctx, who, dev, {{src, px * 4, PFX_ARG_DWORD, "src"}, {dst, px * 4, PFX_ARG_OUT | PFX_ARG_DWORD, "dst"},
+                                          {mask, px, PFX_ARG_OPTIONAL, "the mask"}, {params, 0, PFX_ARG_IN, "the settings"}}, src);
 }
 
 int check_settings(pfx_ctx* ctx, const pfx_color_to_alpha* s, const char* who)
@@ -70,7 +63,6 @@ int pfx_color_to_alpha_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uin
 {
     PFX_TRY(check_images(ctx, src_dev, dst_dev, mask_dev, settings, w, h, true, "pfx_color_to_alpha_dev"));
     PFX_TRY(check_settings(ctx, settings, "pfx_color_to_alpha_dev"));
-    PFX_TRY(pfx_use(ctx));
     const pfxk_cta S = prepare_settings(settings);
     pfx_timer t(ctx, "color_to_alpha");
     PFX_HIP(ctx, pfxk_color_to_alpha(ctx->stream, (const uint8_t*)src_dev, (uint8_t*)dst_dev, (const uint8_t*)mask_dev, (size_t)w * h, &S));
@@ -81,15 +73,13 @@ int pfx_color_to_alpha_core(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint
 {
     PFX_TRY(check_images(ctx, src, dst, mask, settings, w, h, false, "pfx_color_to_alpha_core"));
     PFX_TRY(check_settings(ctx, settings, "pfx_color_to_alpha_core"));
-    PFX_TRY(pfx_use(ctx));
     const size_t px = (size_t)w * h;
-    PFX_TRY(pfx_reserve(ctx, ctx->st_in, px * 4));
-    if (mask) PFX_TRY(pfx_reserve(ctx, ctx->st_mask, px));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_in.p, src, px * 4));
-    if (mask) PFX_TRY(pfx_h2d(ctx, ctx->st_mask.p, mask, px));
-    PFX_TRY(pfx_color_to_alpha_dev(ctx, ctx->st_in.p, ctx->st_in.p, w, h, settings, mask ? ctx->st_mask.p : nullptr));   // in place
-    PFX_TRY(pfx_d2h(ctx, dst, ctx->st_in.p, px * 4));
-    return pfx_sync(ctx);
+    void* d_img;
+    const void* d_mask;
+    PFX_TRY(pfx_stage(ctx, ctx->st_in, src, px * 4, &d_img));
+    PFX_TRY(pfx_stage_opt(ctx, ctx->st_mask, mask, px, &d_mask));
+    PFX_TRY(pfx_color_to_alpha_dev(ctx, d_img, d_img, w, h, settings, d_mask));   // in place
+    return pfx_unstage(ctx, dst, ctx->st_in, px * 4);
 }
 
 int pfx_color_removal_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, const pfx_color_removal_req* req, const void* selection_dev)
@@ -97,7 +87,6 @@ int pfx_color_removal_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint
     const char* who = "pfx_color_removal_dev";
     PFX_TRY(check_images(ctx, src_dev, dst_dev, selection_dev, req, w, h, true, who));
     PFX_TRY(check_request(ctx, req, w, h, who));
-    PFX_TRY(pfx_use(ctx));
     const size_t px = (size_t)w * h;
     const uint32_t smooth = req->smoothness, chunk = PFXK_COLORKEY_CHUNK;
     const uint8_t* src = (const uint8_t*)src_dev;
@@ -109,9 +98,9 @@ int pfx_color_removal_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint
     PFX_TRY(pfx_flood_work_reserve(ctx, w, h, &W));
     uint16_t* levels[2] = {nullptr, nullptr};
     if (smooth > chunk) {
-        PFX_TRY(pfx_reserve(ctx, ctx->colorkey_ws, 2 * align256(px * 2)));
+        PFX_TRY(pfx_reserve(ctx, ctx->colorkey_ws, 2 * pfx_align256(px * 2)));
         levels[0] = (uint16_t*)ctx->colorkey_ws.p;
-        levels[1] = (uint16_t*)((uint8_t*)ctx->colorkey_ws.p + align256(px * 2));
+        levels[1] = (uint16_t*)((uint8_t*)ctx->colorkey_ws.p + pfx_align256(px * 2));
     }
     // the click: the seed's pixel and its selection byte
     const size_t seed_at = (size_t)req->seed_y * w + req->seed_x;
@@ -140,7 +129,7 @@ int pfx_color_removal_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint
         ctx->flood_passes = ctx->flood_launches = ctx->flood_visits = 0;
         PFX_TRY(pfx_flood_converge(ctx, &W, w, h, req->seed_x, req->seed_y, 4, who));
         ctx->colorkey_flood_passes = ctx->flood_passes;
-        ctx->colorkey_launches += (uint32_t)sat_int(ctx->flood_launches);
+        ctx->colorkey_launches += (uint32_t)pfx_sat_int(ctx->flood_launches);
         core = W.d;
     }
     if (smooth == 0) {
@@ -162,22 +151,20 @@ int pfx_color_removal(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_t w
 {
     PFX_TRY(check_images(ctx, src, dst, selection, req, w, h, false, "pfx_color_removal"));
     PFX_TRY(check_request(ctx, req, w, h, "pfx_color_removal"));
-    PFX_TRY(pfx_use(ctx));
     const size_t px = (size_t)w * h;
-    PFX_TRY(pfx_reserve(ctx, ctx->st_in, px * 4));
-    if (selection) PFX_TRY(pfx_reserve(ctx, ctx->st_mask, px));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_in.p, src, px * 4));
-    if (selection) PFX_TRY(pfx_h2d(ctx, ctx->st_mask.p, selection, px));
-    PFX_TRY(pfx_color_removal_dev(ctx, ctx->st_in.p, ctx->st_in.p, w, h, req, selection ? ctx->st_mask.p : nullptr));   // in place
-    PFX_TRY(pfx_d2h(ctx, dst, ctx->st_in.p, px * 4));
-    return pfx_sync(ctx);
+    void* d_img;
+    const void* d_sel;
+    PFX_TRY(pfx_stage(ctx, ctx->st_in, src, px * 4, &d_img));
+    PFX_TRY(pfx_stage_opt(ctx, ctx->st_mask, selection, px, &d_sel));
+    PFX_TRY(pfx_color_removal_dev(ctx, d_img, d_img, w, h, req, d_sel));   // in place
+    return pfx_unstage(ctx, dst, ctx->st_in, px * 4);
 }
 
 int pfx_int_colorkey_last(pfx_ctx* ctx, int which)
 {
     if (!ctx) return -1;
     switch (which) {
-        case 0: return sat_int(ctx->colorkey_flood_passes);
+        case 0: return pfx_sat_int(ctx->colorkey_flood_passes);
         case 1: return (int)ctx->colorkey_ring_launches;
         case 2: return PFXK_COLORKEY_TILE;
         case 3: return PFXK_COLORKEY_CHUNK;

@@ -64,6 +64,67 @@ int pfx_sync(pfx_ctx* ctx)
     return PFX_OK;
 }
 
+int pfx_stage(pfx_ctx* ctx, pfx_devbuf& buf, const void* host_or_null, size_t bytes, void** dev_ptr)
+{
+    PFX_TRY(pfx_reserve(ctx, buf, bytes));
+    if (host_or_null) PFX_TRY(pfx_h2d(ctx, buf.p, host_or_null, bytes));
+    *dev_ptr = buf.p;
+    return PFX_OK;
+}
+
+int pfx_unstage(pfx_ctx* ctx, void* host_dst, const pfx_devbuf& buf, size_t bytes)
+{
+    PFX_TRY(pfx_d2h(ctx, host_dst, buf.p, bytes));
+    return pfx_sync(ctx);
+}
+
+// ---- the argument rule (pfx_internal.h) ----
+int pfx_int_check_args(const pfx_arg_case* bufs, int n, int dev, uint64_t in_place_with, int* which, int* other)
+{
+    *which = *other = -1;
+    for (int i = 0; i < n; ++i)
+        if (bufs[i].addr == 0 && !(bufs[i].flags & PFX_ARG_OPTIONAL)) { *which = i; return PFX_ARG_IS_NULL; }
+    for (int i = 0; dev && i < n; ++i)
+        if ((bufs[i].flags & PFX_ARG_DWORD) && (bufs[i].addr & 3u)) { *which = i; return PFX_ARG_MISALIGNED; }
+    int partner = -1;   // the one buffer an output may coincide with: the first input declared at in_place_with
+    for (int j = n - 1; j >= 0 && in_place_with; --j)
+        if (!(bufs[j].flags & PFX_ARG_OUT) && bufs[j].addr == in_place_with) partner = j;
+    for (int i = 0; i < n; ++i) {
+        const pfx_arg_case& o = bufs[i];
+        if (!(o.flags & PFX_ARG_OUT) || o.addr == 0 || o.bytes == 0) continue;
+        for (int j = 0; j < n; ++j) {
+            const pfx_arg_case& b = bufs[j];
+            if (j == i || b.addr == 0 || b.bytes == 0) continue;
+            if (j == partner && o.addr == b.addr) continue;   // the documented in-place pair
+            if (o.addr < b.addr + b.bytes && b.addr < o.addr + o.bytes) { *which = i; *other = j; return PFX_ARG_OVERLAPS; }
+        }
+    }
+    return PFX_ARG_FINE;
+}
+
+int pfx_check_dims(pfx_ctx* ctx, const char* who, uint32_t w, uint32_t h)
+{
+    if (!ctx) return PFX_ERR_INVALID;
+    if (!pfx_dims_ok(w, h)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: bad image size %ux%u (sides above 0, at most 256 Mpx)", who, w, h);
+    return PFX_OK;
+}
+
+int pfx_check_args(pfx_ctx* ctx, const char* who, bool dev, std::initializer_list<pfx_buf_arg> bufs, const void* in_place_with)
+{
+    if (!ctx) return PFX_ERR_INVALID;
+    pfx_arg_case c[8];
+    const int n = (int)bufs.size();
+    if (n > 8) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: internal error: %d buffers declared", who, n);
+    int i = 0, which, other;
+    for (const pfx_buf_arg& b : bufs) c[i++] = pfx_arg_case{(uint64_t)(uintptr_t)b.p, (uint64_t)b.bytes, b.flags};
+    const int kind = pfx_int_check_args(c, n, dev ? 1 : 0, (uint64_t)(uintptr_t)in_place_with, &which, &other);
+    if (kind == PFX_ARG_FINE) return pfx_use(ctx);
+    const char* name = (bufs.begin() + which)->name;
+    if (kind == PFX_ARG_IS_NULL) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: %s is null", who, name);
+    if (kind == PFX_ARG_MISALIGNED) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: %s is not 4-byte aligned", who, name);
+    return pfx_fail(ctx, PFX_ERR_INVALID, "%s: %s overlaps %s%s", who, name, (bufs.begin() + other)->name, in_place_with ? " (other than in place)" : "");
+}
+
 pfx_timer::pfx_timer(pfx_ctx* c, const char* name) : ctx(c), on(c && c->timing)
 {
     if (!on) return;

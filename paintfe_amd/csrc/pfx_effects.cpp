@@ -8,14 +8,12 @@
 
 namespace {
 
-int check2(pfx_ctx* ctx, const void* a, const void* b, uint32_t w, uint32_t h, const char* who)
+// the effect kernels read neighbourhoods / gather from src while other workgroups write dst: the two never share a byte (pfx.h), in either tier.
+// The mask is not declared: these calls have never looked at where it lies
+int check2(pfx_ctx* ctx, const void* src, const void* dst, uint32_t w, uint32_t h, const char* who)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    if (!a || !b) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: null image pointer", who);
-    if (w == 0 || h == 0 || (uint64_t)w * h > 256000000ull) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: bad image size %ux%u", who, w, h);
-    // the effect kernels read neighbourhoods / gather from src while other workgroups write dst: the buffers must not overlap (pfx.h)
-    if (pfx_ranges_overlap(a, (size_t)w * h * 4, b, (size_t)w * h * 4)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: src and dst overlap", who);
-    return pfx_use(ctx);
+    PFX_TRY(pfx_check_dims(ctx, who, w, h));
+    return pfx_check_args(ctx, who, false, {{src, pfx_img_bytes(w, h), PFX_ARG_IN, "src"}, {dst, pfx_img_bytes(w, h), PFX_ARG_OUT, "dst"}});
 }
 
 inline int32_t f32_as_i32(float v) { return v != v ? 0 : (v >= 2147483648.0f ? 2147483647 : (v <= -2147483648.0f ? (-2147483647 - 1) : (int32_t)v)); }
@@ -24,19 +22,13 @@ template <class F>
 int host_wrap(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_t w, uint32_t h, const uint8_t* mask, const char* who, F&& dev_call)
 {
     PFX_TRY(check2(ctx, src, dst, w, h, who));
-    const size_t bytes = (size_t)w * h * 4;
-    PFX_TRY(pfx_reserve(ctx, ctx->st_in, bytes));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_out, bytes));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_in.p, src, bytes));
-    const void* d_mask = nullptr;
-    if (mask) {
-        PFX_TRY(pfx_reserve(ctx, ctx->st_mask, (size_t)w * h));
-        PFX_TRY(pfx_h2d(ctx, ctx->st_mask.p, mask, (size_t)w * h));
-        d_mask = ctx->st_mask.p;
-    }
-    PFX_TRY(dev_call(ctx->st_in.p, ctx->st_out.p, d_mask));
-    PFX_TRY(pfx_d2h(ctx, dst, ctx->st_out.p, bytes));
-    return pfx_sync(ctx);
+    void *d_src, *d_dst;
+    const void* d_mask;
+    PFX_TRY(pfx_stage(ctx, ctx->st_in, src, pfx_img_bytes(w, h), &d_src));
+    PFX_TRY(pfx_stage(ctx, ctx->st_out, nullptr, pfx_img_bytes(w, h), &d_dst));
+    PFX_TRY(pfx_stage_opt(ctx, ctx->st_mask, mask, (size_t)w * h, &d_mask));
+    PFX_TRY(dev_call(d_src, d_dst, d_mask));
+    return pfx_unstage(ctx, dst, ctx->st_out, pfx_img_bytes(w, h));
 }
 
 } // namespace
@@ -137,7 +129,6 @@ int pfx_motion_blur_core(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_
 // =====================================================================================================================
 namespace {
 
-inline uint32_t pack4(const uint8_t c[4]) { return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24); }
 inline float to_radians(float deg) { return deg * (3.14159265358979323846f / 180.0f); } // f32::to_radians
 inline float rs_clampf(float x, float lo, float hi) { if (x < lo) x = lo; if (x > hi) x = hi; return x; }
 inline uint32_t clamp_u32(uint32_t v, uint32_t lo, uint32_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -185,7 +176,6 @@ int pfx_zoom_blur_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t
                       uint32_t samples, const float tint_color[4], float tint_strength, const void* mask_dev)
 {
     PFX_TRY(check2(ctx, src_dev, dst_dev, w, h, "pfx_zoom_blur_dev"));
-    PFX_REQUIRE(ctx, src_dev != dst_dev, "pfx_zoom_blur_dev: in-place not supported");
     if (strength < 0.001f) return copy_through(ctx, src_dev, dst_dev, w, h); // blur.rs:332
     PFX_REQUIRE(ctx, samples <= 4096, "zoom blur: too many samples");
     const float cx = center_x * (float)w, cy = center_y * (float)h;
@@ -207,7 +197,6 @@ int pfx_crystallize_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32
                         const void* mask_dev)
 {
     PFX_TRY(check2(ctx, src_dev, dst_dev, w, h, "pfx_crystallize_dev"));
-    PFX_REQUIRE(ctx, src_dev != dst_dev, "pfx_crystallize_dev: in-place not supported");
     const float cs = fmaxf(cell_size, 2.0f);
     const int32_t cells_x = std::max(f32_as_i32(ceilf((float)w / cs)), 1), cells_y = std::max(f32_as_i32(ceilf((float)h / cs)), 1);
     const size_t n = (size_t)cells_x * cells_y;
@@ -235,7 +224,6 @@ int pfx_dents_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, 
                   uint32_t octaves, float roughness, int pinch, int wrap, const void* mask_dev)
 {
     PFX_TRY(check2(ctx, src_dev, dst_dev, w, h, "pfx_dents_dev"));
-    PFX_REQUIRE(ctx, src_dev != dst_dev, "pfx_dents_dev: in-place not supported");
     pfxk_fx_params P{};
     P.f[0] = 1.0f / fmaxf(scale, 0.5f); P.f[1] = amount; P.f[2] = scale; P.f[3] = roughness;
     P.u[0] = seed;
@@ -247,7 +235,6 @@ int pfx_bulge_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, 
                   const void* mask_dev)
 {
     PFX_TRY(check2(ctx, src_dev, dst_dev, w, h, "pfx_bulge_dev"));
-    PFX_REQUIRE(ctx, src_dev != dst_dev, "pfx_bulge_dev: in-place not supported");
     const float fw = (float)w, fh = (float)h; // distort.rs:406-411
     const float cx = rs_clampf(origin_x, 0.0f, 1.0f) * fmaxf(fw - 1.0f, 0.0f), cy = rs_clampf(origin_y, 0.0f, 1.0f) * fmaxf(fh - 1.0f, 0.0f);
     pfxk_fx_params P{};
@@ -262,7 +249,6 @@ int pfx_twist_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, 
                   const void* mask_dev)
 {
     PFX_TRY(check2(ctx, src_dev, dst_dev, w, h, "pfx_twist_dev"));
-    PFX_REQUIRE(ctx, src_dev != dst_dev, "pfx_twist_dev: in-place not supported");
     const float fw = (float)w, fh = (float)h; // distort.rs:470-477
     const float cx = rs_clampf(origin_x, 0.0f, 1.0f) * fmaxf(fw - 1.0f, 0.0f), cy = rs_clampf(origin_y, 0.0f, 1.0f) * fmaxf(fh - 1.0f, 0.0f);
     const float mx = fmaxf(cx, fw - cx), my = fmaxf(cy, fh - cy);
@@ -290,7 +276,6 @@ int pfx_reduce_noise_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint3
                          const void* mask_dev)
 {
     PFX_TRY(check2(ctx, src_dev, dst_dev, w, h, "pfx_reduce_noise_dev"));
-    PFX_REQUIRE(ctx, src_dev != dst_dev, "pfx_reduce_noise_dev: in-place not supported");
     PFX_REQUIRE(ctx, radius <= 64, "reduce_noise: radius above 64 is not supported");
     const int32_t r = radius < 1 ? 1 : (int32_t)radius;
     const float sigma_s = (float)r, sigma_r = strength * 2.55f; // noise.rs:184-186
@@ -328,7 +313,7 @@ int pfx_grid_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, u
     PFX_TRY(check2(ctx, src_dev, dst_dev, w, h, "pfx_grid_dev"));
     PFX_REQUIRE(ctx, color != nullptr && (style == PFX_GRID_LINES || style == PFX_GRID_CHECKERBOARD), "pfx_grid_dev: bad colour / style");
     pfxk_fx_params P{};
-    P.u[0] = std::max(cell_w, 2u); P.u[1] = std::max(cell_h, 2u); P.u[2] = std::max(line_width, 1u); P.u[3] = pack4(color);
+    P.u[0] = std::max(cell_w, 2u); P.u[1] = std::max(cell_h, 2u); P.u[2] = std::max(line_width, 1u); P.u[3] = pfx_pack_rgba8(color);
     P.i[0] = style;
     P.f[0] = opacity;
     return launch_fx(ctx, PFXK_FX2_GRID, "grid", src_dev, dst_dev, mask_dev, P, w, h);
@@ -341,7 +326,7 @@ int pfx_canvas_border_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint
     PFX_REQUIRE(ctx, color != nullptr, "pfx_canvas_border_dev: null colour");
     pfxk_fx_params P{};
     P.u[0] = std::min(std::max(width, 1u), std::min(w, h)); // render.rs:126
-    P.u[1] = pack4(color);
+    P.u[1] = pfx_pack_rgba8(color);
     return launch_fx(ctx, PFXK_FX2_BORDER, "canvas_border", src_dev, dst_dev, mask_dev, P, w, h);
 }
 
@@ -350,7 +335,6 @@ int pfx_shadow_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w,
 {
     PFX_TRY(check2(ctx, src_dev, dst_dev, w, h, "pfx_shadow_dev"));
     PFX_REQUIRE(ctx, color != nullptr, "pfx_shadow_dev: null colour");
-    PFX_REQUIRE(ctx, src_dev != dst_dev, "pfx_shadow_dev: in-place not supported");
     const size_t n = (size_t)w * h;
     int32_t spread = 0;
     if (widen_radius) spread = f32_as_i32(roundf(fmaxf(blur_radius, 1.0f))); // render.rs:251
@@ -380,7 +364,7 @@ int pfx_shadow_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w,
     }
     pfxk_fx_params P{};
     P.f[0] = opacity;
-    P.u[0] = pack4(color);
+    P.u[0] = pfx_pack_rgba8(color);
     P.u[1] = plane_path ? 1u : 0u;
     P.aux0 = alpha_img;
     return launch_fx(ctx, PFXK_FX2_SHADOW, "shadow_composite", src_dev, dst_dev, mask_dev, P, w, h);
@@ -391,13 +375,12 @@ int pfx_outline_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w
 {
     PFX_TRY(check2(ctx, src_dev, dst_dev, w, h, "pfx_outline_dev"));
     PFX_REQUIRE(ctx, color != nullptr && mode >= PFX_OUTLINE_OUTSIDE && mode <= PFX_OUTLINE_CENTER, "pfx_outline_dev: bad colour / mode");
-    PFX_REQUIRE(ctx, src_dev != dst_dev, "pfx_outline_dev: in-place not supported");
     PFX_REQUIRE(ctx, width <= 256, "outline: width above 256 is not supported");
     const float radius = (float)std::max(width, 1u); // render.rs:417-418
     pfxk_fx_params P{};
     P.f[0] = radius;
     P.i[0] = f32_as_i32(ceilf(radius)) + 1; P.i[1] = mode; P.i[2] = anti_alias ? 1 : 0;
-    P.u[0] = pack4(color);
+    P.u[0] = pfx_pack_rgba8(color);
     if (P.i[0] <= 15 && ctx->outline_bits) { // search windows up to 31 columns: nearest filled / empty texel from a bit plane of alpha != 0
         const uint32_t stride = pfxk_alpha_bits_stride(w);
         PFX_TRY(pfx_reserve(ctx, ctx->st_tmp, (size_t)h * stride * 4));
@@ -412,7 +395,6 @@ int pfx_pixel_drag_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_
                        float direction, const void* mask_dev)
 {
     PFX_TRY(check2(ctx, src_dev, dst_dev, w, h, "pfx_pixel_drag_dev"));
-    PFX_REQUIRE(ctx, src_dev != dst_dev, "pfx_pixel_drag_dev: in-place not supported");
     const float dir_rad = to_radians(direction); // glitch.rs:64-67
     pfxk_fx_params P{};
     P.f[0] = cosf(dir_rad); P.f[1] = sinf(dir_rad); P.f[2] = (float)std::max(distance, 1u); P.f[3] = amount / 100.0f;
@@ -424,7 +406,6 @@ int pfx_rgb_displace_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint3
                          int32_t g_dy, int32_t b_dx, int32_t b_dy, const void* mask_dev)
 {
     PFX_TRY(check2(ctx, src_dev, dst_dev, w, h, "pfx_rgb_displace_dev"));
-    PFX_REQUIRE(ctx, src_dev != dst_dev, "pfx_rgb_displace_dev: in-place not supported");
     pfxk_fx_params P{};
     const int32_t off[6] = {r_dx, r_dy, g_dx, g_dy, b_dx, b_dy};
     for (int k = 0; k < 6; ++k) P.i[k] = std::max(-(1 << 28), std::min(1 << 28, off[k])); // far beyond any image: same clamped texel, no i32 overflow
@@ -434,7 +415,6 @@ int pfx_rgb_displace_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint3
 int pfx_ink_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, float edge_strength, float threshold, const void* mask_dev)
 {
     PFX_TRY(check2(ctx, src_dev, dst_dev, w, h, "pfx_ink_dev"));
-    PFX_REQUIRE(ctx, src_dev != dst_dev, "pfx_ink_dev: in-place not supported");
     pfxk_fx_params P{};
     P.f[0] = edge_strength; P.f[1] = threshold;
     return launch_fx(ctx, PFXK_FX2_INK, "ink", src_dev, dst_dev, mask_dev, P, w, h);
@@ -444,7 +424,6 @@ int pfx_oil_painting_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint3
                          const void* mask_dev)
 {
     PFX_TRY(check2(ctx, src_dev, dst_dev, w, h, "pfx_oil_painting_dev"));
-    PFX_REQUIRE(ctx, src_dev != dst_dev, "pfx_oil_painting_dev: in-place not supported");
     pfx_timer t(ctx, "oil_painting"); // artistic.rs:135-136
     PFX_HIP(ctx, pfxk_oil_painting(ctx->stream, (const uint8_t*)src_dev, (uint8_t*)dst_dev, (const uint8_t*)mask_dev, (int)clamp_u32(radius, 1, 10),
                                    (int)clamp_u32(levels, 2, 64), w, h));

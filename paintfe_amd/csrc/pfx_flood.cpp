@@ -6,44 +6,36 @@
 // w * h pixels and every pass settles the next one).  The flood runs in working memory: a failed call leaves `dist` untouched.  The pass loop itself
 // (pfx_flood_converge) takes a device cost map: the colour remover's core flood (pfx_colorkey.cpp) runs it over its passability map.
 #include <algorithm>
-#include <climits>
 #include <cmath>
 
 #include "pfx_internal.h"
 
 namespace {
 
-inline size_t align256(size_t n) { return (n + 255u) & ~(size_t)255u; }
-inline uint32_t pack4(const uint8_t c[4]) { return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24); }
-
 float srgb_to_linear(float v) { return v <= 0.04045f ? v / 12.92f : powf((v + 0.055f) / 1.055f, 2.4f); }   // :84
 
 int check_flood(pfx_ctx* ctx, const void* src, uint32_t w, uint32_t h, const pfx_flood* f, const void* dist, bool dev, const char* who)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    if (!pfx_dims_ok(w, h)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: bad image size %ux%u", who, w, h);
-    if (!src || !dist || !f) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: null pointer", who);
+    PFX_TRY(pfx_check_dims(ctx, who, w, h));
+    const size_t px = (size_t)w * h;
+    PFX_TRY(pfx_check_args(ctx, who, dev, {{src, px * 4, PFX_ARG_DWORD, "src"}, {dist, px, PFX_ARG_OUT, "dist"}, {f, 0, PFX_ARG_IN, "flood"}}));
     if (f->connectivity != 4 && f->connectivity != 8) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: connectivity %u (4 or 8)", who, f->connectivity);
     if (f->distance_mode > 1 || f->global > 1) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: unknown distance mode %u or scope %u", who, f->distance_mode, f->global);
     if (f->seed_x >= w || f->seed_y >= h) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: seed (%u, %u) outside the %ux%u image", who, f->seed_x, f->seed_y, w, h);
-    const size_t px = (size_t)w * h;
-    if (pfx_ranges_overlap(dist, px, src, px * 4)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: dist overlaps src", who);
-    if (dev && ((uintptr_t)src & 3u)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: src_dev is not 4-byte aligned", who);   // the kernels read a pixel as one dword
-    return pfx_use(ctx);
+    return PFX_OK;
 }
 
-// the threshold kernels' shared checks: `out` of out_bytes must not overlap the distance map, nor `other` (the base mask / the selection, may be NULL)
-// unless same_ok and the two are the same buffer
-int check_threshold_call(pfx_ctx* ctx, const void* dist, const void* other, const void* out, size_t out_bytes, bool same_ok, uint32_t w, uint32_t h, const char* who)
+// the threshold kernels' shared declaration: an output of `out_px` bytes per pixel — the wand's mask (1), which may BE the base mask, or an RGBA8 image (4),
+// dword-aligned on the device — against the distance map and `other` (the base mask / the selection, may be NULL); `fill` is the colour, where there is one
+int check_threshold_call(pfx_ctx* ctx, const void* dist, const void* other, const void* out, size_t out_px, bool dev, uint32_t w, uint32_t h, const uint8_t* fill,
+                         const char* who)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    if (!pfx_dims_ok(w, h)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: bad image size %ux%u", who, w, h);
-    if (!dist || !out) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: null pointer", who);
+    PFX_TRY(pfx_check_dims(ctx, who, w, h));
     const size_t px = (size_t)w * h;
-    if (pfx_ranges_overlap(out, out_bytes, dist, px)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: the distance map overlaps the output", who);
-    if (other && !(same_ok && other == out) && pfx_ranges_overlap(out, out_bytes, other, px))
-        return pfx_fail(ctx, PFX_ERR_INVALID, "%s: the output overlaps the %s", who, same_ok ? "base mask (other than in place)" : "selection");
-    return pfx_use(ctx);
+    const bool wand = out_px == 1;
+    return pfx_check_args(ctx, who, dev, {{dist, px, PFX_ARG_IN, "dist"}, {other, px, PFX_ARG_OPTIONAL, wand ? "base_mask" : "selection"},
+                                          {out, px * out_px, wand ? PFX_ARG_OUT : PFX_ARG_OUT | PFX_ARG_DWORD, wand ? "mask_out" : "the image"},
+                                          {fill, 0, wand ? PFX_ARG_OPTIONAL : PFX_ARG_IN, "fill"}}, wand ? other : nullptr);
 }
 
 int flood_table(pfx_ctx* ctx)
@@ -61,13 +53,11 @@ int flood_table(pfx_ctx* ctx)
 pfxk_flood_target make_target(const pfx_flood* f)
 {
     pfxk_flood_target G;
-    G.rgba = pack4(f->target);
+    G.rgba = pfx_pack_rgba8(f->target);
     G.ta = (float)f->target[3] / 255.0f;
     for (int k = 0; k < 3; ++k) G.lin[k] = srgb_to_linear((float)f->target[k] / 255.0f) * G.ta;   // :112-114
     return G;
 }
-
-inline int sat_int(uint64_t v) { return v > (uint64_t)INT_MAX ? INT_MAX : (int)v; }
 
 } // namespace
 
@@ -76,8 +66,8 @@ int pfx_flood_work_reserve(pfx_ctx* ctx, uint32_t w, uint32_t h, pfx_flood_work*
 {
     const uint32_t T = PFXK_FLOOD_TILE;
     const size_t px = (size_t)w * h, tiles = (size_t)((w + T - 1) / T) * ((h + T - 1) / T);
-    const size_t off_c = 256, off_d = off_c + align256(px), off_l0 = off_d + align256(px), off_l1 = off_l0 + align256(tiles * 4),
-                 off_mark = off_l1 + align256(tiles * 4), total = off_mark + align256(tiles * 4);
+    const size_t off_c = 256, off_d = off_c + pfx_align256(px), off_l0 = off_d + pfx_align256(px), off_l1 = off_l0 + pfx_align256(tiles * 4),
+                 off_mark = off_l1 + pfx_align256(tiles * 4), total = off_mark + pfx_align256(tiles * 4);
     PFX_TRY(pfx_reserve(ctx, ctx->flood_ws, total));
     uint8_t* ws = (uint8_t*)ctx->flood_ws.p;
     W->state = (uint32_t*)ws;
@@ -163,20 +153,17 @@ int pfx_flood_distance(pfx_ctx* ctx, const uint8_t* src, uint32_t w, uint32_t h,
 {
     PFX_TRY(check_flood(ctx, src, w, h, flood, dist, false, "pfx_flood_distance"));
     const size_t px = (size_t)w * h;
-    PFX_TRY(pfx_reserve(ctx, ctx->st_in, px * 4));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_mask, px));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_in.p, src, px * 4));
-    PFX_TRY(pfx_flood_distance_dev(ctx, ctx->st_in.p, w, h, flood, ctx->st_mask.p));
-    PFX_TRY(pfx_d2h(ctx, dist, ctx->st_mask.p, px));
-    return pfx_sync(ctx);
+    void *d_src, *d_dist;
+    PFX_TRY(pfx_stage(ctx, ctx->st_in, src, px * 4, &d_src));
+    PFX_TRY(pfx_stage(ctx, ctx->st_mask, nullptr, px, &d_dist));
+    PFX_TRY(pfx_flood_distance_dev(ctx, d_src, w, h, flood, d_dist));
+    return pfx_unstage(ctx, dist, ctx->st_mask, px);
 }
 
 int pfx_flood_bboxes_dev(pfx_ctx* ctx, const void* dist_dev, uint32_t w, uint32_t h, int32_t boxes[1024])
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    if (!pfx_dims_ok(w, h)) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_flood_bboxes_dev: bad image size %ux%u", w, h);
-    if (!dist_dev || !boxes) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_flood_bboxes_dev: null pointer");
-    PFX_TRY(pfx_use(ctx));
+    PFX_TRY(pfx_check_dims(ctx, "pfx_flood_bboxes_dev", w, h));
+    PFX_TRY(pfx_check_args(ctx, "pfx_flood_bboxes_dev", true, {{dist_dev, (size_t)w * h, PFX_ARG_IN, "dist_dev"}, {boxes, 0, PFX_ARG_IN, "boxes"}}));
     PFX_TRY(pfx_reserve(ctx, ctx->d_misc, 4096));
     uint32_t per[1024];
     {
@@ -204,7 +191,7 @@ int pfx_wand_mask_dev(pfx_ctx* ctx, const void* dist_dev, const void* base_mask_
                       uint8_t combine_mode, void* mask_out_dev)
 {
     const size_t px = (size_t)w * h;
-    PFX_TRY(check_threshold_call(ctx, dist_dev, base_mask_dev, mask_out_dev, px, true, w, h, "pfx_wand_mask_dev"));
+    PFX_TRY(check_threshold_call(ctx, dist_dev, base_mask_dev, mask_out_dev, 1, true, w, h, nullptr, "pfx_wand_mask_dev"));
     if (combine_mode > 3) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_wand_mask_dev: unknown combine mode %u", combine_mode);
     pfx_timer t(ctx, "wand_mask");
     PFX_HIP(ctx, pfxk_wand_mask(ctx->stream, (const uint8_t*)dist_dev, (const uint8_t*)base_mask_dev, (uint8_t*)mask_out_dev, px, threshold, anti_aliased != 0, combine_mode));
@@ -215,26 +202,22 @@ int pfx_wand_mask(pfx_ctx* ctx, const uint8_t* dist, const uint8_t* base_mask, u
                   uint8_t* mask_out)
 {
     const size_t px = (size_t)w * h;
-    PFX_TRY(check_threshold_call(ctx, dist, base_mask, mask_out, px, true, w, h, "pfx_wand_mask"));
+    PFX_TRY(check_threshold_call(ctx, dist, base_mask, mask_out, 1, false, w, h, nullptr, "pfx_wand_mask"));
     if (combine_mode > 3) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_wand_mask: unknown combine mode %u", combine_mode);
-    PFX_TRY(pfx_reserve(ctx, ctx->st_tmp, px));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_mask, px));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_tmp.p, dist, px));
-    if (base_mask) PFX_TRY(pfx_h2d(ctx, ctx->st_mask.p, base_mask, px));
-    PFX_TRY(pfx_wand_mask_dev(ctx, ctx->st_tmp.p, base_mask ? ctx->st_mask.p : nullptr, w, h, threshold, anti_aliased, combine_mode, ctx->st_mask.p));   // in place
-    PFX_TRY(pfx_d2h(ctx, mask_out, ctx->st_mask.p, px));
-    return pfx_sync(ctx);
+    void *d_dist, *d_mask;
+    PFX_TRY(pfx_stage(ctx, ctx->st_tmp, dist, px, &d_dist));
+    PFX_TRY(pfx_stage(ctx, ctx->st_mask, base_mask, px, &d_mask));
+    PFX_TRY(pfx_wand_mask_dev(ctx, d_dist, base_mask ? d_mask : nullptr, w, h, threshold, anti_aliased, combine_mode, d_mask));   // in place
+    return pfx_unstage(ctx, mask_out, ctx->st_mask, px);
 }
 
 int pfx_fill_preview_dev(pfx_ctx* ctx, const void* dist_dev, const void* selection_dev, uint32_t w, uint32_t h, uint8_t threshold, const uint8_t fill[4],
                          void* canvas_out_dev)
 {
     const size_t px = (size_t)w * h;
-    PFX_TRY(check_threshold_call(ctx, dist_dev, selection_dev, canvas_out_dev, px * 4, false, w, h, "pfx_fill_preview_dev"));
-    if (!fill) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_fill_preview_dev: null fill colour");
-    if ((uintptr_t)canvas_out_dev & 3u) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_fill_preview_dev: canvas_out_dev is not 4-byte aligned");
+    PFX_TRY(check_threshold_call(ctx, dist_dev, selection_dev, canvas_out_dev, 4, true, w, h, fill, "pfx_fill_preview_dev"));
     pfx_timer t(ctx, "fill_preview");
-    PFX_HIP(ctx, pfxk_fill_preview(ctx->stream, (const uint8_t*)dist_dev, (const uint8_t*)selection_dev, (uint8_t*)canvas_out_dev, px, threshold, pack4(fill)));
+    PFX_HIP(ctx, pfxk_fill_preview(ctx->stream, (const uint8_t*)dist_dev, (const uint8_t*)selection_dev, (uint8_t*)canvas_out_dev, px, threshold, pfx_pack_rgba8(fill)));
     return PFX_OK;
 }
 
@@ -242,65 +225,58 @@ int pfx_fill_preview(pfx_ctx* ctx, const uint8_t* dist, const uint8_t* selection
                      uint8_t* canvas_out)
 {
     const size_t px = (size_t)w * h;
-    PFX_TRY(check_threshold_call(ctx, dist, selection, canvas_out, px * 4, false, w, h, "pfx_fill_preview"));
-    if (!fill) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_fill_preview: null fill colour");
-    PFX_TRY(pfx_reserve(ctx, ctx->st_tmp, px));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_mask, px));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_out, px * 4));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_tmp.p, dist, px));
-    if (selection) PFX_TRY(pfx_h2d(ctx, ctx->st_mask.p, selection, px));
-    PFX_TRY(pfx_fill_preview_dev(ctx, ctx->st_tmp.p, selection ? ctx->st_mask.p : nullptr, w, h, threshold, fill, ctx->st_out.p));
-    PFX_TRY(pfx_d2h(ctx, canvas_out, ctx->st_out.p, px * 4));
-    return pfx_sync(ctx);
+    PFX_TRY(check_threshold_call(ctx, dist, selection, canvas_out, 4, false, w, h, fill, "pfx_fill_preview"));
+    void *d_dist, *d_out;
+    const void* d_sel;
+    PFX_TRY(pfx_stage(ctx, ctx->st_tmp, dist, px, &d_dist));
+    PFX_TRY(pfx_stage_opt(ctx, ctx->st_mask, selection, px, &d_sel));
+    PFX_TRY(pfx_stage(ctx, ctx->st_out, nullptr, px * 4, &d_out));
+    PFX_TRY(pfx_fill_preview_dev(ctx, d_dist, d_sel, w, h, threshold, fill, d_out));
+    return pfx_unstage(ctx, canvas_out, ctx->st_out, px * 4);
 }
 
 int pfx_fill_commit_dev(pfx_ctx* ctx, void* layer_dev, const void* dist_dev, const void* selection_dev, uint32_t w, uint32_t h, uint8_t threshold,
                         const uint8_t fill[4], uint8_t blend_mode)
 {
     const size_t px = (size_t)w * h;
-    PFX_TRY(check_threshold_call(ctx, dist_dev, selection_dev, layer_dev, px * 4, false, w, h, "pfx_fill_commit_dev"));
-    if (!fill) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_fill_commit_dev: null fill colour");
-    if ((uintptr_t)layer_dev & 3u) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_fill_commit_dev: layer_dev is not 4-byte aligned");
+    PFX_TRY(check_threshold_call(ctx, dist_dev, selection_dev, layer_dev, 4, true, w, h, fill, "pfx_fill_commit_dev"));
     if (blend_mode > 24) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_fill_commit_dev: unknown blend mode %u", blend_mode);
     pfx_timer t(ctx, "fill_commit");
-    PFX_HIP(ctx, pfxk_fill_commit(ctx->stream, (uint8_t*)layer_dev, (const uint8_t*)dist_dev, (const uint8_t*)selection_dev, px, threshold, pack4(fill), blend_mode));
+    PFX_HIP(ctx, pfxk_fill_commit(ctx->stream, (uint8_t*)layer_dev, (const uint8_t*)dist_dev, (const uint8_t*)selection_dev, px, threshold, pfx_pack_rgba8(fill), blend_mode));
     return PFX_OK;
 }
 
 int pfx_bucket_fill(pfx_ctx* ctx, uint8_t* layer_inout, uint32_t w, uint32_t h, uint32_t seed_x, uint32_t seed_y, float tolerance, const uint8_t fill[4],
                     uint8_t blend_mode, int global_fill, const uint8_t* selection)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    if (!pfx_dims_ok(w, h)) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_bucket_fill: bad image size %ux%u", w, h);
-    if (!layer_inout || !fill) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_bucket_fill: null pointer");
+    PFX_TRY(pfx_check_dims(ctx, "pfx_bucket_fill", w, h));
+    const size_t px = (size_t)w * h;
+    PFX_TRY(pfx_check_args(ctx, "pfx_bucket_fill", false, {{layer_inout, px * 4, PFX_ARG_OUT, "layer_inout"}, {selection, px, PFX_ARG_OPTIONAL, "selection"},
+                                                            {fill, 0, PFX_ARG_IN, "fill"}}));
     if (seed_x >= w || seed_y >= h) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_bucket_fill: seed (%u, %u) outside the %ux%u image", seed_x, seed_y, w, h);
     if (blend_mode > 24) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_bucket_fill: unknown blend mode %u", blend_mode);
-    const size_t px = (size_t)w * h;
-    if (selection && pfx_ranges_overlap(layer_inout, px * 4, selection, px)) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_bucket_fill: the layer overlaps the selection");
-    PFX_TRY(pfx_use(ctx));
     pfx_flood f{};
     f.seed_x = seed_x; f.seed_y = seed_y;
     memcpy(f.target, layer_inout + ((size_t)seed_y * w + seed_x) * 4, 4);   // :1252
     f.distance_mode = 0; f.connectivity = 4; f.global = global_fill ? 1 : 0;   // :1272-1273
-    PFX_TRY(pfx_reserve(ctx, ctx->st_in, px * 4));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_tmp, px));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_mask, px));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_in.p, layer_inout, px * 4));
-    if (selection) PFX_TRY(pfx_h2d(ctx, ctx->st_mask.p, selection, px));
-    PFX_TRY(pfx_flood_distance_dev(ctx, ctx->st_in.p, w, h, &f, ctx->st_tmp.p));
-    PFX_TRY(pfx_fill_commit_dev(ctx, ctx->st_in.p, ctx->st_tmp.p, selection ? ctx->st_mask.p : nullptr, w, h, pfx_tolerance_threshold(tolerance), fill, blend_mode));
-    PFX_TRY(pfx_d2h(ctx, layer_inout, ctx->st_in.p, px * 4));
-    return pfx_sync(ctx);
+    void *d_layer, *d_dist;
+    const void* d_sel;
+    PFX_TRY(pfx_stage(ctx, ctx->st_in, layer_inout, px * 4, &d_layer));
+    PFX_TRY(pfx_stage(ctx, ctx->st_tmp, nullptr, px, &d_dist));
+    PFX_TRY(pfx_stage_opt(ctx, ctx->st_mask, selection, px, &d_sel));
+    PFX_TRY(pfx_flood_distance_dev(ctx, d_layer, w, h, &f, d_dist));
+    PFX_TRY(pfx_fill_commit_dev(ctx, d_layer, d_dist, d_sel, w, h, pfx_tolerance_threshold(tolerance), fill, blend_mode));
+    return pfx_unstage(ctx, layer_inout, ctx->st_in, px * 4);
 }
 
 int pfx_int_flood_last(pfx_ctx* ctx, int which)
 {
     if (!ctx) return -1;
     switch (which) {
-        case 0: return sat_int(ctx->flood_passes);
-        case 1: return sat_int(ctx->flood_launches);
+        case 0: return pfx_sat_int(ctx->flood_passes);
+        case 1: return pfx_sat_int(ctx->flood_launches);
         case 2: return PFXK_FLOOD_TILE;
-        case 3: return sat_int(ctx->flood_visits);
+        case 3: return pfx_sat_int(ctx->flood_visits);
         default: return -1;
     }
 }

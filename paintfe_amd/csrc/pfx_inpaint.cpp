@@ -9,38 +9,30 @@
 
 namespace {
 
-inline uint32_t f32_as_u32(float v) { return !(v > 0.0f) ? 0u : (v >= 4294967296.0f ? 0xffffffffu : (uint32_t)v); }
 inline float clamp01(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
-inline size_t align256(size_t n) { return (n + 255u) & ~(size_t)255u; }
 
 int check_instant(pfx_ctx* ctx, const void* src, const void* mask, const void* out, uint32_t w, uint32_t h, const pfx_inpaint_dab* dabs, uint32_t n_dabs,
                   const char* who)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    if (!src || !mask || !out) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: null image pointer", who);
-    if (!pfx_dims_ok(w, h)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: bad canvas size %ux%u", who, w, h);
+    PFX_TRY(pfx_check_dims(ctx, who, w, h));
     const size_t px = (size_t)w * h;
-    if (pfx_ranges_overlap(out, px * 4, src, px * 4) || pfx_ranges_overlap(out, px * 4, mask, px))
-        return pfx_fail(ctx, PFX_ERR_INVALID, "%s: out overlaps src or the hole mask", who);
+    PFX_TRY(pfx_check_args(ctx, who, false, {{src, px * 4, PFX_ARG_IN, "src"}, {mask, px, PFX_ARG_IN, "hole_mask"}, {out, px * 4, PFX_ARG_OUT, "out"}}));
     if (n_dabs && !dabs) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: null dab list", who);
     for (uint32_t i = 0; i < n_dabs; ++i) {
         const pfx_inpaint_dab& D = dabs[i];
         if (!std::isfinite(D.cx) || !std::isfinite(D.cy) || !std::isfinite(D.brush_radius) || !std::isfinite(D.sample_radius) || !std::isfinite(D.hardness))
             return pfx_fail(ctx, PFX_ERR_INVALID, "%s: non-finite field in dab %u", who, i);
     }
-    return pfx_use(ctx);
+    return PFX_OK;
 }
 
 int check_patchmatch(pfx_ctx* ctx, const void* src, const void* mask, const void* dst, uint32_t w, uint32_t h, uint32_t patch_size, const char* who)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    if (!src || !mask || !dst) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: null image pointer", who);
-    if (!pfx_dims_ok(w, h)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: bad canvas size %ux%u", who, w, h);
-    if (patch_size > 11) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: patch size %u (the tool's range is 3..11)", who, patch_size);
+    PFX_TRY(pfx_check_dims(ctx, who, w, h));
     const size_t px = (size_t)w * h;
-    if ((dst != src && pfx_ranges_overlap(dst, px * 4, src, px * 4)) || pfx_ranges_overlap(dst, px * 4, mask, px))
-        return pfx_fail(ctx, PFX_ERR_INVALID, "%s: dst overlaps src (other than dst == src) or the hole mask", who);
-    return pfx_use(ctx);
+    PFX_TRY(pfx_check_args(ctx, who, false, {{src, px * 4, PFX_ARG_IN, "src"}, {mask, px, PFX_ARG_IN, "hole_mask"}, {dst, px * 4, PFX_ARG_OUT, "dst"}}, src));
+    if (patch_size > 11) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: patch size %u (the tool's range is 3..11)", who, patch_size);
+    return PFX_OK;
 }
 
 } // namespace
@@ -65,8 +57,8 @@ int pfx_inpaint_instant_dev(pfx_ctx* ctx, const void* src_dev, const void* hole_
         K.r = fmaxf(D.brush_radius, 1.0f);
         K.hard_t = clamp01(D.hardness * 0.9f + 0.1f);
         K.soft_den = 1.0f - K.hard_t + 1e-6f;
-        K.x0 = f32_as_u32(fmaxf(D.cx - K.r, 0.0f)); K.x1 = std::min(f32_as_u32(ceilf(D.cx + K.r)), w - 1u);   // :93-96
-        K.y0 = f32_as_u32(fmaxf(D.cy - K.r, 0.0f)); K.y1 = std::min(f32_as_u32(ceilf(D.cy + K.r)), h - 1u);
+        K.x0 = pfx_f32_as_u32(fmaxf(D.cx - K.r, 0.0f)); K.x1 = std::min(pfx_f32_as_u32(ceilf(D.cx + K.r)), w - 1u);   // :93-96
+        K.y0 = pfx_f32_as_u32(fmaxf(D.cy - K.r, 0.0f)); K.y1 = std::min(pfx_f32_as_u32(ceilf(D.cy + K.r)), h - 1u);
         uint32_t key;
         memcpy(&key, &D.sample_radius, 4);
         size_t at = std::find(ring_key.begin(), ring_key.end(), key) - ring_key.begin();
@@ -82,7 +74,7 @@ int pfx_inpaint_instant_dev(pfx_ctx* ctx, const void* src_dev, const void* hole_
         }
     }
     if (!any) return PFX_OK;   // every dab's pixel loop is empty
-    const size_t dab_bytes = align256(k.size() * sizeof(pfxk_inpaint_dab));
+    const size_t dab_bytes = pfx_align256(k.size() * sizeof(pfxk_inpaint_dab));
     PFX_TRY(pfx_reserve(ctx, ctx->d_pts, dab_bytes + rings.size() * 4));
     PFX_TRY(pfx_h2d(ctx, ctx->d_pts.p, k.data(), k.size() * sizeof(pfxk_inpaint_dab)));
     PFX_TRY(pfx_h2d(ctx, (uint8_t*)ctx->d_pts.p + dab_bytes, rings.data(), rings.size() * 4));
@@ -99,15 +91,12 @@ int pfx_inpaint_instant(pfx_ctx* ctx, const uint8_t* src, const uint8_t* hole_ma
     PFX_TRY(check_instant(ctx, src, hole_mask, out_inout, w, h, dabs, n_dabs, "pfx_inpaint_instant"));
     if (n_dabs == 0) return PFX_OK;
     const size_t px = (size_t)w * h;
-    PFX_TRY(pfx_reserve(ctx, ctx->st_in, px * 4));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_mask, px));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_out, px * 4));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_in.p, src, px * 4));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_mask.p, hole_mask, px));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_out.p, out_inout, px * 4));
-    PFX_TRY(pfx_inpaint_instant_dev(ctx, ctx->st_in.p, ctx->st_mask.p, ctx->st_out.p, w, h, dabs, n_dabs));
-    PFX_TRY(pfx_d2h(ctx, out_inout, ctx->st_out.p, px * 4));
-    return pfx_sync(ctx);
+    void *d_src, *d_mask, *d_out;
+    PFX_TRY(pfx_stage(ctx, ctx->st_in, src, px * 4, &d_src));
+    PFX_TRY(pfx_stage(ctx, ctx->st_mask, hole_mask, px, &d_mask));
+    PFX_TRY(pfx_stage(ctx, ctx->st_out, out_inout, px * 4, &d_out));
+    PFX_TRY(pfx_inpaint_instant_dev(ctx, d_src, d_mask, d_out, w, h, dabs, n_dabs));
+    return pfx_unstage(ctx, out_inout, ctx->st_out, px * 4);
 }
 
 int pfx_inpaint_patchmatch_dev(pfx_ctx* ctx, const void* src_dev, const void* hole_mask_dev, void* dst_dev, uint32_t w, uint32_t h, uint32_t patch_size,
@@ -142,9 +131,9 @@ int pfx_inpaint_patchmatch_dev(pfx_ctx* ctx, const void* src_dev, const void* ho
     // working memory, one block: [0] 256 bytes of counters | live mask | source list (w * h indices: the non-hole pixels, then every peel's boundary) |
     // compaction block counts | NNF ox, oy, ssd over the box plus one | diagonal starts, cursors, list
     const size_t nnf = (size_t)(G.bw + 2u) * (G.bh + 2u), n_diag = (size_t)G.bw + G.bh - 1u, blocks = (px + 1023u) / 1024u;
-    const size_t off_live = 256, off_list = off_live + align256(px), off_counts = off_list + align256(px * 4), off_ox = off_counts + align256(blocks * 4),
-                 off_oy = off_ox + align256(nnf * 4), off_sd = off_oy + align256(nnf * 4), off_dstart = off_sd + align256(nnf * 4),
-                 off_cursor = off_dstart + align256((n_diag + 1) * 4), off_dlist = off_cursor + align256(n_diag * 4), total = off_dlist + align256((size_t)holes * 4);
+    const size_t off_live = 256, off_list = off_live + pfx_align256(px), off_counts = off_list + pfx_align256(px * 4), off_ox = off_counts + pfx_align256(blocks * 4),
+                 off_oy = off_ox + pfx_align256(nnf * 4), off_sd = off_oy + pfx_align256(nnf * 4), off_dstart = off_sd + pfx_align256(nnf * 4),
+                 off_cursor = off_dstart + pfx_align256((n_diag + 1) * 4), off_dlist = off_cursor + pfx_align256(n_diag * 4), total = off_dlist + pfx_align256((size_t)holes * 4);
     PFX_TRY(pfx_reserve(ctx, ctx->inpaint_ws, total));   // a failure leaves dst untouched
     uint8_t* ws = (uint8_t*)ctx->inpaint_ws.p;
     uint32_t* d_total = (uint32_t*)ws;
@@ -183,13 +172,11 @@ int pfx_inpaint_patchmatch(pfx_ctx* ctx, const uint8_t* src, const uint8_t* hole
 {
     PFX_TRY(check_patchmatch(ctx, src, hole_mask, dst, w, h, patch_size, "pfx_inpaint_patchmatch"));
     const size_t px = (size_t)w * h;
-    PFX_TRY(pfx_reserve(ctx, ctx->st_in, px * 4));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_mask, px));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_in.p, src, px * 4));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_mask.p, hole_mask, px));
-    PFX_TRY(pfx_inpaint_patchmatch_dev(ctx, ctx->st_in.p, ctx->st_mask.p, ctx->st_in.p, w, h, patch_size, iterations));   // in place in the staging copy
-    PFX_TRY(pfx_d2h(ctx, dst, ctx->st_in.p, px * 4));
-    return pfx_sync(ctx);
+    void *d_img, *d_mask;
+    PFX_TRY(pfx_stage(ctx, ctx->st_in, src, px * 4, &d_img));
+    PFX_TRY(pfx_stage(ctx, ctx->st_mask, hole_mask, px, &d_mask));
+    PFX_TRY(pfx_inpaint_patchmatch_dev(ctx, d_img, d_mask, d_img, w, h, patch_size, iterations));   // in place in the staging copy
+    return pfx_unstage(ctx, dst, ctx->st_in, px * 4);
 }
 
 int pfx_int_inpaint_last(pfx_ctx* ctx, int which) { return !ctx ? -1 : (which == 0 ? (int)ctx->inpaint_peels : (int)ctx->inpaint_launches); }

@@ -4,6 +4,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <vector>
@@ -137,12 +138,44 @@ inline bool pfx_ranges_overlap(const void* a, size_t a_bytes, const void* b, siz
     return x < y + b_bytes && y < x + a_bytes;
 }
 
+// ---- small host helpers every module shares ----
+inline size_t pfx_img_bytes(uint32_t w, uint32_t h) { return (size_t)w * h * 4; }
+inline size_t pfx_align256(size_t n) { return (n + 255u) & ~(size_t)255u; }
+inline uint32_t pfx_pack_rgba8(const uint8_t c[4]) { return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24); }
+inline int pfx_sat_int(uint64_t v) { return v > 0x7fffffffull ? 0x7fffffff : (int)v; }
+inline uint32_t pfx_f32_as_u32(float v) { return !(v > 0.0f) ? 0u : (v >= 4294967296.0f ? 0xffffffffu : (uint32_t)v); }   // Rust's `v as u32`: truncates, saturates, NaN -> 0
+
 // ---- helpers (pfx_ctx.cpp) ----
 int pfx_use(pfx_ctx* ctx);                                     // hipSetDevice
 int pfx_reserve(pfx_ctx* ctx, pfx_devbuf& b, size_t bytes);    // grow-on-demand
 int pfx_h2d(pfx_ctx* ctx, void* dst, const void* src, size_t bytes);
 int pfx_d2h(pfx_ctx* ctx, void* dst, const void* src, size_t bytes);
 int pfx_sync(pfx_ctx* ctx);
+
+// ---- the argument rule of every entry point that takes an image or a mask (pfx_ctx.cpp; the contract itself: include/pfx.h) ----
+// An entry point runs its pfx_check_dims line(s), then declares its buffers to pfx_check_args: a required pointer is non-NULL; an OUT buffer shares no byte
+// with any other declared buffer, except that it may BE `in_place_with` (the same pointer); a DWORD buffer is 4-byte aligned in a `_dev` call (the kernels
+// read a pixel as one dword).  A pointer that is only required (a settings struct, a colour) is declared with 0 bytes.  Every refusal is PFX_ERR_INVALID,
+// "<who>: <what is wrong with which argument>"; checks of a single operation (ranges, seeds, finite settings) follow in the entry point.
+enum { PFX_ARG_IN = 0, PFX_ARG_OUT = 1, PFX_ARG_OPTIONAL = 2, PFX_ARG_DWORD = 4,
+       PFX_ARG_STAGED_OUT = PFX_ARG_IN };   // an output of the older host-buffer wrappers, written from a staged copy once every input has been read: no aliasing rule
+struct pfx_buf_arg { const void* p; size_t bytes; int flags; const char* name; };
+int pfx_check_dims(pfx_ctx* ctx, const char* who, uint32_t w, uint32_t h);   // NULL ctx: PFX_ERR_INVALID without a message; then pfx_dims_ok
+int pfx_check_args(pfx_ctx* ctx, const char* who, bool dev, std::initializer_list<pfx_buf_arg> bufs, const void* in_place_with = nullptr);   // ends in pfx_use(ctx)
+// the decision, pure, on plain integers: PFX_ARG_FINE or the kind of the first violation — every NULL first, then every alignment, then every overlap, each
+// in declaration order — with *which the offending buffer and *other the buffer it overlaps.  Exported as a test seam (not in include/pfx.h)
+enum { PFX_ARG_FINE = 0, PFX_ARG_IS_NULL = 1, PFX_ARG_MISALIGNED = 2, PFX_ARG_OVERLAPS = 3 };
+struct pfx_arg_case { uint64_t addr, bytes; int32_t flags; };
+extern "C" int pfx_int_check_args(const pfx_arg_case* bufs, int n, int dev, uint64_t in_place_with, int* which, int* other);
+
+// ---- the host-buffer tier's staging pair (pfx_ctx.cpp): the wrapper picks the staging buffer, since several `_dev` calls use some as their own scratch ----
+int pfx_stage(pfx_ctx* ctx, pfx_devbuf& buf, const void* host_or_null, size_t bytes, void** dev_ptr);   // reserve, and upload when a host pointer is given
+int pfx_unstage(pfx_ctx* ctx, void* host_dst, const pfx_devbuf& buf, size_t bytes);                     // download and sync: the one step that writes the caller's output
+inline int pfx_stage_opt(pfx_ctx* ctx, pfx_devbuf& buf, const void* host_or_null, size_t bytes, const void** dev_ptr)   // an optional mask: NULL stays NULL
+{
+    *dev_ptr = nullptr;
+    return host_or_null ? pfx_stage(ctx, buf, host_or_null, bytes, const_cast<void**>(dev_ptr)) : PFX_OK;
+}
 
 // RAII-less timing scope: records two events around a launch sequence when ctx->timing is on
 struct pfx_timer {

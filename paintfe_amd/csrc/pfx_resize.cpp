@@ -75,18 +75,34 @@ void build_axis(uint32_t n_in, uint32_t n_out, int filter, AxisTable& t)
     }
 }
 
+// what the resamplers declare: a w x h source and a dw x dh destination.  On the device the two never share a byte; the host tier works on staged copies
+int check_resample(pfx_ctx* ctx, const char* who, bool dev, const void* src, uint32_t w, uint32_t h, const void* dst, uint32_t dw, uint32_t dh)
+{
+    const size_t src_bytes = std::max<size_t>(pfx_img_bytes(w, h), 1);   // pfx_affine_transform_dev's empty source is still a pointer that dst may not contain
+    return pfx_check_args(ctx, who, dev, {{src, src_bytes, PFX_ARG_IN, "src"}, {dst, pfx_img_bytes(dw, dh), dev ? PFX_ARG_OUT : PFX_ARG_STAGED_OUT, "dst"}});
+}
+
+// the host tier: src staged in st_in, the `_dev` twin into st_out, dst written last
+template <class F>
+int staged(pfx_ctx* ctx, const uint8_t* src, size_t src_bytes, uint8_t* dst, size_t dst_bytes, F&& dev_call)
+{
+    void *d_src, *d_dst;
+    PFX_TRY(pfx_stage(ctx, ctx->st_in, src, src_bytes, &d_src));
+    PFX_TRY(pfx_stage(ctx, ctx->st_out, nullptr, dst_bytes, &d_dst));
+    PFX_TRY(dev_call(d_src, d_dst));
+    return pfx_unstage(ctx, dst, ctx->st_out, dst_bytes);
+}
+
 } // namespace
 
 extern "C" {
 
 int pfx_resize_image_dev(pfx_ctx* ctx, const void* src_dev, uint32_t w, uint32_t h, void* dst_dev, uint32_t new_w, uint32_t new_h, int filter)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, src_dev && dst_dev && src_dev != dst_dev, "pfx_resize_image_dev: bad image pointers");
-    PFX_REQUIRE(ctx, w && h && new_w && new_h && (uint64_t)w * h <= 256000000ull && (uint64_t)new_w * new_h <= 256000000ull, "pfx_resize_image_dev: bad size");
+    PFX_TRY(pfx_check_dims(ctx, "pfx_resize_image_dev", w, h));
+    PFX_TRY(pfx_check_dims(ctx, "pfx_resize_image_dev", new_w, new_h));
+    PFX_TRY(check_resample(ctx, "pfx_resize_image_dev", true, src_dev, w, h, dst_dev, new_w, new_h));
     PFX_REQUIRE(ctx, filter >= PFX_RESIZE_NEAREST && filter <= PFX_RESIZE_LANCZOS3, "pfx_resize_image_dev: unknown filter");
-    PFX_REQUIRE(ctx, !pfx_ranges_overlap(src_dev, (size_t)w * h * 4, dst_dev, (size_t)new_w * new_h * 4), "pfx_resize_image_dev: src and dst overlap");
-    PFX_TRY(pfx_use(ctx));
     if (new_w == w && new_h == h) { // the crate copies instead of resampling
         PFX_HIP(ctx, hipMemcpyAsync(dst_dev, src_dev, (size_t)w * h * 4, hipMemcpyDeviceToDevice, ctx->stream));
         return PFX_OK;
@@ -129,13 +145,10 @@ int pfx_resize_image_dev(pfx_ctx* ctx, const void* src_dev, uint32_t w, uint32_t
 int pfx_affine_transform_dev(pfx_ctx* ctx, const void* src_dev, uint32_t src_w, uint32_t src_h, void* dst_dev, uint32_t canvas_w, uint32_t canvas_h,
                              float rotation_z, float rotation_x, float rotation_y, float scale, float offset_x, float offset_y, int interpolation)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, src_dev && dst_dev && src_dev != dst_dev, "pfx_affine_transform_dev: bad image pointers");
-    PFX_REQUIRE(ctx, canvas_w && canvas_h && (uint64_t)canvas_w * canvas_h <= 256000000ull && (uint64_t)src_w * src_h <= 256000000ull,
-                "pfx_affine_transform_dev: bad size");
+    PFX_TRY(pfx_check_dims(ctx, "pfx_affine_transform_dev", canvas_w, canvas_h));
+    if (src_w && src_h) PFX_TRY(pfx_check_dims(ctx, "pfx_affine_transform_dev", src_w, src_h));   // an empty source has never been refused here (the host tier does)
+    PFX_TRY(check_resample(ctx, "pfx_affine_transform_dev", true, src_dev, src_w, src_h, dst_dev, canvas_w, canvas_h));
     PFX_REQUIRE(ctx, interpolation == PFX_RESIZE_NEAREST || interpolation == PFX_RESIZE_BILINEAR, "pfx_affine_transform_dev: nearest or bilinear only");
-    PFX_REQUIRE(ctx, !pfx_ranges_overlap(src_dev, (size_t)src_w * src_h * 4, dst_dev, (size_t)canvas_w * canvas_h * 4), "pfx_affine_transform_dev: src and dst overlap");
-    PFX_TRY(pfx_use(ctx));
     pfxk_affine_params P{};
     P.cx = (float)canvas_w * 0.5f;
     P.cy = (float)canvas_h * 0.5f;
@@ -167,26 +180,20 @@ int pfx_affine_transform_dev(pfx_ctx* ctx, const void* src_dev, uint32_t src_w, 
 int pfx_affine_transform(pfx_ctx* ctx, const uint8_t* src, uint32_t src_w, uint32_t src_h, uint8_t* dst, uint32_t canvas_w, uint32_t canvas_h,
                          float rotation_z, float rotation_x, float rotation_y, float scale, float offset_x, float offset_y, int interpolation)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, src && dst && pfx_dims_ok(src_w, src_h) && pfx_dims_ok(canvas_w, canvas_h), "pfx_affine_transform: bad arguments");
-    PFX_TRY(pfx_use(ctx));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_in, (size_t)src_w * src_h * 4));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_out, (size_t)canvas_w * canvas_h * 4));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_in.p, src, (size_t)src_w * src_h * 4));
-    PFX_TRY(pfx_affine_transform_dev(ctx, ctx->st_in.p, src_w, src_h, ctx->st_out.p, canvas_w, canvas_h, rotation_z, rotation_x, rotation_y, scale, offset_x,
-                                     offset_y, interpolation));
-    PFX_TRY(pfx_d2h(ctx, dst, ctx->st_out.p, (size_t)canvas_w * canvas_h * 4));
-    return pfx_sync(ctx);
+    PFX_TRY(pfx_check_dims(ctx, "pfx_affine_transform", src_w, src_h));
+    PFX_TRY(pfx_check_dims(ctx, "pfx_affine_transform", canvas_w, canvas_h));
+    PFX_TRY(check_resample(ctx, "pfx_affine_transform", false, src, src_w, src_h, dst, canvas_w, canvas_h));
+    return staged(ctx, src, pfx_img_bytes(src_w, src_h), dst, pfx_img_bytes(canvas_w, canvas_h), [&](const void* s, void* d) {
+        return pfx_affine_transform_dev(ctx, s, src_w, src_h, d, canvas_w, canvas_h, rotation_z, rotation_x, rotation_y, scale, offset_x, offset_y, interpolation);
+    });
 }
 
 // flip / rotate one layer image (ref: src/ops/transform.rs flip_canvas_* / rotate_canvas_* = imageops::flip_* / rotate*)
 int pfx_flip_rotate_dev(pfx_ctx* ctx, const void* src_dev, uint32_t w, uint32_t h, void* dst_dev, int op)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, src_dev && dst_dev && src_dev != dst_dev && w && h && (uint64_t)w * h <= 256000000ull, "pfx_flip_rotate_dev: bad arguments");
+    PFX_TRY(pfx_check_dims(ctx, "pfx_flip_rotate_dev", w, h));
+    PFX_TRY(check_resample(ctx, "pfx_flip_rotate_dev", true, src_dev, w, h, dst_dev, w, h));
     PFX_REQUIRE(ctx, op >= PFX_CANVAS_FLIP_HORIZONTAL && op <= PFX_CANVAS_ROTATE_180, "pfx_flip_rotate_dev: unknown operation");
-    PFX_REQUIRE(ctx, !pfx_ranges_overlap(src_dev, (size_t)w * h * 4, dst_dev, (size_t)w * h * 4), "pfx_flip_rotate_dev: src and dst overlap");
-    PFX_TRY(pfx_use(ctx));
     static const int mode_of[5] = {0, 1, 3, 4, 2}; // FLIP_H, FLIP_V, ROTATE_90CW, ROTATE_90CCW, ROTATE_180 -> k_script.hip permutation modes
     pfx_timer t(ctx, "permute");
     PFX_HIP(ctx, pfxk_permute(ctx->stream, (const uint8_t*)src_dev, (uint8_t*)dst_dev, mode_of[op], w, h));
@@ -195,30 +202,21 @@ int pfx_flip_rotate_dev(pfx_ctx* ctx, const void* src_dev, uint32_t w, uint32_t 
 
 int pfx_flip_rotate(pfx_ctx* ctx, const uint8_t* src, uint32_t w, uint32_t h, uint8_t* dst, int op)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, src && dst && pfx_dims_ok(w, h), "pfx_flip_rotate: bad arguments");
-    PFX_TRY(pfx_use(ctx));
-    const size_t bytes = (size_t)w * h * 4;
-    PFX_TRY(pfx_reserve(ctx, ctx->st_in, bytes));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_out, bytes));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_in.p, src, bytes));
-    PFX_TRY(pfx_flip_rotate_dev(ctx, ctx->st_in.p, w, h, ctx->st_out.p, op));
-    PFX_TRY(pfx_d2h(ctx, dst, ctx->st_out.p, bytes));
-    return pfx_sync(ctx);
+    PFX_TRY(pfx_check_dims(ctx, "pfx_flip_rotate", w, h));
+    PFX_TRY(check_resample(ctx, "pfx_flip_rotate", false, src, w, h, dst, w, h));
+    return staged(ctx, src, pfx_img_bytes(w, h), dst, pfx_img_bytes(w, h), [&](const void* s, void* d) { return pfx_flip_rotate_dev(ctx, s, w, h, d, op); });
 }
 
 // resize_canvas(state, new_w, new_h, anchor, fill) for one layer image (ref: src/ops/transform.rs:382-424)
 int pfx_resize_canvas_dev(pfx_ctx* ctx, const void* src_dev, uint32_t w, uint32_t h, void* dst_dev, uint32_t new_w, uint32_t new_h, uint32_t anchor_x,
                           uint32_t anchor_y, const uint8_t fill[4])
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, src_dev && dst_dev && src_dev != dst_dev && w && h && new_w && new_h && (uint64_t)new_w * new_h <= 256000000ull,
-                "pfx_resize_canvas_dev: bad arguments");
-    PFX_REQUIRE(ctx, !pfx_ranges_overlap(src_dev, (size_t)w * h * 4, dst_dev, (size_t)new_w * new_h * 4), "pfx_resize_canvas_dev: src and dst overlap");
-    PFX_TRY(pfx_use(ctx));
+    PFX_TRY(pfx_check_dims(ctx, "pfx_resize_canvas_dev", new_w, new_h));
+    PFX_REQUIRE(ctx, w && h, "pfx_resize_canvas_dev: bad image size");   // w * h has never been bounded here (the host tier does)
+    PFX_TRY(check_resample(ctx, "pfx_resize_canvas_dev", true, src_dev, w, h, dst_dev, new_w, new_h));
     const int32_t off_x = anchor_x == 0 ? 0 : (anchor_x == 1 ? ((int32_t)new_w - (int32_t)w) / 2 : (int32_t)new_w - (int32_t)w);
     const int32_t off_y = anchor_y == 0 ? 0 : (anchor_y == 1 ? ((int32_t)new_h - (int32_t)h) / 2 : (int32_t)new_h - (int32_t)h);
-    const uint32_t rgba = fill ? ((uint32_t)fill[0] | ((uint32_t)fill[1] << 8) | ((uint32_t)fill[2] << 16) | ((uint32_t)fill[3] << 24)) : 0u;
+    const uint32_t rgba = fill ? pfx_pack_rgba8(fill) : 0u;
     pfx_timer t(ctx, "resize_canvas");
     PFX_HIP(ctx, pfxk_recanvas(ctx->stream, (const uint8_t*)src_dev, (uint8_t*)dst_dev, w, h, new_w, new_h, off_x, off_y, rgba));
     return PFX_OK;
@@ -227,28 +225,20 @@ int pfx_resize_canvas_dev(pfx_ctx* ctx, const void* src_dev, uint32_t w, uint32_
 int pfx_resize_canvas(pfx_ctx* ctx, const uint8_t* src, uint32_t w, uint32_t h, uint8_t* dst, uint32_t new_w, uint32_t new_h, uint32_t anchor_x,
                       uint32_t anchor_y, const uint8_t fill[4])
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, src && dst && pfx_dims_ok(w, h) && pfx_dims_ok(new_w, new_h), "pfx_resize_canvas: bad arguments");
-    PFX_TRY(pfx_use(ctx));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_in, (size_t)w * h * 4));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_out, (size_t)new_w * new_h * 4));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_in.p, src, (size_t)w * h * 4));
-    PFX_TRY(pfx_resize_canvas_dev(ctx, ctx->st_in.p, w, h, ctx->st_out.p, new_w, new_h, anchor_x, anchor_y, fill));
-    PFX_TRY(pfx_d2h(ctx, dst, ctx->st_out.p, (size_t)new_w * new_h * 4));
-    return pfx_sync(ctx);
+    PFX_TRY(pfx_check_dims(ctx, "pfx_resize_canvas", w, h));
+    PFX_TRY(pfx_check_dims(ctx, "pfx_resize_canvas", new_w, new_h));
+    PFX_TRY(check_resample(ctx, "pfx_resize_canvas", false, src, w, h, dst, new_w, new_h));
+    return staged(ctx, src, pfx_img_bytes(w, h), dst, pfx_img_bytes(new_w, new_h),
+                  [&](const void* s, void* d) { return pfx_resize_canvas_dev(ctx, s, w, h, d, new_w, new_h, anchor_x, anchor_y, fill); });
 }
 
 int pfx_resize_image(pfx_ctx* ctx, const uint8_t* src, uint32_t w, uint32_t h, uint8_t* dst, uint32_t new_w, uint32_t new_h, int filter)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, src && dst && pfx_dims_ok(w, h) && pfx_dims_ok(new_w, new_h), "pfx_resize_image: bad arguments");
-    PFX_TRY(pfx_use(ctx));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_in, (size_t)w * h * 4));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_out, (size_t)new_w * new_h * 4));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_in.p, src, (size_t)w * h * 4));
-    PFX_TRY(pfx_resize_image_dev(ctx, ctx->st_in.p, w, h, ctx->st_out.p, new_w, new_h, filter));
-    PFX_TRY(pfx_d2h(ctx, dst, ctx->st_out.p, (size_t)new_w * new_h * 4));
-    return pfx_sync(ctx);
+    PFX_TRY(pfx_check_dims(ctx, "pfx_resize_image", w, h));
+    PFX_TRY(pfx_check_dims(ctx, "pfx_resize_image", new_w, new_h));
+    PFX_TRY(check_resample(ctx, "pfx_resize_image", false, src, w, h, dst, new_w, new_h));
+    return staged(ctx, src, pfx_img_bytes(w, h), dst, pfx_img_bytes(new_w, new_h),
+                  [&](const void* s, void* d) { return pfx_resize_image_dev(ctx, s, w, h, d, new_w, new_h, filter); });
 }
 
 } // extern "C"

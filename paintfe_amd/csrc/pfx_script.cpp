@@ -63,7 +63,7 @@ bool png_decode(const std::vector<uint8_t>& file, std::vector<uint8_t>& rgba, ui
         else if (!std::memcmp(type, "IEND", 4)) break;
         pos += 12 + (size_t)len;
     }
-    if (!w || !h || (uint64_t)w * h > 256000000ull) { why = "bad dimensions"; return false; }
+    if (!pfx_dims_ok(w, h)) { why = "bad dimensions"; return false; }
     int ch;
     switch (color_type) { case 0: ch = 1; break; case 2: ch = 3; break; case 3: ch = 1; break; case 4: ch = 2; break; case 6: ch = 4; break; default: why = "bad colour type"; return false; }
     const bool depth_ok = (color_type == 0 && (bit_depth == 1 || bit_depth == 2 || bit_depth == 4 || bit_depth == 8 || bit_depth == 16)) ||

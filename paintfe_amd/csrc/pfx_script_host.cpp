@@ -628,7 +628,7 @@ int pfx_script_execute(pfx_ctx* ctx, const char* source, const uint8_t* pixels, 
     if (result) std::memset(result, 0, sizeof *result);
     if (out) *out = nullptr;
     if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, source && pixels && out && w && h && (uint64_t)w * h <= 256000000ull, "pfx_script_execute: bad arguments");
+    PFX_REQUIRE(ctx, source && pixels && out && pfx_dims_ok(w, h), "pfx_script_execute: bad arguments");
     PFX_TRY(pfx_use(ctx));
     const size_t bytes = (size_t)w * h * 4;
     PFX_TRY(pfx_reserve(ctx, ctx->st_in, bytes));

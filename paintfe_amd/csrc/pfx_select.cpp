@@ -12,22 +12,13 @@
 
 namespace {
 
-inline size_t align256(size_t n) { return (n + 255u) & ~(size_t)255u; }
-inline uint32_t pack4(const uint8_t c[4]) { return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24); }
-
-// Rust `v as u32`
-inline uint32_t cast_u32(float v) { return !(v > 0.0f) ? 0u : (v >= 4294967296.0f ? 0xffffffffu : (uint32_t)v); }
-
-// out of a mask-to-mask op: `in` (may be NULL) may be `out` itself when same_ok, any other shared byte is refused
+// a mask-to-mask op's declaration: `in` (may be NULL unless in_required) may be `out` itself when same_ok, any other shared byte is refused
 int check_masks(pfx_ctx* ctx, const void* in, bool in_required, const void* out, bool same_ok, uint32_t w, uint32_t h, const char* who)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    if (!pfx_dims_ok(w, h)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: bad image size %ux%u", who, w, h);
-    if (!out || (in_required && !in)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: null pointer", who);
+    PFX_TRY(pfx_check_dims(ctx, who, w, h));
     const size_t px = (size_t)w * h;
-    if (in && !(same_ok && in == out) && pfx_ranges_overlap(out, px, in, px))
-        return pfx_fail(ctx, PFX_ERR_INVALID, "%s: the output overlaps the input mask%s", who, same_ok ? " (other than in place)" : "");
-    return pfx_use(ctx);
+    return pfx_check_args(ctx, who, false, {{in, px, in_required ? PFX_ARG_IN : PFX_ARG_OPTIONAL, in_required ? "mask" : "base_mask"}, {out, px, PFX_ARG_OUT, "mask_out"}},
+                          same_ok ? in : nullptr);
 }
 
 int check_combine(pfx_ctx* ctx, const void* base, const void* out, uint32_t w, uint32_t h, uint8_t mode, const char* who)
@@ -50,10 +41,10 @@ pfxk_select_shape ellipse_shape(uint32_t w, uint32_t h, float cx, float cy, floa
     pfxk_select_shape S{};
     S.kind = 1; S.cx = cx; S.cy = cy; S.rx = rx; S.ry = ry;
     if (rx <= 0.0f || ry <= 0.0f) { S.x0 = S.y0 = 1u; S.x1 = S.y1 = 0u; return S; }   // contains :83
-    S.x0 = cast_u32(floorf(fmaxf(cx - rx, 0.0f)));   // bounds :107-113; f32::max and fmaxf both drop a NaN operand
-    S.y0 = cast_u32(floorf(fmaxf(cy - ry, 0.0f)));
-    S.x1 = std::min(cast_u32(ceilf(cx + rx)), w - 1u);
-    S.y1 = std::min(cast_u32(ceilf(cy + ry)), h - 1u);
+    S.x0 = pfx_f32_as_u32(floorf(fmaxf(cx - rx, 0.0f)));   // bounds :107-113; f32::max and fmaxf both drop a NaN operand
+    S.y0 = pfx_f32_as_u32(floorf(fmaxf(cy - ry, 0.0f)));
+    S.x1 = std::min(pfx_f32_as_u32(ceilf(cx + rx)), w - 1u);
+    S.y1 = std::min(pfx_f32_as_u32(ceilf(cy + ry)), h - 1u);
     return S;
 }
 
@@ -122,41 +113,25 @@ int morph_dev(pfx_ctx* ctx, bool expand, const void* mask_dev, uint32_t w, uint3
     return PFX_OK;
 }
 
-// an op of the shape (ctx, mask_dev, w, h, <arg>, out_dev) through the staging buffers; in place on st_mask
+// a mask-to-mask op through the staging pair, in place on st_mask: `in` (NULL for a combine op without a base) is uploaded there, dev_call(in, out) runs
 template <class F>
-int staged(pfx_ctx* ctx, const uint8_t* mask, uint32_t w, uint32_t h, uint8_t* out, F&& dev_call)
+int staged(pfx_ctx* ctx, const uint8_t* in, uint32_t w, uint32_t h, uint8_t* out, F&& dev_call)
 {
     const size_t px = (size_t)w * h;
-    PFX_TRY(pfx_reserve(ctx, ctx->st_mask, px));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_mask.p, mask, px));
-    PFX_TRY(dev_call(ctx->st_mask.p));
-    PFX_TRY(pfx_d2h(ctx, out, ctx->st_mask.p, px));
-    return pfx_sync(ctx);
-}
-
-// the combine ops through the staging buffers: base (may be NULL) uploaded to st_mask, the op in place there
-template <class F>
-int staged_combine(pfx_ctx* ctx, const uint8_t* base, uint32_t w, uint32_t h, uint8_t* out, F&& dev_call)
-{
-    const size_t px = (size_t)w * h;
-    PFX_TRY(pfx_reserve(ctx, ctx->st_mask, px));
-    if (base) PFX_TRY(pfx_h2d(ctx, ctx->st_mask.p, base, px));
-    PFX_TRY(dev_call(base ? ctx->st_mask.p : nullptr, ctx->st_mask.p));
-    PFX_TRY(pfx_d2h(ctx, out, ctx->st_mask.p, px));
-    return pfx_sync(ctx);
+    void* m;
+    PFX_TRY(pfx_stage(ctx, ctx->st_mask, in, px, &m));
+    PFX_TRY(dev_call(in ? m : nullptr, m));
+    return pfx_unstage(ctx, out, ctx->st_mask, px);
 }
 
 int fill_delete_dev(pfx_ctx* ctx, void* layer_dev, const void* mask_dev, uint32_t w, uint32_t h, const uint8_t* color, bool erase, const char* who)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    if (!pfx_dims_ok(w, h)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: bad image size %ux%u", who, w, h);
-    if (!layer_dev || !mask_dev || (!erase && !color)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: null pointer", who);
+    PFX_TRY(pfx_check_dims(ctx, who, w, h));
     const size_t px = (size_t)w * h;
-    if (pfx_ranges_overlap(layer_dev, px * 4, mask_dev, px)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: the layer overlaps the mask", who);
-    if ((uintptr_t)layer_dev & 3u) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: layer_dev is not 4-byte aligned", who);
-    PFX_TRY(pfx_use(ctx));
+    PFX_TRY(pfx_check_args(ctx, who, true, {{layer_dev, px * 4, PFX_ARG_OUT | PFX_ARG_DWORD, "layer_dev"}, {mask_dev, px, PFX_ARG_IN, "mask_dev"},
+                                            {color, 0, erase ? PFX_ARG_OPTIONAL : PFX_ARG_IN, "color"}}));
     pfx_timer t(ctx, erase ? "selection_delete" : "selection_fill");
-    PFX_HIP(ctx, pfxk_select_fill(ctx->stream, (uint8_t*)layer_dev, (const uint8_t*)mask_dev, w, h, erase ? 0u : pack4(color), erase));
+    PFX_HIP(ctx, pfxk_select_fill(ctx->stream, (uint8_t*)layer_dev, (const uint8_t*)mask_dev, w, h, erase ? 0u : pfx_pack_rgba8(color), erase));
     return PFX_OK;
 }
 
@@ -178,7 +153,7 @@ int pfx_select_rect(pfx_ctx* ctx, const uint8_t* base_mask, uint32_t w, uint32_t
                     uint8_t combine_mode, uint8_t* mask_out)
 {
     PFX_TRY(check_combine(ctx, base_mask, mask_out, w, h, combine_mode, "pfx_select_rect"));
-    return staged_combine(ctx, base_mask, w, h, mask_out,
+    return staged(ctx, base_mask, w, h, mask_out,
                           [&](const void* b, void* o) { return pfx_select_rect_dev(ctx, b, w, h, min_x, min_y, max_x, max_y, combine_mode, o); });
 }
 
@@ -196,7 +171,7 @@ int pfx_select_ellipse(pfx_ctx* ctx, const uint8_t* base_mask, uint32_t w, uint3
                        uint8_t* mask_out)
 {
     PFX_TRY(check_combine(ctx, base_mask, mask_out, w, h, combine_mode, "pfx_select_ellipse"));
-    return staged_combine(ctx, base_mask, w, h, mask_out, [&](const void* b, void* o) { return pfx_select_ellipse_dev(ctx, b, w, h, cx, cy, rx, ry, combine_mode, o); });
+    return staged(ctx, base_mask, w, h, mask_out, [&](const void* b, void* o) { return pfx_select_ellipse_dev(ctx, b, w, h, cx, cy, rx, ry, combine_mode, o); });
 }
 
 int pfx_select_lasso_dev(pfx_ctx* ctx, const void* base_mask_dev, uint32_t w, uint32_t h, const float* points_xy, uint32_t n_points, uint8_t combine_mode,
@@ -220,7 +195,7 @@ int pfx_select_lasso(pfx_ctx* ctx, const uint8_t* base_mask, uint32_t w, uint32_
 {
     PFX_TRY(check_combine(ctx, base_mask, mask_out, w, h, combine_mode, "pfx_select_lasso"));
     PFX_TRY(check_lasso(ctx, points_xy, n_points, "pfx_select_lasso"));
-    return staged_combine(ctx, base_mask, w, h, mask_out, [&](const void* b, void* o) { return pfx_select_lasso_dev(ctx, b, w, h, points_xy, n_points, combine_mode, o); });
+    return staged(ctx, base_mask, w, h, mask_out, [&](const void* b, void* o) { return pfx_select_lasso_dev(ctx, b, w, h, points_xy, n_points, combine_mode, o); });
 }
 
 int pfx_selection_translate_dev(pfx_ctx* ctx, const void* mask_dev, uint32_t w, uint32_t h, int32_t dx, int32_t dy, void* mask_out_dev)
@@ -235,23 +210,22 @@ int pfx_selection_translate(pfx_ctx* ctx, const uint8_t* mask, uint32_t w, uint3
 {
     PFX_TRY(check_masks(ctx, mask, true, mask_out, false, w, h, "pfx_selection_translate"));
     const size_t px = (size_t)w * h;
-    PFX_TRY(pfx_reserve(ctx, ctx->st_tmp, px));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_mask, px));
-    PFX_TRY(pfx_h2d(ctx, ctx->st_tmp.p, mask, px));
-    PFX_TRY(pfx_selection_translate_dev(ctx, ctx->st_tmp.p, w, h, dx, dy, ctx->st_mask.p));
-    PFX_TRY(pfx_d2h(ctx, mask_out, ctx->st_mask.p, px));
-    return pfx_sync(ctx);
+    void *d_in, *d_out;
+    PFX_TRY(pfx_stage(ctx, ctx->st_tmp, mask, px, &d_in));
+    PFX_TRY(pfx_stage(ctx, ctx->st_mask, nullptr, px, &d_out));
+    PFX_TRY(pfx_selection_translate_dev(ctx, d_in, w, h, dx, dy, d_out));
+    return pfx_unstage(ctx, mask_out, ctx->st_mask, px);
 }
 
 int pfx_selection_feather_dev(pfx_ctx* ctx, const void* mask_dev, uint32_t w, uint32_t h, float radius, void* mask_out_dev)
 {
     PFX_TRY(check_masks(ctx, mask_dev, true, mask_out_dev, true, w, h, "pfx_selection_feather_dev"));
     PFX_TRY(check_feather(ctx, radius, "pfx_selection_feather_dev"));
-    const uint32_t passes = std::max(cast_u32(radius / 2.0f), 1u), r = std::max(cast_u32(radius), 1u);   // :1457-1458
+    const uint32_t passes = std::max(pfx_f32_as_u32(radius / 2.0f), 1u), r = std::max(pfx_f32_as_u32(radius), 1u);   // :1457-1458
     const size_t px = (size_t)w * h;
     ctx->select_passes = 0; ctx->select_launches = 0;
-    PFX_TRY(pfx_reserve(ctx, ctx->select_ws, 2u * align256(px)));   // a failure leaves mask_out untouched
-    uint8_t *a = (uint8_t*)ctx->select_ws.p, *tmp = a + align256(px);
+    PFX_TRY(pfx_reserve(ctx, ctx->select_ws, 2u * pfx_align256(px)));   // a failure leaves mask_out untouched
+    uint8_t *a = (uint8_t*)ctx->select_ws.p, *tmp = a + pfx_align256(px);
     pfx_timer t(ctx, "selection_feather");
     for (uint32_t p = 0; p < passes; ++p) {
         PFX_HIP(ctx, pfxk_select_feather_pass(ctx->stream, p == 0 ? (const uint8_t*)mask_dev : a, tmp, a, w, h, r));
@@ -265,7 +239,7 @@ int pfx_selection_feather(pfx_ctx* ctx, const uint8_t* mask, uint32_t w, uint32_
 {
     PFX_TRY(check_masks(ctx, mask, true, mask_out, true, w, h, "pfx_selection_feather"));
     PFX_TRY(check_feather(ctx, radius, "pfx_selection_feather"));
-    return staged(ctx, mask, w, h, mask_out, [&](void* m) { return pfx_selection_feather_dev(ctx, m, w, h, radius, m); });
+    return staged(ctx, mask, w, h, mask_out, [&](const void* m, void* o) { return pfx_selection_feather_dev(ctx, m, w, h, radius, o); });
 }
 
 int pfx_selection_expand_dev(pfx_ctx* ctx, const void* mask_dev, uint32_t w, uint32_t h, int32_t radius, void* mask_out_dev)
@@ -277,7 +251,7 @@ int pfx_selection_expand(pfx_ctx* ctx, const uint8_t* mask, uint32_t w, uint32_t
 {
     PFX_TRY(check_masks(ctx, mask, true, mask_out, true, w, h, "pfx_selection_expand"));
     PFX_TRY(check_morph(ctx, radius, "pfx_selection_expand"));
-    return staged(ctx, mask, w, h, mask_out, [&](void* m) { return pfx_selection_expand_dev(ctx, m, w, h, radius, m); });
+    return staged(ctx, mask, w, h, mask_out, [&](const void* m, void* o) { return pfx_selection_expand_dev(ctx, m, w, h, radius, o); });
 }
 
 int pfx_selection_contract_dev(pfx_ctx* ctx, const void* mask_dev, uint32_t w, uint32_t h, int32_t radius, void* mask_out_dev)
@@ -289,15 +263,13 @@ int pfx_selection_contract(pfx_ctx* ctx, const uint8_t* mask, uint32_t w, uint32
 {
     PFX_TRY(check_masks(ctx, mask, true, mask_out, true, w, h, "pfx_selection_contract"));
     PFX_TRY(check_morph(ctx, radius, "pfx_selection_contract"));
-    return staged(ctx, mask, w, h, mask_out, [&](void* m) { return pfx_selection_contract_dev(ctx, m, w, h, radius, m); });
+    return staged(ctx, mask, w, h, mask_out, [&](const void* m, void* o) { return pfx_selection_contract_dev(ctx, m, w, h, radius, o); });
 }
 
 int pfx_selection_bounds_dev(pfx_ctx* ctx, const void* mask_dev, uint32_t w, uint32_t h, int32_t box[4])
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    if (!pfx_dims_ok(w, h)) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_selection_bounds_dev: bad image size %ux%u", w, h);
-    if (!mask_dev || !box) return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_selection_bounds_dev: null pointer");
-    PFX_TRY(pfx_use(ctx));
+    PFX_TRY(pfx_check_dims(ctx, "pfx_selection_bounds_dev", w, h));
+    PFX_TRY(pfx_check_args(ctx, "pfx_selection_bounds_dev", true, {{mask_dev, (size_t)w * h, PFX_ARG_IN, "mask_dev"}, {box, 0, PFX_ARG_IN, "box"}}));
     PFX_TRY(pfx_reserve(ctx, ctx->d_misc, 4096));
     uint32_t got[4];
     {

@@ -14,7 +14,6 @@ constexpr float TAU = 6.28318530717958647692f, PI = 3.14159265358979323846f;
 inline int32_t f32_as_i32(float v) { return v != v ? 0 : (v >= 2147483648.0f ? 2147483647 : (v <= -2147483648.0f ? (-2147483647 - 1) : (int32_t)v)); }
 inline float rs_max(float a, float b) { return fmaxf(a, b); } // f32::max / min: the non-NaN operand, like fmaxf / fminf
 inline float rs_min(float a, float b) { return fminf(a, b); }
-inline uint32_t pack4(const uint8_t c[4]) { return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24); }
 
 const char* shape_problem(const pfx_shape* s)
 {
@@ -67,7 +66,7 @@ int shape_params(const pfx_shape* s, const int32_t box[4], pfxk_shape_params& P)
     P.hx = hx; P.hy = hy;
     P.outline_width = rs_max(s->outline_width, 0.0f);
     P.corner_radius = s->corner_radius;
-    P.primary = pack4(s->primary); P.secondary = pack4(s->secondary);
+    P.primary = pfx_pack_rgba8(s->primary); P.secondary = pfx_pack_rgba8(s->secondary);
     P.fill_mode = s->fill_mode; P.anti_alias = s->anti_alias != 0;
     auto vert = [&](int i, float x, float y) { P.verts[i][0] = x; P.verts[i][1] = y; };
     auto polygon = [&](uint32_t n) { // sdf_polygon_stretched :425, sdf_polygon :412
@@ -156,11 +155,10 @@ int shape_params(const pfx_shape* s, const int32_t box[4], pfxk_shape_params& P)
 
 int check_shape_call(pfx_ctx* ctx, const pfx_shape* shape, uint32_t w, uint32_t h, const void* buf, const char* who)
 {
-    if (!ctx) return PFX_ERR_INVALID;
-    if (!buf) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: null image pointer", who);
-    if (!pfx_dims_ok(w, h)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: bad canvas size %ux%u", who, w, h);
+    PFX_TRY(pfx_check_dims(ctx, who, w, h));
+    PFX_TRY(pfx_check_args(ctx, who, false, {{buf, pfx_img_bytes(w, h), PFX_ARG_OUT, "the image"}}));   // at most the canvas: the box is known once the shape is checked
     if (const char* why = shape_problem(shape)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: %s", who, why);
-    return pfx_use(ctx);
+    return PFX_OK;
 }
 
 int launch_shape(pfx_ctx* ctx, const pfx_shape* shape, int form, uint32_t w, uint32_t h, void* out_dev, const void* selection_dev, uint32_t mode,
@@ -199,10 +197,10 @@ int pfx_shape_rasterize(pfx_ctx* ctx, const pfx_shape* shape, uint32_t canvas_w,
     int32_t box[4];
     if (!shape_box(shape, canvas_w, canvas_h, box)) return PFX_OK;
     const size_t bytes = (size_t)box[2] * (size_t)box[3] * 4;
-    PFX_TRY(pfx_reserve(ctx, ctx->st_out, bytes));
-    PFX_TRY(pfx_shape_rasterize_dev(ctx, shape, canvas_w, canvas_h, ctx->st_out.p));
-    PFX_TRY(pfx_d2h(ctx, box_rgba, ctx->st_out.p, bytes));
-    return pfx_sync(ctx);
+    void* d_box;
+    PFX_TRY(pfx_stage(ctx, ctx->st_out, nullptr, bytes, &d_box));
+    PFX_TRY(pfx_shape_rasterize_dev(ctx, shape, canvas_w, canvas_h, d_box));
+    return pfx_unstage(ctx, box_rgba, ctx->st_out, bytes);
 }
 
 int pfx_shape_preview_dev(pfx_ctx* ctx, const pfx_shape* shape, uint32_t canvas_w, uint32_t canvas_h, void* canvas_dev)
@@ -214,11 +212,11 @@ int pfx_shape_preview_dev(pfx_ctx* ctx, const pfx_shape* shape, uint32_t canvas_
 int pfx_shape_preview(pfx_ctx* ctx, const pfx_shape* shape, uint32_t canvas_w, uint32_t canvas_h, uint8_t* canvas_rgba)
 {
     PFX_TRY(check_shape_call(ctx, shape, canvas_w, canvas_h, canvas_rgba, "pfx_shape_preview"));
-    const size_t bytes = (size_t)canvas_w * canvas_h * 4;
-    PFX_TRY(pfx_reserve(ctx, ctx->st_out, bytes));
-    PFX_TRY(pfx_shape_preview_dev(ctx, shape, canvas_w, canvas_h, ctx->st_out.p));
-    PFX_TRY(pfx_d2h(ctx, canvas_rgba, ctx->st_out.p, bytes));
-    return pfx_sync(ctx);
+    const size_t bytes = pfx_img_bytes(canvas_w, canvas_h);
+    void* d_canvas;
+    PFX_TRY(pfx_stage(ctx, ctx->st_out, nullptr, bytes, &d_canvas));
+    PFX_TRY(pfx_shape_preview_dev(ctx, shape, canvas_w, canvas_h, d_canvas));
+    return pfx_unstage(ctx, canvas_rgba, ctx->st_out, bytes);
 }
 
 int pfx_shape_draw_dev(pfx_ctx* ctx, void* layer_dev, uint32_t canvas_w, uint32_t canvas_h, const pfx_shape* shape, uint8_t blend_mode,

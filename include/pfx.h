@@ -493,6 +493,12 @@ int pfx_contours_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t 
 /* device self-test: compares the compositor's shared-reciprocal division with the compiler's IEEE f32 divide on
  * n_millions*1e6 random operand pairs drawn from the kernel's operand range; *mismatches must come back 0 */
 int pfx_selftest_division(pfx_ctx* ctx, uint64_t seed, uint32_t n_millions, uint64_t* mismatches);
+/* the same comparison with the operand range given: random significands, numerator exponents num_exp_lo .. num_exp_hi (a quarter of the
+ * numerators are 0), denominator exponents den_exp_lo .. den_exp_hi, all within -126 .. 127; n_millions in 1 .. 4096.  The library's
+ * documented range is numerators 2^-100 .. 2^20 over denominators 2^-48 .. 2^20; reduce_noise divides integers up to 195075 (exponents
+ * 0 .. 17) by its range divisor, exponents -10 .. 100. */
+int pfx_selftest_division_range(pfx_ctx* ctx, uint64_t seed, uint32_t n_millions, int32_t num_exp_lo, int32_t num_exp_hi, int32_t den_exp_lo,
+                                int32_t den_exp_hi, uint64_t* mismatches);
 /* device self-test: the three-instruction round-and-pack (`v.round().clamp(0.0, 255.0) as u8` of every pointwise op, resampler, effect and
  * warp) against the step-by-step formula for ALL 2^32 f32 bit patterns; *mismatches must come back 0.  Signalling NaNs, which no
  * arithmetic instruction produces, are counted separately (they convert to 255 instead of 0). */

@@ -46,7 +46,9 @@ PFX_DEV float div255(float x)
 // scales every intermediate exactly while nothing leaves the normal range and the residual stays representable
 // (exponent(n) >= -100 suffices), which holds for every use in this library: numerators 0 or in [2^-100, 2^20],
 // denominators in [2^-48, 2^20], checked where used.  pfx_selftest_division() re-checks 2.7e8 random pairs of the
-// kernels' operand range against `/` on the device the context runs on.
+// kernels' operand range against `/` on the device the context runs on; pfx_selftest_division_range() does so for a
+// range given by the caller (the whole range above; reduce_noise's, whose range divisor goes up to 2^100 and beyond
+// that — +inf included, where rdiv_prepare gives NaN — is divided with `/`: pfx_effects.cpp:pfx_reduce_noise_dev).
 struct rdiv { float d, y; };
 PFX_DEV rdiv rdiv_prepare(float d)
 {

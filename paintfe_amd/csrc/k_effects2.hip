@@ -199,11 +199,13 @@ PFX_DEV uint32_t fx_pixel(const uint32_t* __restrict__ src, uint32_t s, int x, i
             nb = (hash_f32(qx, qy, seed + 2u) * 2.0f - 1.0f) * strength;
         }
         return pack_round(r + nr, g + ng, b + nb, a);
-    } else if constexpr (FX == PFXK_FX2_REDUCE_NOISE) { // noise.rs:211-256; f: 2*sigma_s^2, 2*sigma_r^2+0.001; i0: r
+    } else if constexpr (FX == PFXK_FX2_REDUCE_NOISE) { // noise.rs:211-256; f: 2*sigma_s^2, 2*sigma_r^2+0.001; i0: r; i1: range term by plain '/'
         const int rad = P.i[0];
+        const bool range_ieee = P.i[1] != 0;
         float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, wsum = 0.f;
         // both divisors are per-call constants: the refined reciprocals are shared by all taps (k_common.h:rdiv, bit-identical to
-        // '/' for these operands: divisors >= 0.001, integer-valued numerators <= 195075)
+        // '/' for these operands: spatial divisor 2 .. 8192, range divisor in [0.001, 2^100), integer-valued numerators <= 195075).
+        // A range divisor outside that interval (+inf from a huge or infinite strength, NaN) takes '/': pfx_reduce_noise_dev sets i1
         const rdiv k_spatial = rdiv_prepare(P.f[0]), k_range = rdiv_prepare(P.f[1]);
         for (int dy = -rad; dy <= rad; ++dy) {
             const uint32_t* row = src + (size_t)clampi(y + dy, 0, h - 1) * w;
@@ -212,7 +214,8 @@ PFX_DEV uint32_t fx_pixel(const uint32_t* __restrict__ src, uint32_t s, int x, i
                 const float pr = ubyte0(p), pg = ubyte1(p), pb = ubyte2(p), pa = ubyte3(p);
                 const float spatial = rdiv_apply(k_spatial, (float)(dx * dx + dy * dy));
                 const float dr = r - pr, dg = g - pg, db = b - pb;
-                const float range = rdiv_apply(k_range, dr * dr + dg * dg + db * db);
+                const float nrange = dr * dr + dg * dg + db * db;
+                const float range = range_ieee ? nrange / P.f[1] : rdiv_apply(k_range, nrange);   // uniform
                 const float wt = libm_exp(-spatial - range);
                 s0 += pr * wt; s1 += pg * wt; s2 += pb * wt; s3 += pa * wt;
                 wsum += wt;
@@ -609,6 +612,27 @@ __global__ __launch_bounds__(256) void plane_expand_kernel(const uint8_t* __rest
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) rgba[i] = (uint32_t)plane[i] * 0x01010101u;
 }
 
+// k_common.h:rdiv against the compiler's IEEE divide on random significands with biased exponents drawn from [num_lo, num_hi] / [den_lo, den_hi]
+// (k_flatten.hip:rdiv_check_kernel with the ranges as arguments): out[0] += number of mismatching pairs
+__global__ __launch_bounds__(256) void rdiv_check_range_kernel(uint64_t seed, uint32_t iters, uint32_t num_lo, uint32_t num_span, uint32_t den_lo,
+                                                               uint32_t den_span, unsigned long long* out)
+{
+    uint64_t s = seed + ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 0x9E3779B97F4A7C15ull;
+    unsigned long long bad = 0;
+    for (uint32_t i = 0; i < iters; ++i) {
+        s = s * 6364136223846793005ull + 1442695040888963407ull;
+        const uint32_t a = (uint32_t)(s >> 32), b = (uint32_t)(s >> 7);
+        s = s * 6364136223846793005ull + 1442695040888963407ull;
+        const uint32_t c = (uint32_t)(s >> 32);
+        const float n = ((a & 0xC0000000u) == 0u) ? 0.0f : __builtin_bit_cast(float, (a & 0x007fffffu) | ((num_lo + (c & 0xffffu) % num_span) << 23));
+        const float d = __builtin_bit_cast(float, (b & 0x007fffffu) | ((den_lo + (c >> 16) % den_span) << 23));
+        const float q_ref = n / d;
+        const float q_fast = rdiv_apply(rdiv_prepare(d), n);
+        bad += (__builtin_bit_cast(uint32_t, q_ref) != __builtin_bit_cast(uint32_t, q_fast));
+    }
+    if (bad) atomicAdd(out, bad);
+}
+
 dim3 tile_grid(uint32_t w, uint32_t h) { return dim3((w + 63) / 64, (h + 3) / 4); }
 
 } // namespace
@@ -627,6 +651,14 @@ extern "C" hipError_t pfxk_fx(hipStream_t s, int fx, const uint8_t* d_src, uint8
         FX_CASE(PFXK_FX2_COLOR_FILTER) FX_CASE(PFXK_FX2_CONTOURS)
     default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+extern "C" hipError_t pfxk_rdiv_check_range(hipStream_t s, uint64_t seed, uint32_t blocks, uint32_t iters, uint32_t num_lo, uint32_t num_hi,
+                                            uint32_t den_lo, uint32_t den_hi, unsigned long long* d_out)
+{
+    if (num_lo < 1 || num_hi > 254 || num_lo > num_hi || den_lo < 1 || den_hi > 254 || den_lo > den_hi || blocks == 0) return hipErrorInvalidValue;
+    rdiv_check_range_kernel<<<blocks, 256, 0, s>>>(seed, iters, num_lo, num_hi - num_lo + 1, den_lo, den_hi - den_lo + 1, d_out);
     return hipGetLastError();
 }
 

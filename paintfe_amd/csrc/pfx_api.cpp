@@ -1474,6 +1474,27 @@ int pfx_selftest_division(pfx_ctx* ctx, uint64_t seed, uint32_t n_millions, uint
     return PFX_OK;
 }
 
+int pfx_selftest_division_range(pfx_ctx* ctx, uint64_t seed, uint32_t n_millions, int32_t num_exp_lo, int32_t num_exp_hi, int32_t den_exp_lo,
+                                int32_t den_exp_hi, uint64_t* mismatches)
+{
+    if (!ctx || !mismatches) return PFX_ERR_INVALID;
+    PFX_TRY(pfx_use(ctx));
+    // normal f32 exponents only, and a pair count that one launch finishes in seconds
+    PFX_REQUIRE(ctx, num_exp_lo >= -126 && num_exp_hi <= 127 && num_exp_lo <= num_exp_hi && den_exp_lo >= -126 && den_exp_hi <= 127 && den_exp_lo <= den_exp_hi,
+                "pfx_selftest_division_range: exponents must lie in -126 .. 127, lo <= hi");
+    PFX_REQUIRE(ctx, n_millions >= 1 && n_millions <= 4096, "pfx_selftest_division_range: 1 .. 4096 million pairs");
+    PFX_TRY(pfx_reserve(ctx, ctx->d_misc, 64));
+    PFX_HIP(ctx, hipMemsetAsync(ctx->d_misc.p, 0, 8, ctx->stream));
+    const uint32_t blocks = 1024, iters = (uint32_t)(((uint64_t)n_millions * 1000000ull + blocks * 256ull - 1) / (blocks * 256ull));
+    PFX_HIP(ctx, pfxk_rdiv_check_range(ctx->stream, seed, blocks, iters, (uint32_t)(num_exp_lo + 127), (uint32_t)(num_exp_hi + 127), (uint32_t)(den_exp_lo + 127),
+                                       (uint32_t)(den_exp_hi + 127), (unsigned long long*)ctx->d_misc.p));
+    unsigned long long bad = 0;
+    PFX_TRY(pfx_d2h(ctx, &bad, ctx->d_misc.p, 8));
+    PFX_TRY(pfx_sync(ctx));
+    *mismatches = bad;
+    return PFX_OK;
+}
+
 int pfx_selftest_unorm_store(pfx_ctx* ctx, uint64_t* mismatches)
 {
     if (!ctx || !mismatches) return PFX_ERR_INVALID;

@@ -283,6 +283,10 @@ int pfx_reduce_noise_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint3
     P.f[0] = 2.0f * sigma_s * sigma_s;
     P.f[1] = 2.0f * sigma_r * sigma_r + 0.001f;
     P.i[0] = r;
+    // k_common.h:rdiv is `/` while its reciprocal and residuals stay normal: here for divisors in [0.001, 2^100) (numerators are integers <= 195075;
+    // pfx_selftest_division_range re-checks exactly this range).  Beyond it — strength >= ~5e18 or infinite makes the divisor +inf, whose reciprocal
+    // step gives NaN where noise.rs:236-237 gets x / inf = 0; NaN stays NaN either way — the kernel divides with `/`
+    P.i[1] = (P.f[1] >= 0.001f && P.f[1] < 0x1p100f) ? 0 : 1;
     return launch_fx(ctx, PFXK_FX2_REDUCE_NOISE, "reduce_noise", src_dev, dst_dev, mask_dev, P, w, h);
 }
 

@@ -78,6 +78,9 @@ hipError_t pfxk_unorm_store_check(hipStream_t s, uint8_t* d_scratch1k, unsigned 
 void       pfxk_flatten_set_variant(int v); // tuning knob: 0 = shipped kernel, 1.. = experimental pixels-per-lane / occupancy variants
 // counts (into *d_out) operand pairs for which the shared-reciprocal division differs from the IEEE divide
 hipError_t pfxk_rdiv_check(hipStream_t s, uint64_t seed, uint32_t blocks, uint32_t iters, unsigned long long* d_out);
+// the same count with explicit biased-exponent ranges [lo, hi] (1 .. 254) for numerator and denominator (k_effects2.hip); a quarter of the numerators are 0
+hipError_t pfxk_rdiv_check_range(hipStream_t s, uint64_t seed, uint32_t blocks, uint32_t iters, uint32_t num_lo, uint32_t num_hi, uint32_t den_lo,
+                                 uint32_t den_hi, unsigned long long* d_out);
 hipError_t pfxk_round_pack_check(hipStream_t s, unsigned long long* d_out /* [2]: mismatches, signalling-NaN mismatches */);
 
 // ---- k_gauss.hip ---- (d_wts_tap0 points at tap 0 of a device array with pfxk_gauss_weight_pad() zeros on both sides)

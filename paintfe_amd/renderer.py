@@ -212,8 +212,8 @@ def png_decode(raw: bytes) -> np.ndarray:
 
 def _install_effects(cls):
     def make(name, marshal):
-        def core(self, img, *a, mask=None, **kw):
-            return self._img_call(getattr(self._lib, f"pfx_{name}_core"), img, *marshal(*a, **kw), mask=mask)
+        def core(self, img, *a, mask=None, out=None, **kw):
+            return self._img_call(getattr(self._lib, f"pfx_{name}_core"), img, *marshal(*a, **kw), mask=mask, out=out)
 
         def dev(self, src_ptr, dst_ptr, w, h, *a, mask_ptr=0, **kw):
             self._check(getattr(self._lib, f"pfx_{name}_dev")(self._h, C.c_void_p(src_ptr), C.c_void_p(dst_ptr), C.c_uint32(w), C.c_uint32(h),
@@ -347,17 +347,17 @@ class GpuRenderer:
     def pixelate_core(self, img, block_size: int, mask=None):
         return self._img_call(self._lib.pfx_pixelate_core, img, C.c_uint32(block_size), mask=mask)
 
-    def sharpen_core(self, img, amount: float, radius: float, mask=None):      # stylize.rs:96
-        return self._img_call(self._lib.pfx_sharpen_core, img, C.c_float(amount), C.c_float(radius), mask=mask)
+    def sharpen_core(self, img, amount: float, radius: float, mask=None, out=None):      # stylize.rs:96
+        return self._img_call(self._lib.pfx_sharpen_core, img, C.c_float(amount), C.c_float(radius), mask=mask, out=out)
 
-    def glow_core(self, img, radius: float, intensity: float, mask=None):      # stylize.rs:26
-        return self._img_call(self._lib.pfx_glow_core, img, C.c_float(radius), C.c_float(intensity), mask=mask)
+    def glow_core(self, img, radius: float, intensity: float, mask=None, out=None):      # stylize.rs:26
+        return self._img_call(self._lib.pfx_glow_core, img, C.c_float(radius), C.c_float(intensity), mask=mask, out=out)
 
-    def bokeh_blur_core(self, img, radius: float, mask=None):                   # blur.rs:22
-        return self._img_call(self._lib.pfx_bokeh_blur_core, img, C.c_float(radius), mask=mask)
+    def bokeh_blur_core(self, img, radius: float, mask=None, out=None):                   # blur.rs:22
+        return self._img_call(self._lib.pfx_bokeh_blur_core, img, C.c_float(radius), mask=mask, out=out)
 
-    def motion_blur_core(self, img, angle_deg: float, distance: float, mask=None):  # blur.rs:144
-        return self._img_call(self._lib.pfx_motion_blur_core, img, C.c_float(angle_deg), C.c_float(distance), mask=mask)
+    def motion_blur_core(self, img, angle_deg: float, distance: float, mask=None, out=None):  # blur.rs:144
+        return self._img_call(self._lib.pfx_motion_blur_core, img, C.c_float(angle_deg), C.c_float(distance), mask=mask, out=out)
 
     def adjust(self, img, op, params: Sequence[float] = (), lut=None, mask=None, sparse: int = DENSE):
         opi = ADJUST_OPS.index(op) if isinstance(op, str) else int(op)
@@ -1073,6 +1073,13 @@ class GpuRenderer:
     def selftest_division(self, seed: int, n_millions: int) -> int:
         bad = C.c_uint64(0)
         self._check(self._lib.pfx_selftest_division(self._h, C.c_uint64(seed), C.c_uint32(n_millions), C.byref(bad)))
+        return int(bad.value)
+
+    def selftest_division_range(self, seed: int, n_millions: int, num_exp, den_exp) -> int:
+        """rdiv vs `/` on operands with exponents num_exp = (lo, hi) over den_exp = (lo, hi); the mismatch count"""
+        bad = C.c_uint64(0)
+        self._check(self._lib.pfx_selftest_division_range(self._h, C.c_uint64(seed), C.c_uint32(n_millions), C.c_int32(num_exp[0]), C.c_int32(num_exp[1]),
+                                                          C.c_int32(den_exp[0]), C.c_int32(den_exp[1]), C.byref(bad)))
         return int(bad.value)
 
     def tune(self, key: str, value: int):

@@ -12,6 +12,7 @@ import pytest
 
 from . import libm_cases as LC
 from . import oracle_lib as O
+from .libm_checks import check_glibc, check_model
 
 pytestmark = pytest.mark.gpu
 EXACT, LIBM = "exact", "libm"
@@ -21,30 +22,6 @@ EXACT, LIBM = "exact", "libm"
 def gpu():
     from .backends import GpuBackend
     return GpuBackend(0)
-
-
-def check_glibc(got, ref, cls, what):
-    d = np.abs(got.astype(np.int16) - ref.astype(np.int16))
-    if cls == EXACT:
-        assert d.max() == 0, f"{what} vs glibc: max diff {int(d.max())}, {int((d.max(-1) > 0).sum())} px differ"
-    else:
-        assert d.max() <= 1, f"{what} vs glibc: max diff {int(d.max())}"
-        assert (d > 0).mean() < 1e-3, f"{what} vs glibc: {(d > 0).mean():.2e} of channels off by one"
-
-
-def check_model(got, fn, what):
-    """the device image against the device-flavour oracle; returns the oracle's ambiguous-call count"""
-    with O.libm_flavour("device"):
-        O.libm_reset()
-        model = fn()
-        amb = O.libm_ambiguous()
-    d = np.abs(got.astype(np.int16) - model.astype(np.int16))
-    px = int((d.max(-1) > 0).sum())
-    if amb == 0:
-        assert d.max() == 0, f"{what} vs device model: max diff {int(d.max())}, {px} px differ, no ambiguous call"
-    else:
-        assert d.max() <= 1 and px <= amb, f"{what} vs device model: max diff {int(d.max())}, {px} px differ, {amb} ambiguous calls"
-    return amb
 
 
 def run_effect(gpu, name, img, kw, mask, cls):

@@ -973,6 +973,65 @@ typedef struct pfx_color_removal_req {   /* ColorRemovalRequest, tools/state.rs:
 int pfx_color_removal(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_t w, uint32_t h, const pfx_color_removal_req* req, const uint8_t* selection /* may be NULL */);
 int pfx_color_removal_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, const pfx_color_removal_req* req, const void* selection_dev /* may be NULL */);
 
+/* ================= the floating selection: lift, transform, preview, commit (ref: src/ops/clipboard.rs, PasteOverlay :818) =================
+ * What the Move Pixels tool, every paste and "selection -> new transform" go through: extract_to_overlay :729 lifts the pixels, render_preview :2168 runs on
+ * every drag frame, commit :2032 stamps the transformed pixels back; render_replacement_preview :1144 and rasterize_for_clipboard :1048 are the same sampling
+ * with other windows.  All geometry travels in one descriptor, and pfx_overlay_geometry is the one place that derives sizes and boxes from it.  Images are
+ * RGBA8, `source` is source_w * source_h, the layer / base / preview are doc_w * doc_h; the overwrite mask is source_w * source_h bytes.  Everything is in the
+ * bit-exact class: every f32 expression as the reference writes it, one rounding per operation, round() half away from zero, `as u32` / `as i32` saturating
+ * and truncating; cos and sin of the rotation are taken once per call on the host (cosf / sinf).  The scale step is pfx_resize_image_dev's; the one-byte
+ * overwrite mask follows that resize's NEAREST rule (an index lookup).
+ * Refused with PFX_ERR_INVALID: a NULL descriptor or required pointer, a float of the descriptor that is not finite, interpolation outside PFX_RESIZE_*,
+ * a document, a source or a scaled size (max(round(source * scale), 1)) outside the document limit — the reference would try to allocate it —, a clipboard
+ * raster window outside that limit, an RGBA8 device pointer that is not 4-byte aligned, any overlap of an output with another buffer other than
+ * out == base.  Outputs are untouched on any error: every refusal comes before the first launch.
+ * Two deviations, both in pfx_overlay_preview_dev: in the translation-only path the reference wraps (origin + scaled size) as u32 when that sum is negative
+ * and then indexes outside the scaled image (a panic) — here such an overlay draws nothing; and the reference's row strips keep the column in 16 bits —
+ * here the true column is drawn on documents wider than 65535. */
+typedef struct pfx_overlay {           /* PasteOverlay :818-837, plus the sizes */
+    uint32_t source_w, source_h;       /* the un-transformed source image (and its overwrite mask) */
+    uint32_t doc_w, doc_h;             /* the layer / canvas */
+    float    center_x, center_y;       /* canvas coordinates of the source's centre */
+    float    rotation;                 /* radians */
+    float    scale_x, scale_y;
+    float    anchor_x, anchor_y;       /* anchor_offset, relative to the centre */
+    int32_t  interpolation;            /* PFX_RESIZE_*: Interpolation::to_filter, transform.rs:29-58 */
+    uint8_t  anti_aliasing, overwrite_transparent, _pad[2];
+} pfx_overlay;
+typedef struct pfx_overlay_geom {
+    uint32_t scaled_w, scaled_h;       /* max(round(source * scale), 1) as u32 */
+    float    cos_r, sin_r;
+    float    corners[8];               /* corners_canvas :1313: x, y of top-left, top-right, bottom-left, bottom-right, from the unrounded half size */
+    uint32_t row_start, row_end, col_start, col_end;   /* the commit box :2054-2069, inclusive; empty when a start is above its end */
+    uint32_t has_bounds, bounds[4];    /* transformed_bounds :939-959: x0, y0, x1, y1 (exclusive ends), has_bounds 0 = None */
+    int32_t  raster_col, raster_row;   /* rasterize_for_clipboard's window :1060-1081, not clipped to the document */
+    uint32_t raster_w, raster_h;       /* 0 where the reference returns None; saturates at UINT32_MAX */
+} pfx_overlay_geom;
+/* host only, no context: the derived quantities of a descriptor; the calls below start with it */
+int pfx_overlay_geometry(const pfx_overlay* ov, pfx_overlay_geom* out);
+/* commit (out == base: only pixels of the commit box are written) or render_replacement_preview (any other out: a copy of base, then the same stamp; every
+ * byte is written).  Per pixel of the box: the inverse rotation about centre + anchor, the +-0.5 window (the tight one without anti-aliasing), sample_bilinear
+ * :2326 or the truncating nearest pick, then either the overwrite (overwrite_transparent, where overwrite_mask_allows :1150) or alpha_blend :2368 of samples
+ * with alpha > 0.  The mask is read only when overwrite_transparent is set */
+int pfx_overlay_commit_dev(pfx_ctx* ctx, const pfx_overlay* ov, const void* source_dev, const void* overwrite_mask_dev /* may be NULL */, const void* base_dev,
+                           void* out_dev);
+int pfx_overlay_commit(pfx_ctx* ctx, const pfx_overlay* ov, const uint8_t* source, const uint8_t* overwrite_mask /* may be NULL */, const uint8_t* base, uint8_t* out);
+/* render_preview: a doc_w * doc_h image, every byte written, (0, 0, 0, 0) where nothing is drawn: ready for pfx_flatten_preview_dev.  Always the NEAREST
+ * scale; |rotation| < 1e-4 and |anchor| < 1e-3 take the translation-only path with the rounded integer origin, anything else the general one (tight window,
+ * nearest pick); only pixels with alpha > 0 are drawn.  interpolation is checked but not used; anti_aliasing and overwrite_transparent are not looked at */
+int pfx_overlay_preview_dev(pfx_ctx* ctx, const pfx_overlay* ov, const void* source_dev, void* preview_dev);
+/* rasterize_for_clipboard: commit's sampler into the geometry's raster window (raster_w * raster_h RGBA8, tightly packed), no blending: samples with
+ * alpha > 0 are stored over zero.  *has_pixels (host memory; the call waits for the device) is 0 where the reference returns None */
+int pfx_overlay_rasterize_dev(pfx_ctx* ctx, const pfx_overlay* ov, const void* source_dev, void* out_dev, int* has_pixels);
+/* extract_to_overlay.  With a selection (doc_w * doc_h bytes): clip = the box of {selection > 0}, tightly packed, the layer's pixel where selection > 0 and
+ * zero elsewhere; clip_mask = 255 / 0 likewise; the layer is blanked as pfx_selection_delete_dev does (grey-aware); *out = the box's size, its centre
+ * (min + size / 2) and PasteOverlay::new's defaults (scale 1, rotation 0, Bilinear, anti-aliasing on, overwrite off).  Without one: the whole layer becomes
+ * the clip, the layer becomes zero, clip_mask is not written (and may be NULL), the centre is the document's.  The reference's None — nothing selected, or no
+ * selection and no alpha anywhere in the layer — is PFX_OK with out->source_w == 0 and nothing written.  clip_dev and clip_mask_dev need room for the
+ * whole document; the call waits for the device once */
+int pfx_overlay_extract_dev(pfx_ctx* ctx, void* layer_dev, const void* selection_dev /* may be NULL */, uint32_t doc_w, uint32_t doc_h, void* clip_dev,
+                            void* clip_mask_dev, pfx_overlay* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,19 @@ class ColorRemoval(C.Structure):   # pfx_color_removal_req
                 ("_pad", C.c_uint8 * 3)]
 
 
+class Overlay(C.Structure):   # pfx_overlay
+    _fields_ = [("source_w", C.c_uint32), ("source_h", C.c_uint32), ("doc_w", C.c_uint32), ("doc_h", C.c_uint32), ("center_x", C.c_float), ("center_y", C.c_float),
+                ("rotation", C.c_float), ("scale_x", C.c_float), ("scale_y", C.c_float), ("anchor_x", C.c_float), ("anchor_y", C.c_float),
+                ("interpolation", C.c_int32), ("anti_aliasing", C.c_uint8), ("overwrite_transparent", C.c_uint8), ("_pad", C.c_uint8 * 2)]
+
+
+class OverlayGeom(C.Structure):   # pfx_overlay_geom
+    _fields_ = [("scaled_w", C.c_uint32), ("scaled_h", C.c_uint32), ("cos_r", C.c_float), ("sin_r", C.c_float), ("corners", C.c_float * 8),
+                ("row_start", C.c_uint32), ("row_end", C.c_uint32), ("col_start", C.c_uint32), ("col_end", C.c_uint32),
+                ("has_bounds", C.c_uint32), ("bounds", C.c_uint32 * 4), ("raster_col", C.c_int32), ("raster_row", C.c_int32),
+                ("raster_w", C.c_uint32), ("raster_h", C.c_uint32)]
+
+
 _lib = None
 
 

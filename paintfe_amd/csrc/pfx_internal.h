@@ -101,6 +101,7 @@ struct pfx_ctx {
     pfx_devbuf colorkey_ws;                             // the colour remover's two u16 level maps, smoothness above one ring chunk only (pfx_colorkey.cpp)
     uint64_t colorkey_flood_passes = 0;                 // of the context's last pfx_color_removal[_dev]; pfx_int_colorkey_last reads them
     uint32_t colorkey_ring_launches = 0, colorkey_launches = 0;
+    pfx_devbuf overlay_ws;                              // the floating selection's scaled source (pfx_overlay.cpp); pfx_resize_image_dev itself uses fx_a and st_tmp
 };
 
 // ---- error plumbing ----

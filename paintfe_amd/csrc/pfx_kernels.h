@@ -393,6 +393,31 @@ hipError_t pfxk_ckey_apply_core(hipStream_t s, const uint8_t* d_src, const uint8
 hipError_t pfxk_ckey_rings(hipStream_t s, const uint8_t* d_core, const uint16_t* d_lin, const uint8_t* d_sel /* may be NULL */, uint16_t* d_lout, const uint8_t* d_src,
                            uint8_t* d_dst, uint32_t w, uint32_t h, uint32_t base, uint32_t k, const pfxk_ckey* P);
 
+// ---- k_overlay.hip ---- the floating selection (src/ops/clipboard.rs: commit :2032, render_preview :2168, rasterize_for_clipboard :1048, extract_to_overlay :729); host side: pfx_overlay.cpp
+// What the sampling kernels share, all derived on the host (pfx_overlay_geometry): the anchor in canvas coordinates, cos / sin of the rotation, origin =
+// centre - scaled / 2, the scaled image and the source it was scaled from with ratio = (f32)source / (f32)scaled — the NEAREST rule of the resize's
+// per-axis tables is source index min(floor((o + 0.5) * ratio), source - 1), weight 1 — and the window: box_w x box_h pixels from (x0, y0), written at
+// row pitch `pitch` pixels from pixel (x0 - out_x0, y0 - out_y0) of the output
+typedef struct pfxk_overlay {
+    float ax, ay, cos_r, sin_r, origin_x, origin_y, ratio_x, ratio_y;
+    uint32_t scaled_w, scaled_h, source_w, source_h;
+    int32_t x0, y0, out_x0, out_y0;
+    uint32_t box_w, box_h, pitch;
+} pfxk_overlay;
+// commit's stamp over the box, in place on d_img (the document): aa = the +-0.5 window and sample_bilinear, else the tight window and the nearest pick;
+// overwrite 0 = alpha_blend only, 1 = every sample overwrites, 2 = where d_mask (source_w x source_h bytes, through the NEAREST rule) allows.  d_scaled is scaled_w x scaled_h
+hipError_t pfxk_overlay_commit(hipStream_t s, const uint8_t* d_scaled, const uint8_t* d_mask, uint8_t* d_img, const pfxk_overlay* P, int aa, int overwrite);
+// rasterize_for_clipboard: the same sampler, samples with alpha > 0 stored into d_out (zeroed by the caller); *d_any |= 1 when one was
+hipError_t pfxk_overlay_rasterize(hipStream_t s, const uint8_t* d_scaled, uint8_t* d_out, const pfxk_overlay* P, int aa, uint32_t* d_any);
+// render_preview over every pixel of the doc_w x doc_h output, NEAREST-scaled straight from d_source.  translate: the pixels of [x0, x0 + box_w) x [y0, y0 +
+// box_h) are scaled pixel (x - out_x0, y - out_y0), out_x0 / out_y0 being the rounded origin; else the general path over the box.  Zero where nothing is drawn
+hipError_t pfxk_overlay_preview(hipStream_t s, const uint8_t* d_source, uint8_t* d_out, uint32_t doc_w, uint32_t doc_h, const pfxk_overlay* P, int translate);
+// extract_to_overlay with a selection: clip / clip_mask over the box (x0, y0, bw x bh), tightly packed
+hipError_t pfxk_overlay_lift(hipStream_t s, const uint8_t* d_layer, const uint8_t* d_sel, uint8_t* d_clip, uint8_t* d_clip_mask, uint32_t w, uint32_t x0, uint32_t y0,
+                             uint32_t bw, uint32_t bh);
+// *d_any |= 1 when a pixel of the n has alpha > 0
+hipError_t pfxk_overlay_any_alpha(hipStream_t s, const uint8_t* d_img, size_t n, uint32_t* d_any);
+
 #ifdef __cplusplus
 }
 #endif

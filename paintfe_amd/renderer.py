@@ -180,6 +180,26 @@ def _color_removal(seed, tolerance, smoothness, contiguous):
     return r
 
 
+INTERPOLATIONS = ["nearest", "bilinear", "bicubic", "lanczos3"]         # PFX_RESIZE_*
+
+
+def overlay(source_size, doc_size, center, rotation: float = 0.0, scale=(1.0, 1.0), anchor=(0.0, 0.0), interpolation="bilinear", anti_aliasing: bool = True,
+            overwrite_transparent: bool = False) -> _lib.Overlay:
+    """a pfx_overlay: PasteOverlay's transform plus the sizes, (w, h) each; the defaults are PasteOverlay::new's"""
+    interp = INTERPOLATIONS.index(interpolation) if isinstance(interpolation, str) else int(interpolation)
+    return _lib.Overlay(int(source_size[0]), int(source_size[1]), int(doc_size[0]), int(doc_size[1]), float(center[0]), float(center[1]), float(rotation),
+                        float(scale[0]), float(scale[1]), float(anchor[0]), float(anchor[1]), interp, int(bool(anti_aliasing)), int(bool(overwrite_transparent)))
+
+
+def overlay_geometry(ov: _lib.Overlay) -> _lib.OverlayGeom:
+    """pfx_overlay_geometry: the scaled size, cos / sin, corners, commit box, transformed bounds and clipboard raster window of an overlay; host only"""
+    g = _lib.OverlayGeom()
+    st = _lib.load().pfx_overlay_geometry(C.byref(ov), C.byref(g))
+    if st != _lib.OK:
+        raise PfxError(st, "pfx_overlay_geometry refused the descriptor")
+    return g
+
+
 def script_check(source: str, w: int = 64, h: int = 64):
     """Language-only evaluation of a script (no device, no image functions; ref: compile_script, scripting.rs:1489): returns
     the console lines or raises PfxError with .line / .col."""
@@ -835,6 +855,38 @@ class GpuRenderer:
         (pfx_int_colorkey_last; for tests and profiles)"""
         return int(self._lib.pfx_int_colorkey_last(self._h, C.c_int(which)))
 
+    # ---- the floating selection (pfx_overlay_*): `ov` is an `overlay(...)` descriptor ----
+    def overlay_commit(self, ov, source, base, overwrite_mask=None) -> np.ndarray:
+        """PasteOverlay::commit on a copy of `base` (doc_h, doc_w, 4); source is (source_h, source_w, 4), overwrite_mask (source_h, source_w) or None"""
+        src, b = _u8(source), _u8(base)
+        m = None if overwrite_mask is None else _u8(overwrite_mask)
+        out = np.empty_like(b)
+        self._check(self._lib.pfx_overlay_commit(self._h, C.byref(ov), _p(src), _p(m), _p(b), _p(out)))
+        return out
+
+    def overlay_commit_dev(self, ov, source_ptr: int, base_ptr: int, out_ptr: int, overwrite_mask_ptr: int = 0):
+        """out_ptr == base_ptr is commit (only the commit box is written); any other out_ptr is render_replacement_preview (every byte written)"""
+        self._check(self._lib.pfx_overlay_commit_dev(self._h, C.byref(ov), C.c_void_p(source_ptr), C.c_void_p(overwrite_mask_ptr or None), C.c_void_p(base_ptr),
+                                                     C.c_void_p(out_ptr)))
+
+    def overlay_preview_dev(self, ov, source_ptr: int, preview_ptr: int):
+        """render_preview: a doc_w x doc_h RGBA8 image, every byte written, ready for composite_with_preview_dev"""
+        self._check(self._lib.pfx_overlay_preview_dev(self._h, C.byref(ov), C.c_void_p(source_ptr), C.c_void_p(preview_ptr)))
+
+    def overlay_rasterize_dev(self, ov, source_ptr: int, out_ptr: int) -> bool:
+        """rasterize_for_clipboard into overlay_geometry(ov)'s raster window (raster_w x raster_h RGBA8); False = the reference's None"""
+        has = C.c_int(0)
+        self._check(self._lib.pfx_overlay_rasterize_dev(self._h, C.byref(ov), C.c_void_p(source_ptr), C.c_void_p(out_ptr), C.byref(has)))
+        return bool(has.value)
+
+    def overlay_extract_dev(self, layer_ptr: int, selection_ptr: int, w: int, h: int, clip_ptr: int, clip_mask_ptr: int = 0):
+        """extract_to_overlay: lifts the selected pixels (selection_ptr 0: the whole layer) into clip / clip_mask, blanks them on the layer and returns the
+        overlay descriptor, or None where the reference does (nothing selected / nothing on the layer; the layer is then untouched)"""
+        ov = _lib.Overlay()
+        self._check(self._lib.pfx_overlay_extract_dev(self._h, C.c_void_p(layer_ptr), C.c_void_p(selection_ptr or None), C.c_uint32(w), C.c_uint32(h),
+                                                      C.c_void_p(clip_ptr), C.c_void_p(clip_mask_ptr or None), C.byref(ov)))
+        return ov if ov.source_w else None
+
     # ------------------------------------------------------------------ script front-end
     def resize_image(self, img, new_w: int, new_h: int, filter="bilinear"):   # transform.rs:347 (imageops::resize)
         src = _u8(img)
@@ -853,6 +905,12 @@ class GpuRenderer:
                                                    C.c_float(rotation_z), C.c_float(rotation_x), C.c_float(rotation_y), C.c_float(scale),
                                                    C.c_float(offset[0]), C.c_float(offset[1]), _enum(RESIZE_FILTERS, interpolation)))
         return dst
+
+    def affine_transform_dev(self, src_ptr: int, w: int, h: int, dst_ptr: int, canvas_w: int, canvas_h: int, rotation_z=0.0, rotation_x=0.0, rotation_y=0.0,
+                             scale=1.0, offset=(0.0, 0.0), interpolation="bilinear"):
+        self._check(self._lib.pfx_affine_transform_dev(self._h, C.c_void_p(src_ptr), C.c_uint32(w), C.c_uint32(h), C.c_void_p(dst_ptr), C.c_uint32(canvas_w),
+                                                       C.c_uint32(canvas_h), C.c_float(rotation_z), C.c_float(rotation_x), C.c_float(rotation_y), C.c_float(scale),
+                                                       C.c_float(offset[0]), C.c_float(offset[1]), _enum(RESIZE_FILTERS, interpolation)))
 
     def flip_rotate(self, img, op):                                            # transform.rs flip_canvas_* / rotate_canvas_*
         src = _u8(img)

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import sys
 
@@ -256,6 +257,24 @@ def main() -> int:
                       note=f"seed at the centre, tolerance 8: {r.colorkey_last(0)} flood passes, {r.colorkey_last(1)} ring launches, {r.colorkey_last(4)} launches; 14 B/px = the map (4 + 1) "
                            f"and the last launch (1 + 4 + 4), the flood's and the earlier ring launches' traffic not counted; the timer starts after the seed's read-back; mean of 3 calls")
     del ck, ckd
+    # ---------------- the floating selection (k_overlay.hip): commit is a gather of four taps plus the document pixel read and written in place; the affine
+    # transform (bilinear) is the existing kernel nearest to it — a four-tap gather and one write — and runs beside it at the same size and angle
+    from paintfe_amd import overlay
+    full = dict(source_size=(w, h), doc_size=(w, h), center=(w / 2.0, h / 2.0))
+    ov_rot = overlay(rotation=0.3, **full)
+    timed("overlay: commit, full-canvas source, rotation 0.3, anti-aliased, blend", ["overlay_commit"], lambda: r.overlay_commit_dev(ov_rot, s, d, d), px, 12,
+          "in place; 12 B/px = 4 gathered (four taps, mostly cached) + 4 read + 4 written, over the whole canvas although the rotated box's corners hold no sample; random alpha: nearly every pixel takes the general blend with its division")
+    timed("overlay orientation: affine transform, bilinear, rotation_z 0.3 rad, same size", ["affine"],
+          lambda: r.affine_transform_dev(s, w, h, d, w, h, rotation_z=math.degrees(0.3)), px, 8, "4 gathered + 4 written")
+    ov_flat = overlay(rotation=0.3, anti_aliasing=False, overwrite_transparent=True, **full)
+    timed("overlay: commit, rotation 0.3, no anti-aliasing, overwrite", ["overlay_commit"], lambda: r.overlay_commit_dev(ov_flat, s, d, d), px, 8, "one tap, no blend: 4 gathered + 4 written")
+    timed("overlay: preview, rotation 0.3 (the general path)", ["overlay_preview"], lambda: r.overlay_preview_dev(ov_rot, s, d), px, 8, "every drag frame: one nearest tap, the whole canvas written")
+    ov_move = overlay(source_size=(w, h), doc_size=(w, h), center=(w / 2.0 + 301.0, h / 2.0 - 77.0))
+    timed("overlay: preview, translation only", ["overlay_preview"], lambda: r.overlay_preview_dev(ov_move, s, d), px, 8)
+    ov_clip, ov_cmask = torch.empty_like(src), torch.empty_like(mask)
+    timed("overlay: extract through a 70 % selection", ["overlay_extract"], lambda: r.overlay_extract_dev(d, m, w, h, ov_clip.data_ptr(), ov_cmask.data_ptr()), px, 19,
+          "lift (1 + 4 read, 4 + 1 written) + the grey-aware delete (1 + 4 read, 4 written where selected); the bounds launch and its read-back come before the timer")
+    del ov_clip, ov_cmask
     src_h = src.cpu().numpy()
     import time
     r.execute_script_sync("map_channels(|r, g, b, a| [255 - r, g / 2, (b * 3 + a) / 4, a]);", src_h)   # warm: a process's first launch of k_script's code object loads it (~1 ms)

@@ -667,6 +667,8 @@ PFX_DEV void stream_layer_groups(float (&acc)[PX][4], const float (&t)[PX][4], u
 // Scalar work per layer is kept short — the CU's one scalar unit serves all 24 waves, and round 4's counters show it more than half busy: the descriptor
 // pointer advances instead of being indexed, nothing clamps it (the host appends PFXK_DESC_PAD copies of the last descriptor: pfx_api.cpp:build_stack; a pass reads up to descriptor le + 2; what is
 // fetched through them or beyond `le` is never blended), the whole 32-byte descriptor comes with one scalar load, the resource needs no mask.
+// Since round 7 this loop and srt_early serve only the PFX_SRT_PIPE 0 and TR builds: the shipped path is srt_layers_pipe / srt_early_pipe below,
+// which request nothing past le - 1 and read no descriptor past `le`.
 // NOBLEND (diagnostic, pfx_tune "dle_stats" = 2): the load stream without the arithmetic — results are garbage.
 // TR (diagnostic build, pfx_tune "dle_stats" = 4): wave clock spent in front of each blend waiting for the layer's pixels (an explicit s_waitcnt bracketed by
 // s_memtime) and inside the blends, accumulated into tr[0] / tr[1]
@@ -850,6 +852,220 @@ PFX_DEV void srt_early(float (&acc)[1][4], const pfxk_layer_desc* __restrict__ l
 #define PFX_EARLY_NB 2   // 8K x 32 layers (S2), one box: 2 sets 0.990-1.010 ms, 4 sets 1.013-1.018, 6 / 8 sets 1.04-1.05, srt_layers<1> 1.044-1.048 (profiles/r05_tuning.md)
 #endif
 
+// ---- the pipelined passes (round 7): no load without a use, no phase opening on a cold fetch --------------------------------------------------------
+// srt_layers / srt_early above request one layer ahead unconditionally, so each pass ends on one or two requests for layers it never blends, and each
+// phase of a unit (classification, early pass, natural pass) opens by issuing a load and waiting for it.  Here the loops are peeled instead: the steady
+// state still has every fetch outside a conditional (exact s_waitcnt counts), the last one or two layers run in a tail that requests nothing past
+// le - 1, and the tail's free slot — the other register set is dead there — carries the NEXT phase's first request:
+//   part 1  natural pass -> the topmost candidate's alpha of the wave's next unit (PX format_x loads, lane order), consumed by the next classification;
+//   part 2  early pass   -> the next early group's first layer (eg > 1); the first group's first request goes out as soon as the dealt offsets are read;
+//   part 3  early pass of the last group -> layer r for all PX groups into the natural pass's set 0, which then starts "already in flight".
+// A slot's loads are never behind a branch of their own: a request that sits in one arm of a join makes the compiler wait for vmcnt(0) in front of the
+// blend that follows, which would expose exactly the round trip the slot is meant to hide.  Where a slot has nothing to ask for (no next unit, or the
+// next unit does not probe) the alpha loads go through a resource of zero records: range-checked out, no memory access.
+// Descriptors: a pass reads up to descriptor `le` (the one behind its last layer; for the natural pass the first PFXK_DESC_PAD copy), nothing beyond.
+// PFX_SRT_PIPE 0 = the loops above (development A/B); PFX_SRT_PIPE_PARTS 1 / 2 / 3 = parts 1, 1 + 2, 1 + 2 + 3.
+// The TR build (s_memtime brackets with hard-coded vmcnt counts) is pinned to the loops above: its counts describe their in-flight loads.
+// Shipped: parts 1 + 2 (8K x 32 layers, S2, six alternations on one box: flatten 0.994-1.003 -> 0.984-0.989 ms, VMEM reads 1.297 -> 1.240 * 10^7 per launch).
+// Part 3 is NOT shipped: it measured neutral (0.980-0.993 against 0.980-0.987 for parts 1 + 2 in one run) and removes no read; it has the longest live range
+// and in the present build costs two VGPR spills.  profiles/r07_tuning.md has the numbers, profiles/srt_pipe_ab.txt the raw runs.
+#ifndef PFX_SRT_PIPE
+#define PFX_SRT_PIPE 1
+#endif
+#ifndef PFX_SRT_PIPE_PARTS
+#define PFX_SRT_PIPE_PARTS 2
+#endif
+
+// The descriptor table is read through the constant address space: a wave-uniform load from it is a scalar load by construction.  (Through the
+// global pointer the compiler must first prove that no store of the kernel can reach the table, and gives up on that proof once the peeled loops have
+// doubled the blend sites: the descriptors then arrive by vector loads and every fetch becomes a waterfall loop over a VGPR resource.)
+typedef const __attribute__((address_space(4))) pfxk_layer_desc* pfx_desc_cptr;
+PFX_DEV pfx_desc_cptr desc_const(const pfxk_layer_desc* p) { return (pfx_desc_cptr)p; }
+PFX_DEV void desc_read(pfxk_layer_desc& d, pfx_desc_cptr p) { d.pixels = p->pixels; d.mode = p->mode; d.adj_off = p->adj_off; }
+
+// Natural pass, layers [lb, le), le > lb.  `t` = the two register sets (the caller's: set 0 may arrive in flight, requested under the early pass);
+// `slot` issues the tail slot's loads (the caller's: it builds its resource there, from scratch — anything it kept in SGPRs across the pass would push
+// the kernel's scalar state, which is at its budget, into VGPR lanes, and every v_readlane of a reload is a VALU instruction).
+template <int PX, bool NOBLEND, class Slot>
+PFX_DEV void srt_layers_pipe(float (&acc)[PX][4], float (&t)[2][PX][4], const pfxk_layer_desc* __restrict__ layers, uint32_t lb, uint32_t le, uint32_t bytes,
+                             int (&voff)[PX], uint32_t s1, uint32_t seg, float4* s_x, uint32_t* s_v, uint32_t& st_moves, bool inflight, Slot&& slot)
+{
+    uint32_t m[2], o[2];
+    pfx_desc_cptr nptr = desc_const(layers + lb);
+    pfxk_layer_desc nd;            // raster layers: adj_off = bits of the clamped opacity (pfx_kernels.h)
+    desc_read(nd, nptr);
+    uint32_t next_attempt = lb < s1 ? s1 : lb + 1u;
+    uint32_t lead = 0u;            // leading groups known to be opaque wave-wide
+    bool recount = true;           // ... to be re-taken in front of the next blend (start of the pass; behind Xor / Overwrite, which can lower alpha)
+    auto fetch = [&](auto SET) {
+        constexpr int S = decltype(SET)::value;
+        m[S] = nd.mode; o[S] = nd.adj_off;
+        const pfx_v4i rs = make_rsrc_canonical(nd.pixels, bytes, PFX_RSRC_UNORM8X4);
+#pragma unroll
+        for (int j = 0; j < PX; ++j) {
+            const pfx_v4f v = pfx_buffer_load_format_v4f32(rs, voff[j], 0, 0);
+            t[S][j][0] = v.x; t[S][j][1] = v.y; t[S][j][2] = v.z; t[S][j][3] = v.w;
+        }
+        nptr += 1;
+        desc_read(nd, nptr);
+    };
+    auto blend = [&](auto SET) {
+        constexpr int S = decltype(SET)::value;
+        if constexpr (NOBLEND) {
+#pragma unroll
+            for (int j = 0; j < PX; ++j) { acc[j][0] += t[S][j][0]; acc[j][1] += t[S][j][1]; acc[j][2] += t[S][j][2]; acc[j][3] = t[S][j][3]; }
+        } else if constexpr (PX == 1 && !PFX_TWO_STAGE) {
+            stream_layer<1>(acc, t[S], m[S], __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(o[S])));
+        } else {
+            if (recount) { lead = count_lead<PX>(acc); recount = false; }
+            stream_layer_groups<PX>(acc, t[S], m[S], __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(o[S])), lead);
+            recount = m[S] == M_XOR || m[S] == M_OVERWRITE;
+        }
+    };
+    auto redeal = [&](auto SET, uint32_t K) {          // in front of layer K < le, whose pixels are in flight in set SET (srt_layers' re-deal)
+        constexpr int S = decltype(SET)::value;
+#if !PFX_SRT_REDEAL
+        return;
+#endif
+        if constexpr (PX == 1 || NOBLEND) return;
+        if (K != next_attempt) return;
+        next_attempt = K + seg;
+        uint64_t mo[PX];
+        uint32_t co[PX], total_o = 0u, now = 0u;
+        bool run = true;
+#pragma unroll
+        for (int j = 0; j < PX; ++j) {
+            mo[j] = __ballot(acc[j][3] == 1.0f);
+            co[j] = (uint32_t)__popcll(mo[j]);
+            total_o += co[j];
+            run = run && co[j] == 64u;
+            now += run ? 1u : 0u;
+        }
+        lead = now; recount = false;                   // the count is a by-product of the attempt
+        if (total_o / 64u <= now) return;              // grouping the opaque accumulators would not complete another leading group
+        lead = total_o / 64u;
+        const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); // recomputed: not worth a register across the blends
+        uint32_t slot[PX], pre_o = 0u, pre_n = total_o;
+#pragma unroll
+        for (int j = 0; j < PX; ++j) {
+            const uint32_t rank_o = __builtin_amdgcn_mbcnt_hi((uint32_t)(mo[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mo[j], 0u));
+            slot[j] = acc[j][3] == 1.0f ? pre_o + rank_o : pre_n + (lane - rank_o);
+            pre_o += co[j]; pre_n += 64u - co[j];
+        }
+#pragma unroll
+        for (int j = 0; j < PX; ++j) { s_x[slot[j]] = make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]); s_v[slot[j]] = (uint32_t)voff[j]; }
+        wave_lds_sync();
+#pragma unroll
+        for (int j = 0; j < PX; ++j) {
+            const float4 a = s_x[64u * j + lane];
+            acc[j][0] = a.x; acc[j][1] = a.y; acc[j][2] = a.z; acc[j][3] = a.w;
+            voff[j] = (int)s_v[64u * j + lane];
+        }
+        wave_lds_sync();
+#pragma unroll
+        for (int j = 0; j < PX; ++j) s_x[slot[j]] = make_float4(t[S][j][0], t[S][j][1], t[S][j][2], t[S][j][3]);
+        wave_lds_sync();
+#pragma unroll
+        for (int j = 0; j < PX; ++j) {
+            const float4 a = s_x[64u * j + lane];
+            t[S][j][0] = a.x; t[S][j][1] = a.y; t[S][j][2] = a.z; t[S][j][3] = a.w;
+        }
+        wave_lds_sync();
+        st_moves += 1u;
+    };
+    if (inflight) { m[0] = nd.mode; o[0] = nd.adj_off; nptr += 1; desc_read(nd, nptr); }   // set 0 holds layer lb, requested under the early pass
+    else fetch(std::integral_constant<int, 0>{});
+    // steady state: two layers per trip, every fetch unconditional; the last one or two layers run in the tail, whose free slot carries the alpha loads
+    uint32_t li = lb;                                  // at the top: layer li is in flight or landed in set 0
+    for (; li + 2u < le; li += 2) {
+        fetch(std::integral_constant<int, 1>{}); blend(std::integral_constant<int, 0>{}); redeal(std::integral_constant<int, 1>{}, li + 1);
+        fetch(std::integral_constant<int, 0>{}); blend(std::integral_constant<int, 1>{}); redeal(std::integral_constant<int, 0>{}, li + 2);
+    }
+    if (li + 1u < le) {
+        fetch(std::integral_constant<int, 1>{}); blend(std::integral_constant<int, 0>{}); redeal(std::integral_constant<int, 1>{}, li + 1);
+        slot(); blend(std::integral_constant<int, 1>{});
+    } else { slot(); blend(std::integral_constant<int, 0>{}); }
+}
+
+// The early groups' passes, layers [lb, le) with le > lb on groups 0 .. eg - 1 (one pixel per lane, two four-register sets), each ending on layer le - 1.
+// A group that is not the last asks for the next group's first layer in its tail slot; the last group asks there for layer le = r on all PX groups into
+// the natural pass's set 0 (part 3).  The two kinds of group are separate instantiations, so neither slot is a conditional.
+template <int PX, bool NOBLEND>
+PFX_DEV void srt_early_pipe(float (&acc)[PX][4], float (&tn)[2][PX][4], const pfxk_layer_desc* __restrict__ layers, uint32_t lb, uint32_t le, uint32_t bytes,
+                            const int (&voff)[PX], uint32_t eg)
+{
+    float t[2][1][4], a1[1][4];
+    uint32_t m[2], o[2];
+    pfx_desc_cptr nptr = desc_const(layers + lb);
+    pfxk_layer_desc nd;
+    desc_read(nd, nptr);
+    uint32_t lead = 0u;
+    bool recount = true;
+    int v = voff[0];
+    auto fetch = [&](auto SET) {
+        constexpr int S = decltype(SET)::value;
+        m[S] = nd.mode; o[S] = nd.adj_off;
+        const pfx_v4i rs = make_rsrc_canonical(nd.pixels, bytes, PFX_RSRC_UNORM8X4);
+        const pfx_v4f x = pfx_buffer_load_format_v4f32(rs, v, 0, 0);
+        t[S][0][0] = x.x; t[S][0][1] = x.y; t[S][0][2] = x.z; t[S][0][3] = x.w;
+        nptr += 1;
+        desc_read(nd, nptr);
+    };
+    auto blend = [&](auto SET) {
+        constexpr int S = decltype(SET)::value;
+        if constexpr (NOBLEND) { a1[0][0] += t[S][0][0]; a1[0][1] += t[S][0][1]; a1[0][2] += t[S][0][2]; a1[0][3] = t[S][0][3]; }
+        else {
+            if (recount) { lead = count_lead<1>(a1); recount = false; }
+            stream_layer_groups<1>(a1, t[S], m[S], __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(o[S])), lead);
+            recount = true; // one compare: cheaper than tracking which modes can change a single group's class
+        }
+    };
+    auto slot = [&](auto LAST, auto FREE, uint32_t g) {
+        if constexpr (decltype(LAST)::value) {
+            if constexpr (PFX_SRT_PIPE_PARTS >= 3) {   // nd = descriptor le: layer r, where every pixel of the unit goes on
+                const pfx_v4i rs = make_rsrc_canonical(nd.pixels, bytes, PFX_RSRC_UNORM8X4);
+#pragma unroll
+                for (int j = 0; j < PX; ++j) {
+                    const pfx_v4f x = pfx_buffer_load_format_v4f32(rs, voff[j], 0, 0);
+                    tn[0][j][0] = x.x; tn[0][j][1] = x.y; tn[0][j][2] = x.z; tn[0][j][3] = x.w;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int j = 1; j < PX; ++j) v = g + 1u == (uint32_t)j ? voff[j] : v;
+            nptr = desc_const(layers + lb);
+            desc_read(nd, nptr);
+            fetch(FREE);
+        }
+    };
+    auto group = [&](auto LAST, uint32_t g) {          // at the top: the group's layer lb is in flight in set 0
+        a1[0][0] = a1[0][1] = a1[0][2] = a1[0][3] = 0.0f;
+        recount = true;
+        bool moved = false;
+        uint32_t li = lb;
+        for (; li + 2u < le; li += 2) {
+            fetch(std::integral_constant<int, 1>{}); blend(std::integral_constant<int, 0>{});
+            fetch(std::integral_constant<int, 0>{}); blend(std::integral_constant<int, 1>{});
+        }
+        if (li + 1u < le) {
+            fetch(std::integral_constant<int, 1>{}); blend(std::integral_constant<int, 0>{});
+            slot(LAST, std::integral_constant<int, 0>{}, g); blend(std::integral_constant<int, 1>{});
+        } else { slot(LAST, std::integral_constant<int, 1>{}, g); blend(std::integral_constant<int, 0>{}); moved = true; }
+        if (!decltype(LAST)::value && moved) {         // the next group's first layer was requested into set 1: it starts in set 0
+#pragma unroll
+            for (int c = 0; c < 4; ++c) t[0][0][c] = t[1][0][c];
+            m[0] = m[1]; o[0] = o[1];
+        }
+#pragma unroll
+        for (int j = 0; j < PX; ++j)                   // selects: conditional stores are merged into one store through a selected pointer, and that puts acc in
+#pragma unroll                                         // scratch; a branch and four moves per arm (kept apart by an empty asm) would save 8 VALU per unit but
+            for (int c = 0; c < 4; ++c) acc[j][c] = g == (uint32_t)j ? a1[0][c] : acc[j][c];   // doubles the v_readlane reloads of spilled SGPRs (57 -> 103)
+    };
+    fetch(std::integral_constant<int, 0>{});
+    for (uint32_t g = 0; g + 1u < eg; ++g) group(std::false_type{}, g);
+    group(std::true_type{}, eg - 1u);
+}
+
 // ---- class sorting inside a unit (round 4) -------------------------------------------------------------------------------------------------------
 // Two per-pixel properties decide how much a layer costs a pixel: whether the layer is dead for it (below its topmost reset layer: dead-layer
 // elimination, above) and whether its accumulator is opaque (out_a == 1: no division, no base-alpha products, no alpha re-quantisation, no select for
@@ -916,6 +1132,19 @@ __global__ __launch_bounds__(64) PFX_SRT_ATTR void flatten_srt_kernel(const pfxk
     // TR: [0] classification, [1] deal + early passes, [2] natural pass, [3] back to lane order + store; waits / blends of the early ([4], [5]) and natural ([6], [7]) passes
     unsigned long long tph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tc0 = 0;
     const unsigned long long t_birth = TR ? __builtin_amdgcn_s_memtime() : 0ull;
+    // the pipelined passes (srt_layers_pipe): the topmost candidate's alpha of a unit is requested in the tail of the previous unit's natural pass;
+    // the stream's first unit asks here (it always probes)
+    constexpr bool PIPE = PFX_SRT_PIPE != 0 && !TR && PFX_EARLY_NB == 2;
+    float pa[PX];
+    auto alpha_ahead = [&](uint32_t unit, bool wanted) {   // PX format_x loads, lane order; !wanted: zero records, range-checked out without a memory access
+        const uint32_t top_layer = C.n >= 4u ? C.layer[3] : (C.n == 3u ? C.layer[2] : (C.n == 2u ? C.layer[1] : C.layer[0])); // selects: an index would put C in scratch
+        const pfx_v4i ra = make_rsrc(desc_const(layers + top_layer)->pixels, wanted ? bytes : 0u, PFX_RSRC_ALPHA8);
+        const uint32_t l = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        const int vo = (int)((base_px + unit * UPX + l) * 4u);
+#pragma unroll
+        for (int j = 0; j < PX; ++j) pa[j] = pfx_buffer_load_format_f32(ra, vo + j * 256, 0, 0);
+    };
+    if constexpr (PIPE) alpha_ahead(0u, true);
     for (uint32_t u = 0; u < nu; ++u) {
         if constexpr (TR) tc0 = __builtin_amdgcn_s_memtime();
         int voff[PX];
@@ -935,12 +1164,19 @@ __global__ __launch_bounds__(64) PFX_SRT_ATTR void flatten_srt_kernel(const pfxk
 #pragma unroll
         for (int i = 3; i >= 0; --i) {
             if ((uint32_t)i < C.n && !done) {
-                const pfx_v4i ra = make_rsrc(layers[C.layer[i]].pixels, bytes, PFX_RSRC_ALPHA8);
+                float a[PX];
+                if (PIPE && (uint32_t)i + 1u == C.n) {   // the topmost candidate: in flight since the previous unit's natural pass (or the prologue)
+#pragma unroll
+                    for (int j = 0; j < PX; ++j) a[j] = pa[j];
+                } else {                                 // further candidates on demand: only where the topmost leaves a pixel unclassified
+                    const pfx_v4i ra = make_rsrc(layers[C.layer[i]].pixels, bytes, PFX_RSRC_ALPHA8);
+#pragma unroll
+                    for (int j = 0; j < PX; ++j) a[j] = pfx_buffer_load_format_f32(ra, voff[j], 0, 0);
+                }
                 bool all_found = true;
 #pragma unroll
                 for (int j = 0; j < PX; ++j) {
-                    const float a = pfx_buffer_load_format_f32(ra, voff[j], 0, 0);
-                    const bool hit = C.kind[i] ? (a == 1.0f) : (a != 0.0f);
+                    const bool hit = C.kind[i] ? (a[j] == 1.0f) : (a[j] != 0.0f);
                     cls[j] = (cls[j] == 0u && hit) ? (uint32_t)(i + 1) : cls[j];
                     all_found = all_found && cls[j] != 0u;
                 }
@@ -975,6 +1211,10 @@ __global__ __launch_bounds__(64) PFX_SRT_ATTR void flatten_srt_kernel(const pfxk
             else if (++probe_fail >= 2u) { probe_fail = 0u; skip_left = 14u; }
         }
         if constexpr (TR) { const unsigned long long c = __builtin_amdgcn_s_memtime(); tph[0] += c - tc0; tc0 = c; }
+        [[maybe_unused]] float tnat[2][PX][4];   // PIPE: the natural pass's register sets (set 0 may be requested under the early pass)
+        [[maybe_unused]] bool nat_inflight = false;
+        // PIPE: does the stream's next unit exist and probe?  (skip_left is final for it here: the back-off is resolved one unit ahead)
+        [[maybe_unused]] const bool issue_next = u + 1u < nu && skip_left == 0u;
         if (best != 0u) {
             // ---- early pixels to the leading groups (the accumulators are all (0,0,0,0): only the offsets move), then their layers [s_u, r) ----
             st_cunits += 1u;
@@ -992,6 +1232,13 @@ __global__ __launch_bounds__(64) PFX_SRT_ATTR void flatten_srt_kernel(const pfxk
 #pragma unroll
             for (int j = 0; j < PX; ++j) voff[j] = (int)s_v[64u * j + lane];
             wave_lds_sync();
+            if constexpr (PIPE && PFX_SRT_PIPE_PARTS >= 2) {
+#if PFX_SRT_PRIO
+                __builtin_amdgcn_s_setprio(PFX_SRT_PRIO & 3);
+#endif
+                srt_early_pipe<PX, NOBLEND>(acc, tnat, layers, s_u, r, bytes, voff, eg);
+                nat_inflight = PFX_SRT_PIPE_PARTS >= 3;
+            } else
             for (uint32_t g = 0; g < eg; ++g) {       // eg < PX: one group at a time through the one-pixel-per-lane loop (one call site)
                 int v1[1];
                 float a1[1][4] = {{0.0f, 0.0f, 0.0f, 0.0f}};
@@ -1021,6 +1268,10 @@ __global__ __launch_bounds__(64) PFX_SRT_ATTR void flatten_srt_kernel(const pfxk
 #if PFX_SRT_PRIO
         __builtin_amdgcn_s_setprio((PFX_SRT_PRIO >> 2) & 3);
 #endif
+        if constexpr (PIPE) {
+            srt_layers_pipe<PX, NOBLEND>(acc, tnat, layers, r, n_layers, bytes, voff, s1, P.seg, s_x, s_v, st_moves, nat_inflight,
+                                         [&]() { alpha_ahead(u + 1u, issue_next); });
+        } else
         srt_layers<PX, NOBLEND, TR>(acc, layers, r, n_layers, bytes, voff, s1, P.seg, s_x, s_v, st_moves, tph + 6);
         if constexpr (TR) { const unsigned long long c = __builtin_amdgcn_s_memtime(); tph[2] += c - tc0; tc0 = c; }
         // A dealt unit goes back to lane order before it is stored (three 16-byte LDS writes and reads per unit): whole-line stores instead of three

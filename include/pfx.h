@@ -1032,6 +1032,81 @@ int pfx_overlay_rasterize_dev(pfx_ctx* ctx, const pfx_overlay* ov, const void* s
 int pfx_overlay_extract_dev(pfx_ctx* ctx, void* layer_dev, const void* selection_dev /* may be NULL */, uint32_t doc_w, uint32_t doc_h, void* clip_dev,
                             void* clip_mask_dev, pfx_overlay* out);
 
+/* ================= text layer styles: shadow, outline, fills, inner shadow (ref: src/ops/text_layer/effects.rs, apply_text_effects) =================
+ * What TextLayerData::rasterize (data_impl.rs:132-194) runs behind the glyphs after every keystroke and style-slider tick: it takes the rasterised text as
+ * RGBA8 and returns RGBA8.  Fonts, layout, glyph rasterisation and text warps are not here.  All sizes and parameters travel in one descriptor that mirrors
+ * TextEffects (core.rs:299-364); `flags` says which of its five Options are Some.  coverage = alpha / 255.0f.  The stages, in this order, each through the
+ * integer composite_over of effects.rs:47-71 (u32 arithmetic) onto an output that starts as zero:
+ *   1 shadow        the coverage shifted by (round(offset_x), round(offset_y)) (half away from zero, then a saturating `as i32`; zero from outside), dilated
+ *                   by `spread` when spread > 0.5, alpha = round(mask * colour alpha); blur_radius > 0.5: the (colour rgb, alpha) image through
+ *                   parallel_gaussian_blur_pub (sigma = blur_radius; the bit-exact Gaussian, unless the context opted out with pfx_tune "gauss_fast_effects")
+ *                   and composite_over of the blurred pixel — with clamp-to-edge and one colour everywhere the blurred rgb is the colour itself, so rows that
+ *                   allow it blur the alpha plane alone —; else the colour with that alpha, alpha 0 skipped.
+ *   2 outline       Outside at radius = width, Center at radius = width * 0.5 (its outside half only; render_outline_inside is never reached for Center);
+ *                   nothing when radius <= 0: alpha = clamp(dilated - coverage, 0, 1) * (colour alpha / 255.0), skipped below 1.0 / 255.0, then round(. * 255).
+ *   3 fill          the gradient when its flag is set; else the texture when its flag is set; else the text itself.  Gradient: to_radians, cosf / sinf once
+ *                   per call on the host, scale.max(1.0), proj = ((x - offset[0]) * cos + (y - offset[1]) * sin) / scale, t = proj.rem_euclid(1.0) (fmodf,
+ *                   + 1 when negative: can be exactly 1.0) with `repeat`, else clamp(proj, 0, 1); rgb = round(start * (1 - t) + end * t), alpha =
+ *                   round((start alpha * (1 - t) + end alpha * t) * coverage).  Texture: scale.max(0.01), tx = ((fmodf((x - offset[0]) / scale, tex_w) + tex_w)
+ *                   as usize) % tex_w, likewise ty; rgb of that texel, alpha = min(round(coverage * 255), texel alpha).  The texture is decoded RGBA8
+ *                   (tex_w * tex_h, tightly packed; pfx_png_decode_mem decodes a PNG); a zero tex_w or tex_h is the plain text fill.  Both skip coverage < 1 / 255.
+ *   4 inside outline  radius = width: alpha = clamp(coverage - eroded, 0, 1) * (colour alpha / 255.0) as in 2, eroded = max(1 - dilate(1 - coverage), 0).
+ *   5 inner shadow  1 - coverage shifted like the shadow's (1.0 from outside the image); blur_radius > 0.5: alpha = round(that * colour alpha), the image
+ *                   blurred as in 1, then round(blurred alpha * coverage); else round((that * colour alpha) * coverage).  Both skip coverage < 1 / 255.
+ * With no flag set the result is composite_over(text, zeros).
+ * The dilation is dilate_mask :167-214: the maximum over the disc dx * dx + dy * dy <= radius * radius (f32, the square rounded once) clipped to the image,
+ * starting from 0; rows reach ceil(radius), so a radius of 0.5 changes nothing.  Coverage is monotone in alpha, so the device takes the disc's maximum (the
+ * erosion: minimum) on the u8 alpha plane, row span by row span, not tap by tap.
+ * Everything is in the bit-exact class: every f32 expression as the reference writes it, one rounding per operation, round() half away from zero.
+ * Refused with PFX_ERR_INVALID, before the first launch and with outputs untouched: a NULL descriptor or required pointer; a float of the descriptor that is
+ * not finite (whatever the flags say); an outline position outside PFX_TEXT_OUTLINE_*; width * height outside the document limit; with the texture flag and a
+ * non-zero tex_w * tex_h, a NULL texture or a texture outside the document limit; a device pointer that is not 4-byte aligned; any overlap of the output
+ * with an input (nothing runs in place).  PFX_ERR_UNSUPPORTED, likewise before the first launch: a dilation radius (the outline's, the shadow's spread above
+ * 0.5) whose ceil is above PFX_TEXT_FX_MAX_RADIUS — the editor's sliders reach 50 and 30 —, and a blur radius beyond what the Gaussian accepts
+ * (ceil(3 * blur_radius) above its tile limit, as pfx_gaussian_blur_dev).
+ * One deviation, in the region rule: the reference computes `bx as i32 - pad_px as i32` and `bx + bw + pad_px` in 32 bits, which wrap or panic for a padding
+ * of 2^31 and more; here that arithmetic is 64 bits wide, so such a padding just covers the canvas. */
+#define PFX_TEXT_FX_OUTLINE       1u
+#define PFX_TEXT_FX_SHADOW        2u
+#define PFX_TEXT_FX_INNER_SHADOW  4u
+#define PFX_TEXT_FX_GRADIENT_FILL 8u
+#define PFX_TEXT_FX_TEXTURE_FILL  16u
+#define PFX_TEXT_FX_MAX_RADIUS    64
+enum { PFX_TEXT_OUTLINE_INSIDE = 0, PFX_TEXT_OUTLINE_OUTSIDE = 1, PFX_TEXT_OUTLINE_CENTER = 2 };   /* OutlinePosition, core.rs:314-319 */
+typedef struct pfx_text_fx {              /* TextEffects core.rs:299-364, plus the image size (C has one namespace: pfx_text_effects is the host-tier call below) */
+    uint32_t width, height;               /* of the text image; the canvas for pfx_text_effects_plan and pfx_text_layer_effects_dev */
+    uint32_t flags;                       /* PFX_TEXT_FX_*: which members below are Some */
+    uint8_t  outline_color[4];            /* OutlineEffect */
+    float    outline_width;
+    int32_t  outline_position;            /* PFX_TEXT_OUTLINE_* */
+    uint8_t  shadow_color[4];             /* ShadowEffect */
+    float    shadow_offset_x, shadow_offset_y, shadow_blur_radius, shadow_spread;
+    uint8_t  inner_color[4];              /* InnerShadowEffect */
+    float    inner_offset_x, inner_offset_y, inner_blur_radius;
+    uint8_t  gradient_start[4], gradient_end[4];   /* GradientFillEffect */
+    float    gradient_angle_degrees, gradient_scale, gradient_offset[2];
+    uint32_t gradient_repeat;             /* 0 / 1 */
+    uint32_t tex_w, tex_h;                /* TextureFillEffect: the decoded texture's size */
+    float    texture_scale, texture_offset[2];
+} pfx_text_fx;
+typedef struct pfx_text_region {          /* what data_impl.rs:132-172 derives from the text's tight bounds */
+    uint32_t x, y, w, h;                  /* the bounds grown by pad_px and clamped to the canvas; all zero when there is no visible text */
+    uint32_t pad_px;                      /* max(ceil(pad) as u32, 4) */
+    uint32_t full_canvas;                 /* 1: region area * 2 >= canvas area, the effects run on the whole canvas */
+} pfx_text_region;
+/* apply_text_effects on a width * height image: text and out are RGBA8 of that size, every byte of out is written; asynchronous on the context's stream */
+int pfx_text_effects_dev(pfx_ctx* ctx, const pfx_text_fx* fx, const void* text_dev, const void* texture_dev /* may be NULL */, void* out_dev);
+int pfx_text_effects(pfx_ctx* ctx, const pfx_text_fx* fx, const uint8_t* text, const uint8_t* texture /* may be NULL */, uint8_t* out);
+/* host only, no context: the padding and region rule.  bounds = x, y, w, h of the pixels with alpha > 0 (find_tight_bounds_rgba, raster.rs:23-41), inside the
+ * canvas; a zero w or h is "no visible text": *out is all zero.  pad = max(|ox| + |oy| + 3 * blur + spread of the shadow, ceil(outline width) + 2, |ox| +
+ * |oy| + 3 * blur of the inner shadow), over the members whose flag is set, in f32 as written; pad_px = max(ceil(pad) as u32 (saturating), 4) */
+int pfx_text_effects_plan(const pfx_text_fx* fx, const uint32_t bounds[4], pfx_text_region* out);
+/* data_impl.rs:132-194 for a canvas-sized text image (width * height of the descriptor): the tight bounds of alpha > 0 on the device (one wait for the
+ * device), the plan, the effects on the cropped region or on the whole canvas, the result blitted into an otherwise zero canvas: every byte of out is written.
+ * No visible text is a zero canvas and PFX_OK.  *region_out (host memory) receives the plan */
+int pfx_text_layer_effects_dev(pfx_ctx* ctx, const pfx_text_fx* fx, const void* text_dev, const void* texture_dev /* may be NULL */, void* out_dev,
+                               pfx_text_region* region_out /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,21 @@ class OverlayGeom(C.Structure):   # pfx_overlay_geom
                 ("raster_w", C.c_uint32), ("raster_h", C.c_uint32)]
 
 
+class TextEffects(C.Structure):   # pfx_text_fx
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32),
+                ("outline_color", C.c_uint8 * 4), ("outline_width", C.c_float), ("outline_position", C.c_int32),
+                ("shadow_color", C.c_uint8 * 4), ("shadow_offset_x", C.c_float), ("shadow_offset_y", C.c_float), ("shadow_blur_radius", C.c_float),
+                ("shadow_spread", C.c_float),
+                ("inner_color", C.c_uint8 * 4), ("inner_offset_x", C.c_float), ("inner_offset_y", C.c_float), ("inner_blur_radius", C.c_float),
+                ("gradient_start", C.c_uint8 * 4), ("gradient_end", C.c_uint8 * 4), ("gradient_angle_degrees", C.c_float), ("gradient_scale", C.c_float),
+                ("gradient_offset", C.c_float * 2), ("gradient_repeat", C.c_uint32),
+                ("tex_w", C.c_uint32), ("tex_h", C.c_uint32), ("texture_scale", C.c_float), ("texture_offset", C.c_float * 2)]
+
+
+class TextRegion(C.Structure):   # pfx_text_region
+    _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("pad_px", C.c_uint32), ("full_canvas", C.c_uint32)]
+
+
 _lib = None
 
 
@@ -122,5 +137,11 @@ def load() -> C.CDLL:
     lib.pfx_tolerance_threshold.argtypes = [C.c_float]
     lib.pfx_int_select_span.restype = C.c_int
     lib.pfx_int_select_span.argtypes = [C.c_uint32, C.c_uint32]
+    lib.pfx_int_textfx_span.restype = C.c_int
+    lib.pfx_int_textfx_span.argtypes = [C.c_float, C.c_int32]
+    lib.pfx_text_effects_dev.argtypes = [C.c_void_p, C.POINTER(TextEffects), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pfx_text_effects.argtypes = [C.c_void_p, C.POINTER(TextEffects), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pfx_text_effects_plan.argtypes = [C.POINTER(TextEffects), C.POINTER(C.c_uint32), C.POINTER(TextRegion)]
+    lib.pfx_text_layer_effects_dev.argtypes = [C.c_void_p, C.POINTER(TextEffects), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TextRegion)]
     _lib = lib
     return lib

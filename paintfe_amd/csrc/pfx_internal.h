@@ -102,6 +102,7 @@ struct pfx_ctx {
     uint64_t colorkey_flood_passes = 0;                 // of the context's last pfx_color_removal[_dev]; pfx_int_colorkey_last reads them
     uint32_t colorkey_ring_launches = 0, colorkey_launches = 0;
     pfx_devbuf overlay_ws;                              // the floating selection's scaled source (pfx_overlay.cpp); pfx_resize_image_dev itself uses fx_a and st_tmp
+    pfx_devbuf textfx_ws;                               // the text styles' planes, blur images and cropped region (pfx_textfx.cpp); the Gaussian itself uses st_tmp
 };
 
 // ---- error plumbing ----
@@ -251,6 +252,10 @@ extern "C" int pfx_int_colorkey_last(pfx_ctx* ctx, int which);
 extern "C" int pfx_int_select_last(pfx_ctx* ctx, int which);
 // floor(sqrt(r^2 - k^2)) as the grow / shrink kernels' span table holds it; -1 = k > r or r beyond the cap
 extern "C" int pfx_int_select_span(uint32_t r, uint32_t k);
+
+// the half-width of row dy of dilate_mask's disc as the text styles' span table holds it (pfx_textfx.cpp); -1 = the row is skipped, |dy| > ceil(radius), or
+// a radius the module refuses (not in include/pfx.h)
+extern "C" int pfx_int_textfx_span(float radius, int32_t dy);
 
 // blur_with_selection on device-resident images (pfx_api.cpp); mask_host may be NULL (= no selection)
 int pfx_int_blur_with_selection_dev(pfx_ctx* ctx, const void* d_src, void* d_dst, uint32_t w, uint32_t h, float sigma,

@@ -418,6 +418,46 @@ hipError_t pfxk_overlay_lift(hipStream_t s, const uint8_t* d_layer, const uint8_
 // *d_any |= 1 when a pixel of the n has alpha > 0
 hipError_t pfxk_overlay_any_alpha(hipStream_t s, const uint8_t* d_img, size_t n, uint32_t* d_any);
 
+// ---- k_textfx.hip ---- the text layer's styles (src/ops/text_layer/effects.rs: apply_text_effects :1, dilate_mask :167); host side: pfx_textfx.cpp
+#define PFXK_TEXTFX_MAX_RADIUS 64
+// dilate_mask's disc as row spans, built on the host with the reference's f32 test: span[dy + radius] for dy in [-radius, radius] is PFXK_DISC_SKIP where
+// dy * dy > r_sq, else half | level << 8 | reads << 16: the span [x - half, x + half] is covered by `reads` (1..4) windows of 4^level columns
+#define PFXK_DISC_SKIP 0xffffffffu
+typedef struct pfxk_disc {
+    int32_t  radius;                                   // ceil(r), 1 .. PFXK_TEXTFX_MAX_RADIUS
+    uint32_t levels;                                   // window tables the kernel builds: 4^0 .. 4^(levels - 1) columns
+    uint32_t span[2 * PFXK_TEXTFX_MAX_RADIUS + 1];
+} pfxk_disc;
+// the disc's maximum (take_min: minimum) over a w x h u8 plane read as d_src[(y * w + x) * src_stride + src_offset] (1, 0: a plane; 4, 3: the alpha of an
+// RGBA8 image), clipped to the image, the maximum starting at 0 (the minimum at 255), into the plane d_dst
+hipError_t pfxk_textfx_disc(hipStream_t s, const uint8_t* d_src, uint32_t src_stride, uint32_t src_offset, uint8_t* d_dst, uint32_t w, uint32_t h,
+                            const pfxk_disc* D, int take_min);
+// the shadows' alpha plane: the text's alpha read at (x - dx, y - dy); inner 0: round((a / 255) * alpha), 0 from outside the image; inner 1:
+// round((1 - a / 255) * alpha), `alpha` from outside
+hipError_t pfxk_textfx_plane(hipStream_t s, const uint8_t* d_text, uint8_t* d_plane, uint32_t w, uint32_t h, int32_t dx, int32_t dy, uint32_t alpha, int inner);
+// d_rgba[i] = (rgb, d_plane[i]): the image the reference hands to its Gaussian
+hipError_t pfxk_textfx_expand(hipStream_t s, const uint8_t* d_plane, uint8_t* d_rgba, size_t n, uint32_t rgb);
+enum { PFXK_TFX_SHADOW = 1, PFXK_TFX_SHADOW_RGBA = 2,   // a shadow stage; its alpha is the blurred RGBA image `shadow` (rgb read there too), not a plane
+       PFXK_TFX_OUTLINE_OUT = 4, PFXK_TFX_GRADIENT = 8, PFXK_TFX_GRADIENT_REPEAT = 16, PFXK_TFX_TEXTURE = 32, PFXK_TFX_OUTLINE_IN = 64,
+       PFXK_TFX_INNER = 128,         // an inner shadow stage; without _BLURRED it reads the shifted text itself
+       PFXK_TFX_INNER_BLURRED = 256, PFXK_TFX_INNER_RGBA = 512 };
+typedef struct pfxk_textfx {
+    uint32_t w, h, flags;
+    const uint8_t *shadow, *dilated, *eroded, *inner;   // planes of w * h bytes (or RGBA8 images, see the flags); read only where a flag says so
+    uint32_t shadow_rgb, outline_rgb, inner_rgb;        // r | g << 8 | b << 16
+    float    outline_oa;                                // colour alpha as f32 / 255.0
+    int32_t  inner_dx, inner_dy;
+    float    inner_ia;                                  // colour alpha as f32
+    float    g_dir_x, g_dir_y, g_scale, g_off_x, g_off_y;
+    uint32_t g_start, g_end;                            // packed RGBA8
+    uint32_t tex_w, tex_h;
+    float    t_scale, t_off_x, t_off_y;
+} pfxk_textfx;
+// every per-pixel stage of apply_text_effects in order, the output written once
+hipError_t pfxk_textfx_compose(hipStream_t s, const uint8_t* d_text, const uint8_t* d_texture, uint8_t* d_out, const pfxk_textfx* P);
+// find_tight_bounds_rgba: d_got[0..5) (zeroed by the caller) = max(~x), max(~y), max(x), max(y) over the pixels with alpha > 0, and 1 when there is one
+hipError_t pfxk_textfx_bounds(hipStream_t s, const uint8_t* d_img, uint32_t w, uint32_t h, uint32_t* d_got);
+
 #ifdef __cplusplus
 }
 #endif

@@ -200,6 +200,68 @@ def overlay_geometry(ov: _lib.Overlay) -> _lib.OverlayGeom:
     return g
 
 
+OUTLINE_POSITIONS = ["inside", "outside", "center"]                     # OutlinePosition, PFX_TEXT_OUTLINE_*
+TEXT_FX_OUTLINE, TEXT_FX_SHADOW, TEXT_FX_INNER_SHADOW, TEXT_FX_GRADIENT_FILL, TEXT_FX_TEXTURE_FILL = 1, 2, 4, 8, 16
+TEXT_FX_MAX_RADIUS = 64
+
+
+def text_effects(size, outline=None, shadow=None, inner_shadow=None, gradient_fill=None, texture_fill=None) -> _lib.TextEffects:
+    """a pfx_text_fx for a (w, h) image: TextEffects (core.rs:299-364), each member None or a dict of the reference's field names; a missing field takes
+    the member's Default.  outline: color, width, position; shadow: color, offset_x, offset_y, blur_radius, spread; inner_shadow: color, offset_x, offset_y,
+    blur_radius; gradient_fill: start_color, end_color, angle_degrees, scale, offset, repeat; texture_fill: texture_width, texture_height, scale, offset (the
+    decoded texture itself goes to the call)"""
+    fx = _lib.TextEffects()
+    fx.width, fx.height = int(size[0]), int(size[1])
+    fx.outline_position = 1
+    if outline is not None:
+        o = dict(color=(0, 0, 0, 255), width=2.0, position="outside") | outline
+        fx.flags |= TEXT_FX_OUTLINE
+        fx.outline_color[:] = [int(v) for v in o["color"]]
+        fx.outline_width = float(o["width"])
+        fx.outline_position = OUTLINE_POSITIONS.index(o["position"]) if isinstance(o["position"], str) else int(o["position"])
+    if shadow is not None:
+        s = dict(color=(0, 0, 0, 180), offset_x=4.0, offset_y=4.0, blur_radius=5.0, spread=0.0) | shadow
+        fx.flags |= TEXT_FX_SHADOW
+        fx.shadow_color[:] = [int(v) for v in s["color"]]
+        fx.shadow_offset_x, fx.shadow_offset_y = float(s["offset_x"]), float(s["offset_y"])
+        fx.shadow_blur_radius, fx.shadow_spread = float(s["blur_radius"]), float(s["spread"])
+    if inner_shadow is not None:
+        s = dict(color=(0, 0, 0, 128), offset_x=2.0, offset_y=2.0, blur_radius=3.0) | inner_shadow
+        fx.flags |= TEXT_FX_INNER_SHADOW
+        fx.inner_color[:] = [int(v) for v in s["color"]]
+        fx.inner_offset_x, fx.inner_offset_y, fx.inner_blur_radius = float(s["offset_x"]), float(s["offset_y"]), float(s["blur_radius"])
+    if gradient_fill is not None:
+        g = dict(start_color=(255, 255, 255, 255), end_color=(0, 0, 0, 255), angle_degrees=0.0, scale=200.0, offset=(0.0, 0.0), repeat=False) | gradient_fill
+        fx.flags |= TEXT_FX_GRADIENT_FILL
+        fx.gradient_start[:] = [int(v) for v in g["start_color"]]
+        fx.gradient_end[:] = [int(v) for v in g["end_color"]]
+        fx.gradient_angle_degrees, fx.gradient_scale = float(g["angle_degrees"]), float(g["scale"])
+        fx.gradient_offset[:] = [float(v) for v in g["offset"]]
+        fx.gradient_repeat = int(bool(g["repeat"]))
+    if texture_fill is not None:
+        t = dict(texture_width=0, texture_height=0, scale=1.0, offset=(0.0, 0.0)) | texture_fill
+        fx.flags |= TEXT_FX_TEXTURE_FILL
+        fx.tex_w, fx.tex_h, fx.texture_scale = int(t["texture_width"]), int(t["texture_height"]), float(t["scale"])
+        fx.texture_offset[:] = [float(v) for v in t["offset"]]
+    return fx
+
+
+def text_effects_plan(fx: _lib.TextEffects, bounds) -> _lib.TextRegion:
+    """pfx_text_effects_plan: the padded, clamped region of a text whose pixels with alpha > 0 span bounds = (x, y, w, h) on the fx.width x fx.height canvas, and
+    whether the effects run on the whole canvas instead; host only"""
+    r = _lib.TextRegion()
+    b = (C.c_uint32 * 4)(*[int(v) for v in bounds])
+    st = _lib.load().pfx_text_effects_plan(C.byref(fx), b, C.byref(r))
+    if st != _lib.OK:
+        raise PfxError(st, "pfx_text_effects_plan refused its arguments")
+    return r
+
+
+def textfx_span(radius: float, dy: int) -> int:
+    """the half-width of row dy of dilate_mask's disc as the text styles' kernels walk it (-1: the row is skipped or the radius is refused); host only"""
+    return int(_lib.load().pfx_int_textfx_span(C.c_float(radius), C.c_int32(dy)))
+
+
 def script_check(source: str, w: int = 64, h: int = 64):
     """Language-only evaluation of a script (no device, no image functions; ref: compile_script, scripting.rs:1489): returns
     the console lines or raises PfxError with .line / .col."""
@@ -886,6 +948,26 @@ class GpuRenderer:
         self._check(self._lib.pfx_overlay_extract_dev(self._h, C.c_void_p(layer_ptr), C.c_void_p(selection_ptr or None), C.c_uint32(w), C.c_uint32(h),
                                                       C.c_void_p(clip_ptr), C.c_void_p(clip_mask_ptr or None), C.byref(ov)))
         return ov if ov.source_w else None
+
+    # ---- the text layer's styles (pfx_text_effects*): `fx` is a `text_effects(...)` descriptor ----
+    def text_effects(self, fx, text, texture=None) -> np.ndarray:
+        """apply_text_effects on the rasterised text (fx.height, fx.width, 4); texture is the decoded RGBA8 (fx.tex_h, fx.tex_w, 4) of a texture fill or None"""
+        t = _u8(text)
+        tex = None if texture is None else _u8(texture)
+        out = np.empty_like(t)
+        self._check(self._lib.pfx_text_effects(self._h, C.byref(fx), _p(t), _p(tex), _p(out)))
+        return out
+
+    def text_effects_dev(self, fx, text_ptr: int, out_ptr: int, texture_ptr: int = 0):
+        """apply_text_effects between two device images of fx.width x fx.height; asynchronous"""
+        self._check(self._lib.pfx_text_effects_dev(self._h, C.byref(fx), C.c_void_p(text_ptr), C.c_void_p(texture_ptr or None), C.c_void_p(out_ptr)))
+
+    def text_layer_effects_dev(self, fx, text_ptr: int, out_ptr: int, texture_ptr: int = 0):
+        """TextLayerData::rasterize's effect step on a canvas-sized text image: tight bounds, the padded region or the whole canvas, the result in an otherwise
+        zero canvas; returns the plan as a pfx_text_region (w == 0: no visible text); waits for the device once"""
+        r = _lib.TextRegion()
+        self._check(self._lib.pfx_text_layer_effects_dev(self._h, C.byref(fx), C.c_void_p(text_ptr), C.c_void_p(texture_ptr or None), C.c_void_p(out_ptr), C.byref(r)))
+        return r
 
     # ------------------------------------------------------------------ script front-end
     def resize_image(self, img, new_w: int, new_h: int, filter="bilinear"):   # transform.rs:347 (imageops::resize)

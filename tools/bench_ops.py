@@ -275,6 +275,31 @@ def main() -> int:
     timed("overlay: extract through a 70 % selection", ["overlay_extract"], lambda: r.overlay_extract_dev(d, m, w, h, ov_clip.data_ptr(), ov_cmask.data_ptr()), px, 19,
           "lift (1 + 4 read, 4 + 1 written) + the grey-aware delete (1 + 4 read, 4 written where selected); the bounds launch and its read-back come before the timer")
     del ov_clip, ov_cmask
+    # ---------------- the text layer's styles (k_textfx.hip).  The disc maximum alone (an outline whose other stages are one compose pass, timed apart) at two
+    # radii: the discs hold 81 and 7 845 taps, the span walk reads at most 4 (2 r + 1) bytes of LDS per pixel.  Then the default style on the whole canvas
+    # beside the three existing calls nearest to its stages, and on a 1 500 x 400 block of text inside the same canvas (the region rule)
+    from paintfe_amd import text_effects
+    for radius in (5.0, 50.0):
+        fx_o = text_effects((w, h), outline=dict(width=radius))
+        timed(f"text styles: disc maximum, r = {radius:g}", ["textfx_disc"], lambda: r.text_effects_dev(fx_o, s, d), px, 2,
+              "1 read (the alpha of an RGBA8 pixel: 4 B fetched) + 1 written; the compose pass behind it is not in this row")
+    tfx_timers = ["textfx_bounds", "textfx_crop", "textfx_plane", "textfx_disc", "gauss_plane", "gauss_fused", "gauss_mfma", "gauss_h", "gauss_v", "textfx_compose", "textfx_blit"]
+    fx_d = text_effects((w, h), outline={}, shadow={}, inner_shadow={})
+    timed("text styles: defaults (shadow 4, 4, 5, 0; outline 2 outside; inner shadow 2, 2, 3), whole canvas", tfx_timers, lambda: r.text_layer_effects_dev(fx_d, s, d), px, 8,
+          "random alpha everywhere: the tight bounds are the canvas; the bounds launch's read-back is a wait on the host and not in the timers")
+    if rows and rows[-1]["op"].startswith("text styles: defaults"):
+        for name in tfx_timers:
+            print("   ", name, round(r.timing_read(name)[0] / args.reps, 4), "ms", flush=True)
+    r.set_exact(True)
+    timed("text styles' nearest existing calls: drop shadow blur=5 + outline width=2 + gaussian sigma=3 (exact)",
+          ["shadow_alpha", "gauss_plane", "gauss_mfma", "gauss_fused", "gauss_h", "gauss_v", "shadow_composite", "outline"],
+          lambda: (r.shadow_dev(s, d, w, h, 4, 4, 5.0, False, (0, 0, 0, 180), 1.0), r.outline_dev(s, d, w, h, 2, (0, 0, 0, 255)), r.gaussian_blur_dev(s, d, w, h, 3.0, t)), px, 24)
+    r.set_exact(False)
+    block = torch.zeros_like(src)
+    block[2000:2400, 3000:4500] = src[2000:2400, 3000:4500]
+    timed("text styles: defaults, a 1 500 x 400 text block on the 8K canvas (the region path)", tfx_timers, lambda: r.text_layer_effects_dev(fx_d, block.data_ptr(), d), px, 8,
+          "the bounds pass reads the canvas, the effects run on 1 546 x 446, the canvas is zeroed and the region blitted; Mpx_s and GB/s are per canvas pixel")
+    del block
     src_h = src.cpu().numpy()
     import time
     r.execute_script_sync("map_channels(|r, g, b, a| [255 - r, g / 2, (b * 3 + a) / 4, a]);", src_h)   # warm: a process's first launch of k_script's code object loads it (~1 ms)

@@ -77,8 +77,9 @@ PFX_DEV bool tip_coverage(const pfxk_brush& B, const pfxk_stamp& S, const uint8_
 }
 
 // compute_brush_alpha (brush_render.rs:54-82; k_brush_math.h is the host's form) with its two divisions by wave-uniform denominators — the radius and
-// edge1 - edge0 — as prepared reciprocals (k_common.h: rdiv, correctly rounded, identical to `/`; numerators here are 0 or >= 2^-24 in magnitude, below 2^20).
-// The caller guarantees radius > 0 (brush_prepare skips radius^2 < 0.001).
+// edge1 - edge0 = -1 — as prepared reciprocals (k_common.h: rdiv, correctly rounded, identical to `/`).  Operands: the radius is >= sqrt(0.001) > 2^-5 (brush_prepare
+// skips radius^2 < 0.001) and < 2^24 (this path runs only while radius + 0.5 > radius); a distance is 0 or >= 2^-75 and <= radius + 0.5.  That reaches past the
+// 2^20 k_common.h argues for; tests/test_gpu_brush_edges.py re-checks exponents -75 .. 24 over -5 .. 24 against `/` on the device (2^28 pairs, 0 mismatches on an MI355X).
 struct brush_alpha_k { rdiv radius, edge; float hard_m1, edge0, edge1; };
 PFX_DEV brush_alpha_k brush_alpha_prepare(float radius, float hardness)
 {

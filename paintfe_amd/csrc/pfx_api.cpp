@@ -829,6 +829,7 @@ int pfx_brush_stamps_ex_dev(pfx_ctx* ctx, void* target_dev, uint32_t w, uint32_t
                             const float* points_xy, uint32_t n_points, const void* selection_dev)
 {
     PFX_TRY(check_inout(ctx, "pfx_brush_stamps_dev", target_dev, w, h));
+    ctx->last_brush_path = 0;
     if (n_points == 0) return PFX_OK;
     PFX_REQUIRE(ctx, points_xy != nullptr, "null stamp list");
     const bool image_tip = dyn && dyn->tip_mask;
@@ -844,8 +845,7 @@ int pfx_brush_stamps_ex_dev(pfx_ctx* ctx, void* target_dev, uint32_t w, uint32_t
     auto u8 = [](float v) -> uint32_t { return !(v > 0.0f) ? 0u : (v >= 255.0f ? 255u : (uint32_t)(int)v); };
     std::vector<pfxk_stamp> st(n_points);
     const float half = image_tip ? (float)dyn->tip_mask_size / 2.0f : 0.0f;
-    float reach = image_tip ? half : B.draw_radius;
-    float minx = 0, maxx = 0, miny = 0, maxy = 0;
+    uint32_t ux0 = 1u, ux1 = 0u, uy0 = 1u, uy1 = 0u;   // union of the stamps' pixel boxes; empty so far
     for (uint32_t i = 0; i < n_points; ++i) {
         const float px = points_xy[2 * i], py = points_xy[2 * i + 1];
         pfxk_stamp& S = st[i];
@@ -883,11 +883,8 @@ int pfx_brush_stamps_ex_dev(pfx_ctx* ctx, void* target_dev, uint32_t w, uint32_t
             if (fabsf(rotation_deg) > 0.01f) {
                 const float rad = -(rotation_deg * (3.14159265358979323846f / 180.0f)); // negative: inverse rotation for sampling
                 S.cos_a = cosf(rad); S.sin_a = sinf(rad); S.rotated = 1;
-                reach = std::max(reach, half * 1.41421356237309504880f);
             }
         }
-        if (i == 0) { minx = maxx = S.cx; miny = maxy = S.cy; }
-        else { minx = std::min(minx, S.cx); maxx = std::max(maxx, S.cx); miny = std::min(miny, S.cy); maxy = std::max(maxy, S.cy); }
         // the stamp's pixel box, with the reference's float operations (:209-215 round tip, :584-587 image tip; `as u32` saturates, NaN -> 0): the kernel tests
         // pixels against it and the binning below deals the stamp to the chunks it touches
         {
@@ -901,15 +898,16 @@ int pfx_brush_stamps_ex_dev(pfx_ctx* ctx, void* target_dev, uint32_t w, uint32_t
                 S.y0 = pfx_f32_as_u32(fmaxf(floorf(S.cy - B.draw_radius), 0.0f)); S.y1 = std::min(pfx_f32_as_u32(ceilf(S.cy + B.draw_radius)), hm1);
             }
             if (S.x0 > S.x1 || S.y0 > S.y1) { S.x0 = 1u; S.x1 = 0u; S.y0 = 1u; S.y1 = 0u; }   // touches no pixel
+            else if (ux0 > ux1) { ux0 = S.x0; ux1 = S.x1; uy0 = S.y0; uy1 = S.y1; }
+            else { ux0 = std::min(ux0, S.x0); ux1 = std::max(ux1, S.x1); uy0 = std::min(uy0, S.y0); uy1 = std::max(uy1, S.y1); }
             S.pad[0] = S.pad[1] = 0u;
         }
     }
-    // bounding box of the whole stroke: union of the per-stamp boxes (brush_render.rs:209-215, 584-587) plus slack
-    const float pad = reach + 2.0f;
-    if (!(minx == minx && maxx == maxx && miny == miny && maxy == maxy)) return pfx_fail(ctx, PFX_ERR_INVALID, "stamp positions must be finite");
-    const int bx0 = (int)std::max(0.0f, floorf(std::max(minx - pad, -1.0e9f))), by0 = (int)std::max(0.0f, floorf(std::max(miny - pad, -1.0e9f)));
-    const int bx1 = (int)std::min((float)(w - 1), ceilf(std::min(maxx + pad, 1.0e9f))), by1 = (int)std::min((float)(h - 1), ceilf(std::min(maxy + pad, 1.0e9f)));
-    if (bx1 < bx0 || by1 < by0) return PFX_OK;
+    // The launch box of the bounding-box kernel is the union of the per-stamp pixel boxes above, every one of them inside the canvas.  A non-finite centre has
+    // the box the reference's casts give it (brush_render.rs:208-215, 584-587: NaN -> column / row 0, +inf -> past the edge and empty, -inf -> column / row 0) and
+    // is walked like any other stamp, wherever it stands in the stroke and whichever kernel runs.
+    if (ux0 > ux1) return PFX_OK;   // no stamp touches a pixel
+    const int bx0 = (int)ux0, by0 = (int)uy0, bx1 = (int)ux1, by1 = (int)uy1;
     const size_t stamp_bytes = st.size() * sizeof(pfxk_stamp), tip_bytes = image_tip ? (size_t)dyn->tip_mask_size * dyn->tip_mask_size : 0;
     // Strokes of more than one cull group: deal the stamps to the 64 x 64 chunks (TiledImage's grid) their boxes touch, so that the kernel's work follows the painted
     // area instead of the stroke's bounding box times its length.  A chunk's list holds every stamp whose pixel box (above) touches it, in stroke order.
@@ -967,6 +965,7 @@ int pfx_brush_stamps_ex_dev(pfx_ctx* ctx, void* target_dev, uint32_t w, uint32_t
         d_lut = (const uint8_t*)ctx->d_lut.p;
     }
     pfx_timer t(ctx, "brush_stamps");
+    ctx->last_brush_path = chunk_tab.empty() ? 1 : 2;
     if (!chunk_tab.empty())
         PFX_HIP(ctx, pfxk_brush_stamps_binned(ctx->stream, (uint8_t*)target_dev, w, h, &B, (const pfxk_stamp*)ctx->d_pts.p, n_points, d_lut, d_tip,
                                               (const uint8_t*)selection_dev, (const uint32_t*)((const uint8_t*)ctx->d_pts.p + tab_off), (uint32_t)(chunk_tab.size() / 4u),
@@ -976,6 +975,8 @@ int pfx_brush_stamps_ex_dev(pfx_ctx* ctx, void* target_dev, uint32_t w, uint32_t
                                        (const uint8_t*)selection_dev, bx0, by0, bx1, by1));
     return PFX_OK;
 }
+
+int pfx_int_brush_last(pfx_ctx* ctx) { return !ctx ? -1 : ctx->last_brush_path; }
 
 int pfx_brush_stamps_dev(pfx_ctx* ctx, void* target_dev, uint32_t w, uint32_t h, const pfx_brush* brush, const float* points_xy,
                          uint32_t n_points, const void* selection_dev)

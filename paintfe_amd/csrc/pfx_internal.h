@@ -48,6 +48,8 @@ struct pfx_ctx {
     bool brush_binning = true; // pfx_tune "brush_binning": strokes of more than 64 stamps are dealt to 64 x 64 chunks on the host (pfx_brush_stamps_ex_dev)
     int median_bits_min = 3;   // pfx_tune "median_bits_min", the one per-context knob of pfx_stencil.cpp (see pfx_int_median_path there)
     int last_median_path = -1, last_box_plan = -1;   // what pfx_stencil_median / _box last launched; pfx_int_stencil_last_path reads them, nothing else does
+    int last_resize_path = -1, last_resize_span = -1;   // what pfx_resize_image_dev last launched; pfx_int_resize_last reads them, nothing else does
+    int last_brush_path = -1;                           // what pfx_brush_stamps_ex_dev last did; pfx_int_brush_last reads it, nothing else does
     pfx_devbuf fx_a, fx_b; // effect-bank scratch (crystallize cell table, drop-shadow planes)
     // small parameter buffers
     pfx_devbuf d_desc, d_adj, d_chunks, d_wts, d_lut, d_pts, d_misc;
@@ -225,6 +227,12 @@ struct pfx_box_case { int radius /* ceil, >= 1 */, in_place; uint32_t w, h; int 
 extern "C" int pfx_int_median_path(const pfx_median_case* c);
 extern "C" int pfx_int_box_plan(const pfx_box_case* c, pfx_box_plan* plan);
 extern "C" int pfx_int_stencil_last_path(pfx_ctx* ctx, int which);   // for the tests, what the context's last call ran: which = 0 the median's path, 1 the box blur's kind | h_kind << 4 | px << 8 | py << 16; -1 = none yet
+// for the tests, what the context's last pfx_resize_image[_dev] ran: which = 0 the path (0 the device copy of an unchanged size, 1 the fused kernel, 2 the two
+// passes through the f32 intermediate), 1 span_max, the widest source-column range of one output tile; -1 = none yet (not in include/pfx.h)
+extern "C" int pfx_int_resize_last(pfx_ctx* ctx, int which);
+// likewise for the context's last pfx_brush_stamps[_ex][_dev] / pfx_brush_line[_ex]: 0 no launch (no stamp touches a pixel, or the brush is below the radius
+// skip), 1 the bounding-box kernel, 2 the binned kernel; -1 = none yet
+extern "C" int pfx_int_brush_last(pfx_ctx* ctx);
 int pfx_stencil_tune(pfx_ctx* ctx, const char* key, int value);   // pfx_tune's median_* and box_* keys
 int pfx_stencil_median(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, int radius, const void* mask_dev);   // arguments are the caller's to check
 int pfx_stencil_box(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, int radius, const void* mask_dev, void* tmp_dev /* NULL: st_tmp */);

@@ -97,6 +97,8 @@ int staged(pfx_ctx* ctx, const uint8_t* src, size_t src_bytes, uint8_t* dst, siz
 
 extern "C" {
 
+int pfx_int_resize_last(pfx_ctx* ctx, int which) { return !ctx ? -1 : (which == 0 ? ctx->last_resize_path : ctx->last_resize_span); }
+
 int pfx_resize_image_dev(pfx_ctx* ctx, const void* src_dev, uint32_t w, uint32_t h, void* dst_dev, uint32_t new_w, uint32_t new_h, int filter)
 {
     PFX_TRY(pfx_check_dims(ctx, "pfx_resize_image_dev", w, h));
@@ -105,6 +107,7 @@ int pfx_resize_image_dev(pfx_ctx* ctx, const void* src_dev, uint32_t w, uint32_t
     PFX_REQUIRE(ctx, filter >= PFX_RESIZE_NEAREST && filter <= PFX_RESIZE_LANCZOS3, "pfx_resize_image_dev: unknown filter");
     if (new_w == w && new_h == h) { // the crate copies instead of resampling
         PFX_HIP(ctx, hipMemcpyAsync(dst_dev, src_dev, (size_t)w * h * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        ctx->last_resize_path = 0; ctx->last_resize_span = 0;
         return PFX_OK;
     }
     AxisTable v, hz;
@@ -132,6 +135,7 @@ int pfx_resize_image_dev(pfx_ctx* ctx, const void* src_dev, uint32_t w, uint32_t
     }
     const bool fused = (size_t)span_max * 8 * 16 <= 64u * 1024u && !ctx->resize_two_pass;
     if (!fused) PFX_TRY(pfx_reserve(ctx, ctx->st_tmp, (size_t)w * new_h * 16));
+    ctx->last_resize_path = fused ? 1 : 2; ctx->last_resize_span = (int)span_max;
     const uint32_t* d = (const uint32_t*)ctx->fx_a.p;
     const float* dw = (const float*)(d + n_u32);
     pfx_timer t(ctx, "resize");

@@ -139,6 +139,8 @@ def load() -> C.CDLL:
     lib.pfx_int_select_span.argtypes = [C.c_uint32, C.c_uint32]
     lib.pfx_int_textfx_span.restype = C.c_int
     lib.pfx_int_textfx_span.argtypes = [C.c_float, C.c_int32]
+    lib.pfx_int_textfx_disc_dev.restype = C.c_int
+    lib.pfx_int_textfx_disc_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_int]
     lib.pfx_text_effects_dev.argtypes = [C.c_void_p, C.POINTER(TextEffects), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pfx_text_effects.argtypes = [C.c_void_p, C.POINTER(TextEffects), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pfx_text_effects_plan.argtypes = [C.POINTER(TextEffects), C.POINTER(C.c_uint32), C.POINTER(TextRegion)]

@@ -264,6 +264,10 @@ extern "C" int pfx_int_select_span(uint32_t r, uint32_t k);
 // the half-width of row dy of dilate_mask's disc as the text styles' span table holds it (pfx_textfx.cpp); -1 = the row is skipped, |dy| > ceil(radius), or
 // a radius the module refuses (not in include/pfx.h)
 extern "C" int pfx_int_textfx_span(float radius, int32_t dy);
+// the disc kernel alone, as the text styles' stages run it: build_disc(radius), then one launch between two tight w x h u8 planes on the device (take_min: the
+// erosion's minimum).  PFX_ERR_INVALID for a radius that is not finite or not above 0, a bad size, a NULL plane or planes that share a byte, PFX_ERR_UNSUPPORTED
+// for ceil(radius) above PFX_TEXT_FX_MAX_RADIUS, each before anything is launched; asynchronous (not in include/pfx.h)
+extern "C" int pfx_int_textfx_disc_dev(pfx_ctx* ctx, const void* src_plane, void* dst_plane, uint32_t w, uint32_t h, float radius, int take_min);
 
 // blur_with_selection on device-resident images (pfx_api.cpp); mask_host may be NULL (= no selection)
 int pfx_int_blur_with_selection_dev(pfx_ctx* ctx, const void* d_src, void* d_dst, uint32_t w, uint32_t h, float sigma,

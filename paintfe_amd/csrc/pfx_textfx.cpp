@@ -287,6 +287,24 @@ int pfx_int_textfx_span(float radius, int32_t dy)
     return span_half(radius, int_radius, dy);
 }
 
+// test seam (not in include/pfx.h): the disc's maximum (take_min: minimum) of a tight w x h u8 plane into another, as the stages run it: build_disc, then one
+// launch.  Refuses before anything is launched: PFX_ERR_INVALID for a radius that is not finite or not above 0, a bad size, a NULL or overlapping plane;
+// PFX_ERR_UNSUPPORTED for ceil(radius) above PFX_TEXT_FX_MAX_RADIUS.  Asynchronous
+int pfx_int_textfx_disc_dev(pfx_ctx* ctx, const void* src_plane, void* dst_plane, uint32_t w, uint32_t h, float radius, int take_min)
+{
+    const char* who = "pfx_int_textfx_disc_dev";
+    PFX_TRY(pfx_check_dims(ctx, who, w, h));
+    if (!std::isfinite(radius) || !(radius > 0.0f)) return pfx_fail(ctx, PFX_ERR_INVALID, "%s: radius %g is not finite and above 0", who, (double)radius);
+    const size_t n = (size_t)w * h;
+    PFX_TRY(pfx_check_args(ctx, who, true, {{src_plane, n, PFX_ARG_IN, "src_plane"}, {dst_plane, n, PFX_ARG_OUT, "dst_plane"}}));
+    PFX_TRY(radius_ok(ctx, who, "radius", radius));
+    pfxk_disc D;
+    build_disc(radius, &D);
+    pfx_timer t(ctx, "textfx_disc");
+    PFX_HIP(ctx, pfxk_textfx_disc(ctx->stream, (const uint8_t*)src_plane, 1, 0, (uint8_t*)dst_plane, w, h, &D, take_min ? 1 : 0));
+    return PFX_OK;
+}
+
 int pfx_text_effects_plan(const pfx_text_fx* fx, const uint32_t bounds[4], pfx_text_region* out)
 {
     const char* who = "pfx_text_effects_plan";

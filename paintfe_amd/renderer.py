@@ -969,6 +969,12 @@ class GpuRenderer:
         self._check(self._lib.pfx_text_layer_effects_dev(self._h, C.byref(fx), C.c_void_p(text_ptr), C.c_void_p(texture_ptr or None), C.c_void_p(out_ptr), C.byref(r)))
         return r
 
+    def textfx_disc_dev(self, src_ptr: int, dst_ptr: int, w: int, h: int, radius: float, take_min: bool = False):
+        """the text styles' disc kernel alone between two tight w x h u8 planes on the device: the maximum over dilate_mask's disc, or the erosion's minimum
+        (pfx_int_textfx_disc_dev; for tests); asynchronous"""
+        self._check(self._lib.pfx_int_textfx_disc_dev(self._h, C.c_void_p(src_ptr or None), C.c_void_p(dst_ptr or None), C.c_uint32(w), C.c_uint32(h),
+                                                      C.c_float(radius), C.c_int(int(take_min))))
+
     # ------------------------------------------------------------------ script front-end
     def resize_image(self, img, new_w: int, new_h: int, filter="bilinear"):   # transform.rs:347 (imageops::resize)
         src = _u8(img)

@@ -74,8 +74,7 @@ def test_effects_equal_the_model(gpu, name, size):
     assert np.array_equal(got, want), n
 
 
-@pytest.mark.parametrize("width,position", [(64.0, "outside"), (128.0, "center"), (64.0, "inside"), (63.2, "outside"),
-                                            (8.0, "outside"), (8.01, "outside"), (8.0, "inside"), (9.0, "inside"), (16.0, "center"), (16.5, "center")])
+@pytest.mark.parametrize("width,position", TC.TILE_SHAPE_OUTLINES)
 def test_the_largest_radius_and_the_two_tile_shapes(gpu, width, position):
     """PFX_TEXT_FX_MAX_RADIUS: the disc kernel's largest halo, wider than the 131 x 70 image is tall; and both sides of the halo (8) at which the disc
     kernel changes its tile from 64 x 32 to 64 x 64"""
@@ -84,6 +83,23 @@ def test_the_largest_radius_and_the_two_tile_shapes(gpu, width, position):
     want, counts = M.apply(TC.text_of(size), effects)
     assert sum(counts["outline"]) > 500
     got, _ = run_dev(gpu, describe(size, effects), TC.text_of(size), None)
+    assert np.array_equal(got, want), differing(got, want)
+    # the same on the image that sees each tap of this disc: the slab for the minimum, whose eroded plane is not zero, the dots for the maximum, whose
+    # dilated plane is the disc itself (the rings saturate under a large maximum and vanish under a large minimum; the slab saturates under any maximum:
+    # tests/test_textfx_disc_host.py)
+    image = TC.tile_shape_image(position)
+    shape = (image.shape[1], image.shape[0])
+    want, counts = M.apply(image, effects)
+    assert sum(counts["outline"]) > 500
+    got, _ = run_dev(gpu, describe(shape, effects), image, None)
+    assert np.array_equal(got, want), (shape, differing(got, want))
+
+
+@pytest.mark.parametrize("name,size", TC.DISC_RUNS, ids=lambda v: v if isinstance(v, str) else f"{v[0]}x{v[1]}")
+def test_disc_cases_equal_the_model(gpu, name, size):
+    """inside outlines on the slab, outside outlines and spread shadows on the dots: inputs on which a tap missing from the disc changes the picture"""
+    want, _ = TC.expected_disc_case(name, size)
+    got, _ = run_dev(gpu, describe(size, TC.DISC_CASES[name][1]), TC.disc_text(name, size), None)
     assert np.array_equal(got, want), differing(got, want)
 
 
@@ -101,6 +117,18 @@ def test_layer_equals_the_model(gpu, name):
     text, effects = TC.document(name)
     want, want_region = TC.expected_layer(name)
     got, r = run_dev(gpu, describe(TC.CANVAS, effects), text, None, call="layer")
+    assert dict(x=r.x, y=r.y, w=r.w, h=r.h, pad_px=r.pad_px, full_canvas=r.full_canvas) == want_region
+    assert np.array_equal(got, want), differing(got, want)
+
+
+@pytest.mark.parametrize("name", list(TC.BOUNDS_DOCUMENTS))
+def test_tight_bounds_at_the_canvas_edges(gpu, name):
+    """the bounds kernel's extremes: each corner, the column behind a workgroup's first 256, the rows behind its first 2048 workgroups"""
+    text = TC.bounds_document(name)
+    canvas = TC.BOUNDS_DOCUMENTS[name][0]
+    want, want_region = TC.expected_bounds_layer(name)
+    assert want_region["w"] > 0 and want.any()
+    got, r = run_dev(gpu, describe(canvas, TC.BOUNDS_EFFECTS), text, None, call="layer")
     assert dict(x=r.x, y=r.y, w=r.w, h=r.h, pad_px=r.pad_px, full_canvas=r.full_canvas) == want_region
     assert np.array_equal(got, want), differing(got, want)
 

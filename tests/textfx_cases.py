@@ -95,6 +95,86 @@ def expected(name, size):
     return out, counts
 
 
+# ---- inputs on which every tap of the disc counts (tests/textfx_disc_cases.py has the planes) -------------------------------------------------------------------------
+# The rings above saturate under a large maximum and vanish under a large minimum.  `slab` is for the minimum: one opaque block flush with the left, top and
+# bottom borders (the outside of the image must not count), a ragged soft edge on its right, a few small holes of distinct partial alpha, the lowest of them
+# near the bottom so that the disc's top row alone reaches it from far above; rgb 0, so that a white inside outline shows.  `dots` is for the maximum: the
+# `clear` plane as alpha (one pixel of 255 alone in the window of the largest disc, eight lower ones on the border) with random rgb.
+SLAB_HOLES = [(0.15, 0.95, 40), (0.42, 0.30, 90), (0.62, 0.62, 140), (0.30, 0.55, 200), (0.75, 0.12, 0)]   # x, y as fractions of the size; alpha
+
+
+@functools.lru_cache(maxsize=None)
+def slab_image(w, h, seed=11):
+    rng = np.random.default_rng(seed)
+    edge = w - max(6, w // 12) - rng.integers(0, 4, h)                # the last opaque column of each row
+    xs = np.arange(w)[None, :]
+    alpha = np.clip(np.round((edge[:, None] - xs + 1.5) / 3.0 * 255.0), 0, 255).astype(np.uint8)   # 255 up to the edge, two partial columns, then 0
+    for k, (fx, fy, a) in enumerate(SLAB_HOLES):
+        x, y = int(fx * w), min(int(fy * h), h - 2)
+        alpha[y, x] = a
+        if k % 2:                                                   # every other hole is two pixels wide
+            alpha[y, x + 1] = a
+    img = np.zeros((h, w, 4), np.uint8)
+    img[..., 3] = alpha
+    img.setflags(write=False)
+    return img
+
+
+@functools.lru_cache(maxsize=None)
+def dots_image(seed=12):
+    from . import textfx_disc_cases as DC
+    alpha = DC.clear(64)
+    img = np.random.default_rng(seed).integers(0, 256, alpha.shape + (4,), dtype=np.uint8)
+    img[..., 3] = alpha
+    img[alpha == 0] = 0
+    img.setflags(write=False)
+    return img
+
+
+SLAB_SIZES = [(131, 70), (200, 140)]
+DOTS_SIZE = (200, 140)
+WHITE = (255, 255, 255, 255)
+
+
+def _spread(spread, blur):
+    return dict(shadow=dict(offset_x=3.0, offset_y=-2.0, blur_radius=blur, spread=spread, color=(20, 20, 20, 180)))
+
+
+# name -> (image, effects): every one uses the disc, and tests/test_textfx_disc_host.py shows that each would notice a disc with a tap missing
+DISC_CASES = {
+    **{f"slab-inside-{wd:g}": ("slab", dict(outline=dict(width=wd, position="inside", color=WHITE))) for wd in (3.0, 8.0, 9.0, 30.0, 64.0)},
+    "dots-outside-50": ("dots", dict(outline=dict(width=50.0, color=(10, 30, 200, 255)))),
+    "dots-outside-64": ("dots", dict(outline=dict(width=64.0, color=(10, 30, 200, 255)))),
+    "dots-center-128": ("dots", dict(outline=dict(width=128.0, position="center", color=(200, 30, 10, 200)))),
+    "dots-spread-30": ("dots", _spread(30.0, 0.0)),
+    "dots-spread-64": ("dots", _spread(64.0, 0.0)),
+    "dots-spread-30-blur-2": ("dots", _spread(30.0, 2.0)),
+    "dots-spread-64-blur-2": ("dots", _spread(64.0, 2.0)),
+}
+DISC_RUNS = [(name, size) for name, (image, _) in DISC_CASES.items() for size in (SLAB_SIZES if image == "slab" else [DOTS_SIZE])]
+
+
+# the outlines of test_the_largest_radius_and_the_two_tile_shapes (tests/test_gpu_textfx.py), which run on the rings and on tile_shape_image(position)
+TILE_SHAPE_OUTLINES = [(64.0, "outside"), (128.0, "center"), (64.0, "inside"), (63.2, "outside"), (8.0, "outside"), (8.01, "outside"), (8.0, "inside"), (9.0, "inside"),
+                       (16.0, "center"), (16.5, "center")]
+
+
+def tile_shape_image(position):
+    """the slab at the MEASURED size for the erosion, the dots for the dilations"""
+    return slab_image(*MEASURED) if position == "inside" else dots_image()
+
+
+def disc_text(name, size):
+    return slab_image(*size) if DISC_CASES[name][0] == "slab" else dots_image()
+
+
+@functools.lru_cache(maxsize=None)
+def expected_disc_case(name, size):
+    out, counts = M.apply(disc_text(name, size), DISC_CASES[name][1])
+    out.setflags(write=False)
+    return out, counts
+
+
 # ---- the layer documents: name -> (text, effects) on the CANVAS ------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def document(name):
@@ -111,6 +191,40 @@ def document(name):
 
 
 DOCUMENTS = ["corner", "spread-out", "two-edges", "no-text"]
+
+
+# the tight bounds at their extremes, on small canvases: name -> ((w, h), [(x, y)] of the only pixels, each of alpha 1).  One pixel in each corner in turn and
+# in all four; the column behind a workgroup's first 256; the row behind the bounds kernel's 2048 workgroups, where its walk over the rows takes a second
+# step, and the last row of that canvas; the first and the last pixel of a canvas a little wider than 256
+BOUNDS_DOCUMENTS = {
+    "top-left": ((300, 200), [(0, 0)]),
+    "top-right": ((300, 200), [(299, 0)]),
+    "bottom-left": ((300, 200), [(0, 199)]),
+    "bottom-right": ((300, 200), [(299, 199)]),
+    "four-corners": ((300, 200), [(0, 0), (299, 0), (0, 199), (299, 199)]),
+    "column-256": ((300, 8), [(256, 3)]),
+    "row-2048": ((5, 2100), [(2, 2048)]),
+    "row-2099": ((5, 2100), [(4, 2099)]),
+    "first-and-last": ((260, 3), [(0, 0), (259, 2)]),
+}
+BOUNDS_EFFECTS = dict(outline=dict(width=3.0, color=(10, 30, 200, 255)), shadow=dict(blur_radius=0.0, spread=2.0))
+
+
+@functools.lru_cache(maxsize=None)
+def bounds_document(name):
+    (w, h), pixels = BOUNDS_DOCUMENTS[name]
+    text = np.zeros((h, w, 4), np.uint8)
+    for k, (x, y) in enumerate(pixels):
+        text[y, x] = (200 - 40 * k, 100, 50 + 40 * k, 1)
+    text.setflags(write=False)
+    return text
+
+
+@functools.lru_cache(maxsize=None)
+def expected_bounds_layer(name):
+    out, region = M.layer(bounds_document(name), BOUNDS_EFFECTS)
+    out.setflags(write=False)
+    return out, region
 
 
 @functools.lru_cache(maxsize=None)

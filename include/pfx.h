@@ -1034,7 +1034,7 @@ int pfx_overlay_extract_dev(pfx_ctx* ctx, void* layer_dev, const void* selection
 
 /* ================= text layer styles: shadow, outline, fills, inner shadow (ref: src/ops/text_layer/effects.rs, apply_text_effects) =================
  * What TextLayerData::rasterize (data_impl.rs:132-194) runs behind the glyphs after every keystroke and style-slider tick: it takes the rasterised text as
- * RGBA8 and returns RGBA8.  Fonts, layout, glyph rasterisation and text warps are not here.  All sizes and parameters travel in one descriptor that mirrors
+ * RGBA8 and returns RGBA8.  Fonts, layout and glyph rasterisation are not here; the warps are the next section.  All sizes and parameters travel in one descriptor that mirrors
  * TextEffects (core.rs:299-364); `flags` says which of its five Options are Some.  coverage = alpha / 255.0f.  The stages, in this order, each through the
  * integer composite_over of effects.rs:47-71 (u32 arithmetic) onto an output that starts as zero:
  *   1 shadow        the coverage shifted by (round(offset_x), round(offset_y)) (half away from zero, then a saturating `as i32`; zero from outside), dilated
@@ -1106,6 +1106,68 @@ int pfx_text_effects_plan(const pfx_text_fx* fx, const uint32_t bounds[4], pfx_t
  * No visible text is a zero canvas and PFX_OK.  *region_out (host memory) receives the plan */
 int pfx_text_layer_effects_dev(pfx_ctx* ctx, const pfx_text_fx* fx, const void* text_dev, const void* texture_dev /* may be NULL */, void* out_dev,
                                pfx_text_region* region_out /* may be NULL */);
+
+/* ================= text warps and block placement: arc, circle, path, envelope, rotate, blit (ref: src/ops/text_layer/warp.rs, raster.rs:374-417) =================
+ * What rasterize_block runs on a block's tight raster after every keystroke and every drag of a warp handle, one stage in front of the styles above: the
+ * warp (apply_block_warp, warp.rs:80-93), the rotation (rotate_glyph_buffer, raster.rs:561-653) and the blit into the layer image (maybe_rotate_and_blit,
+ * selection.rs:77-106; blit_rgba_buffer, warp.rs:39-70).  Every warp is an inverse map per output pixel followed by bilinear_sample :707-740 (transparent
+ * outside, p00 (1 - fx)(1 - fy) + p10 fx (1 - fy) + p01 (1 - fx) fy + p11 fx fy, round half away from zero); every f32 expression is the reference's, one
+ * rounding per operation.
+ *   plan      the output's size and offset, on the host, from the reference's own sampling loops (arc :118-150 with glibc sinf / cosf, circular :283-300,
+ *             path :368-406, envelope :460-490).  Identity (the reference's `src.to_vec()` returns; out = src size, offset 0, 0; the device call copies):
+ *             kind NONE; arc with |bend| < 0.001 or an output side of 0 or above 8192; path / envelope with fewer than 4 points or a zero side.
+ *   arc       apply_arc_warp :155-176 with arc_inverse_map :222-274 as written: a distortion of -1 divides by zero and the comparisons then reject the pixel.
+ *   circular  :305-349: radius = max(radius, 10), the annulus test first, the angle normalised by the reference's two loops of f32 additions of tau.
+ *   path      inverse_path_follow :627-695: 65 coarse points (strict <, the first minimum wins), eight refinement steps, tangent, normal, the 257-entry
+ *             arc-length table of build_arc_length_table :575-591.
+ *   envelope  :495-536, with the reference's t measured from the margin-shifted min_x.
+ *   rotate    rotate_glyph_buffer: cosf / sinf once on the host, clamped +1 taps, new_w = ceil(..) + 1; skipped when |rotation| <= 0.001.
+ *   blit      a source pixel with alpha 0 leaves the canvas pixel alone, any other replaces it; clipped to the canvas.
+ * Path, envelope, rotate and blit are in the bit-exact class.  Arc and circular call atan2 per pixel: the device evaluates the f64 atan2 rounded once to
+ * f32, which differs from glibc's atan2f by one ulp on rare arguments: +-1 on fewer than 0.1 % of channels (the LIBM class of the shape rasteriser).
+ * Refused with PFX_ERR_INVALID, before the first launch and with outputs untouched: a NULL descriptor or required pointer; an unknown kind; a zero src_w or
+ * src_h (buf_w, buf_h for the rotation; canvas_w, canvas_h for the placement); any float of the descriptor that is not finite, whatever kind says; a device pointer
+ * that is not 4-byte aligned; an output that overlaps an input; out_bytes too small (host tier).  PFX_ERR_UNSUPPORTED, likewise: |circ_start_angle| above
+ * 8 pi (the reference's loops do not end for a large one; the bound keeps them to a handful of steps); a source, planned output or canvas over the 256 Mpx
+ * document limit (the circular output side ceil(2 (r + h) + 4) is unbounded in the reference). */
+enum { PFX_TEXT_WARP_NONE = 0, PFX_TEXT_WARP_ARC = 1, PFX_TEXT_WARP_CIRCULAR = 2, PFX_TEXT_WARP_PATH = 3, PFX_TEXT_WARP_ENVELOPE = 4 };
+typedef struct pfx_text_warp_desc {       /* TextWarp core.rs:171-294, plus the block raster's size (C has one namespace: pfx_text_warp is the host-tier call) */
+    uint32_t src_w, src_h;
+    int32_t  kind;                        /* PFX_TEXT_WARP_* */
+    float    arc_bend, arc_hdist, arc_vdist;                  /* ArcWarp: bend, horizontal_distortion, vertical_distortion */
+    float    circ_radius, circ_start_angle;                   /* CircularWarp */
+    uint32_t circ_clockwise;
+    uint32_t path_points;                 /* PathFollowWarp: control_points.len() and its first four */
+    float    path[4][2];
+    uint32_t top_points, bottom_points;   /* EnvelopeWarp: top_curve.len(), bottom_curve.len() and the first four of each */
+    float    top[4][2], bottom[4][2];
+} pfx_text_warp_desc;
+typedef struct pfx_text_warp_geom {       /* what the warps' and the rotation's bounds loops derive */
+    uint32_t out_w, out_h;
+    int32_t  off_x, off_y;                /* of the output relative to the source's origin */
+    uint32_t identity;                    /* 1: the output is the source */
+    float    min_x, min_y, max_x, max_y;  /* the f32 bounds, margins included (arc, path, envelope, rotate); 0 otherwise */
+} pfx_text_warp_geom;
+int pfx_text_warp_plan(const pfx_text_warp_desc* warp, pfx_text_warp_geom* out);   /* host only, no context */
+/* src_dev: src_w * src_h RGBA8; out_dev: out_w * out_h RGBA8 of the plan, every byte written (zeros where the reference skips); asynchronous */
+int pfx_text_warp_dev(pfx_ctx* ctx, const pfx_text_warp_desc* warp, const void* src_dev, void* out_dev);
+/* host tier: out_bytes >= out_w * out_h * 4 of the plan, which *plan_out (may be NULL) receives */
+int pfx_text_warp(pfx_ctx* ctx, const pfx_text_warp_desc* warp, const uint8_t* src, uint8_t* out, size_t out_bytes, pfx_text_warp_geom* plan_out);
+/* rotate_glyph_buffer of a buf_w * buf_h buffer by `angle` radians around pivot_xy (buffer coordinates; NULL = the centre).  |angle| <= 0.001 is the identity */
+int pfx_text_rotate_plan(uint32_t buf_w, uint32_t buf_h, float angle, const float* pivot_xy, pfx_text_warp_geom* out);   /* host only, no context */
+int pfx_text_rotate_dev(pfx_ctx* ctx, uint32_t buf_w, uint32_t buf_h, float angle, const float* pivot_xy, const void* src_dev, void* out_dev);
+typedef struct pfx_text_block {           /* one block's tight raster on its way into the layer image */
+    pfx_text_warp_desc warp;              /* its src_w * src_h is the raster */
+    int32_t  off_x, off_y;                /* of the raster on the canvas */
+    float    rotation;                    /* block.rotation, radians */
+    uint32_t has_pivot;                   /* 0: rotate around the (warped) buffer's centre */
+    float    pivot[2];                    /* rot_pivot, canvas coordinates */
+    uint32_t canvas_w, canvas_h;
+} pfx_text_block;
+/* raster.rs:374-417: the warp, the rotation around the pivot, the blit into canvas_dev (canvas_w * canvas_h RGBA8, changed in place); asynchronous.  One
+ * deviation: the reference adds the offsets in 32 bits (a debug build panics on overflow); here the sums are 64 bits wide and a block that lands outside
+ * the canvas changes nothing */
+int pfx_text_block_place_dev(pfx_ctx* ctx, const pfx_text_block* block, const void* src_dev, void* canvas_dev);
 
 #ifdef __cplusplus
 }

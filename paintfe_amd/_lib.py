@@ -115,6 +115,22 @@ class TextRegion(C.Structure):   # pfx_text_region
     _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("pad_px", C.c_uint32), ("full_canvas", C.c_uint32)]
 
 
+class TextWarp(C.Structure):   # pfx_text_warp_desc
+    _fields_ = [("src_w", C.c_uint32), ("src_h", C.c_uint32), ("kind", C.c_int32), ("arc_bend", C.c_float), ("arc_hdist", C.c_float), ("arc_vdist", C.c_float),
+                ("circ_radius", C.c_float), ("circ_start_angle", C.c_float), ("circ_clockwise", C.c_uint32), ("path_points", C.c_uint32),
+                ("path", C.c_float * 2 * 4), ("top_points", C.c_uint32), ("bottom_points", C.c_uint32), ("top", C.c_float * 2 * 4), ("bottom", C.c_float * 2 * 4)]
+
+
+class TextWarpGeom(C.Structure):   # pfx_text_warp_geom
+    _fields_ = [("out_w", C.c_uint32), ("out_h", C.c_uint32), ("off_x", C.c_int32), ("off_y", C.c_int32), ("identity", C.c_uint32),
+                ("min_x", C.c_float), ("min_y", C.c_float), ("max_x", C.c_float), ("max_y", C.c_float)]
+
+
+class TextBlock(C.Structure):   # pfx_text_block
+    _fields_ = [("warp", TextWarp), ("off_x", C.c_int32), ("off_y", C.c_int32), ("rotation", C.c_float), ("has_pivot", C.c_uint32), ("pivot", C.c_float * 2),
+                ("canvas_w", C.c_uint32), ("canvas_h", C.c_uint32)]
+
+
 _lib = None
 
 
@@ -145,5 +161,11 @@ def load() -> C.CDLL:
     lib.pfx_text_effects.argtypes = [C.c_void_p, C.POINTER(TextEffects), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pfx_text_effects_plan.argtypes = [C.POINTER(TextEffects), C.POINTER(C.c_uint32), C.POINTER(TextRegion)]
     lib.pfx_text_layer_effects_dev.argtypes = [C.c_void_p, C.POINTER(TextEffects), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TextRegion)]
+    lib.pfx_text_warp_plan.argtypes = [C.POINTER(TextWarp), C.POINTER(TextWarpGeom)]
+    lib.pfx_text_warp_dev.argtypes = [C.c_void_p, C.POINTER(TextWarp), C.c_void_p, C.c_void_p]
+    lib.pfx_text_warp.argtypes = [C.c_void_p, C.POINTER(TextWarp), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(TextWarpGeom)]
+    lib.pfx_text_rotate_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_float, C.POINTER(C.c_float), C.POINTER(TextWarpGeom)]
+    lib.pfx_text_rotate_dev.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
+    lib.pfx_text_block_place_dev.argtypes = [C.c_void_p, C.POINTER(TextBlock), C.c_void_p, C.c_void_p]
     _lib = lib
     return lib

@@ -105,6 +105,7 @@ struct pfx_ctx {
     uint32_t colorkey_ring_launches = 0, colorkey_launches = 0;
     pfx_devbuf overlay_ws;                              // the floating selection's scaled source (pfx_overlay.cpp); pfx_resize_image_dev itself uses fx_a and st_tmp
     pfx_devbuf textfx_ws;                               // the text styles' planes, blur images and cropped region (pfx_textfx.cpp); the Gaussian itself uses st_tmp
+    pfx_devbuf textwarp_ws;                             // a placed text block's warped and rotated buffers (pfx_textwarp.cpp)
 };
 
 // ---- error plumbing ----

@@ -458,6 +458,33 @@ hipError_t pfxk_textfx_compose(hipStream_t s, const uint8_t* d_text, const uint8
 // find_tight_bounds_rgba: d_got[0..5) (zeroed by the caller) = max(~x), max(~y), max(x), max(y) over the pixels with alpha > 0, and 1 when there is one
 hipError_t pfxk_textfx_bounds(hipStream_t s, const uint8_t* d_img, uint32_t w, uint32_t h, uint32_t* d_got);
 
+// ---- k_textwarp.hip ---- the text block's warps, rotation and blit (src/ops/text_layer/warp.rs, raster.rs:561-653); host side: pfx_textwarp.cpp
+// What is uniform over the image, derived on the host through the reference's own f32 expressions.  Every kernel writes all out_w * out_h pixels
+typedef struct pfxk_textwarp {
+    uint32_t src_w, src_h, out_w, out_h;
+    float w, h, min_x, min_y;                            // src_w / src_h as f32; the bounds' corner (margins included)
+    // arc :222-274
+    float cx, r_abs, r_sign, half_angle, theta_lim;      // w / 2, |radius|, +-1, angle / 2, |angle / 2| + 0.1
+    float half_w, half_h, h_r_sign;                      // w / 2, h / 2, h * r_sign
+    float one_hdist, one_vdist;                          // 1 + hdist, 1 + vdist
+    uint32_t curved, undo_h, undo_v;                     // |angle| > 0.01, |hdist| > 0.001, |vdist| > 0.001
+    // circular :305-349
+    float r, r_outer, out_c, start_angle, dir;
+    // path :413-441 and envelope :495-536: the curves' control points; the envelope's t denominator max(max_x - min_x - 2 margin, 1)
+    float top[4][2], bottom[4][2], t_den;
+} pfxk_textwarp;
+// the path's tables: eval_cubic_bezier at i / 64 and build_arc_length_table's 257 cumulative lengths
+typedef struct pfxk_textwarp_tables { float cx[65], cy[65], len[257]; } pfxk_textwarp_tables;
+hipError_t pfxk_textwarp_arc(hipStream_t s, const uint8_t* d_src, uint8_t* d_out, const pfxk_textwarp* P);
+hipError_t pfxk_textwarp_circular(hipStream_t s, const uint8_t* d_src, uint8_t* d_out, const pfxk_textwarp* P);
+hipError_t pfxk_textwarp_path(hipStream_t s, const uint8_t* d_src, uint8_t* d_out, const pfxk_textwarp* P, const pfxk_textwarp_tables* T);   // P->top = the path
+hipError_t pfxk_textwarp_envelope(hipStream_t s, const uint8_t* d_src, uint8_t* d_out, const pfxk_textwarp* P);
+// rotate_glyph_buffer's loop :605-647: (cx, cy) the pivot, (new_cx, new_cy) the pivot in the output
+typedef struct pfxk_textrotate { uint32_t w, h, new_w, new_h; float cos_a, sin_a, cx, cy, new_cx, new_cy; } pfxk_textrotate;
+hipError_t pfxk_textwarp_rotate(hipStream_t s, const uint8_t* d_src, uint8_t* d_out, const pfxk_textrotate* R);
+// blit_rgba_buffer: the bw x bh buffer at (off_x, off_y) on the cw x ch canvas; alpha 0 keeps the canvas pixel, any other pixel replaces it
+hipError_t pfxk_textwarp_blit(hipStream_t s, const uint8_t* d_buf, uint32_t bw, uint32_t bh, int64_t off_x, int64_t off_y, uint8_t* d_canvas, uint32_t cw, uint32_t ch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -262,6 +262,63 @@ def textfx_span(radius: float, dy: int) -> int:
     return int(_lib.load().pfx_int_textfx_span(C.c_float(radius), C.c_int32(dy)))
 
 
+TEXT_WARP_KINDS = ["none", "arc", "circular", "path", "envelope"]        # TextWarp, PFX_TEXT_WARP_*
+
+
+def text_warp(size, kind="none", **fields) -> _lib.TextWarp:
+    """a pfx_text_warp_desc for a (w, h) block raster: TextWarp (core.rs:171-294) with the reference's field names; a missing field takes the variant's
+    Default.  arc: bend, horizontal_distortion, vertical_distortion; circular: radius, start_angle, clockwise; path: control_points; envelope: top_curve,
+    bottom_curve (lists of (x, y); their length travels, the first four points are used)"""
+    wd = _lib.TextWarp()
+    wd.src_w, wd.src_h = int(size[0]), int(size[1])
+    wd.kind = TEXT_WARP_KINDS.index(kind) if isinstance(kind, str) else int(kind)
+    f = dict(bend=0.5, horizontal_distortion=0.0, vertical_distortion=0.0, radius=150.0, start_angle=float(np.float32(-np.pi / 2)), clockwise=True,
+             control_points=[(0.0, 0.0), (100.0, -50.0), (200.0, -50.0), (300.0, 0.0)],
+             top_curve=[(0.0, -30.0), (100.0, -60.0), (200.0, -60.0), (300.0, -30.0)],
+             bottom_curve=[(0.0, 30.0), (100.0, 60.0), (200.0, 60.0), (300.0, 30.0)]) | fields
+    wd.arc_bend, wd.arc_hdist, wd.arc_vdist = float(f["bend"]), float(f["horizontal_distortion"]), float(f["vertical_distortion"])
+    wd.circ_radius, wd.circ_start_angle, wd.circ_clockwise = float(f["radius"]), float(f["start_angle"]), int(bool(f["clockwise"]))
+    for count, dst, pts in (("path_points", wd.path, f["control_points"]), ("top_points", wd.top, f["top_curve"]), ("bottom_points", wd.bottom, f["bottom_curve"])):
+        setattr(wd, count, len(pts))
+        for i, p in enumerate(list(pts)[:4]):
+            dst[i][0], dst[i][1] = float(p[0]), float(p[1])
+    return wd
+
+
+def text_warp_plan(warp: _lib.TextWarp) -> _lib.TextWarpGeom:
+    """pfx_text_warp_plan: the warped output's size, its offset from the source's origin and whether it is the source itself; host only"""
+    g = _lib.TextWarpGeom()
+    st = _lib.load().pfx_text_warp_plan(C.byref(warp), C.byref(g))
+    if st != _lib.OK:
+        raise PfxError(st, "pfx_text_warp_plan refused its arguments")
+    return g
+
+
+def _pivot(pivot):
+    return None if pivot is None else (C.c_float * 2)(float(pivot[0]), float(pivot[1]))
+
+
+def text_rotate_plan(w: int, h: int, angle: float, pivot=None) -> _lib.TextWarpGeom:
+    """pfx_text_rotate_plan: rotate_glyph_buffer's output size and offset for a w x h buffer (pivot in buffer coordinates, None = the centre); host only"""
+    g = _lib.TextWarpGeom()
+    st = _lib.load().pfx_text_rotate_plan(C.c_uint32(w), C.c_uint32(h), C.c_float(angle), _pivot(pivot), C.byref(g))
+    if st != _lib.OK:
+        raise PfxError(st, "pfx_text_rotate_plan refused its arguments")
+    return g
+
+
+def text_block(warp: _lib.TextWarp, offset, canvas, rotation=0.0, pivot=None) -> _lib.TextBlock:
+    """a pfx_text_block: the block raster described by `warp` at offset = (x, y) on a canvas = (w, h), rotated by `rotation` radians around pivot (canvas
+    coordinates; None = the buffer's centre)"""
+    b = _lib.TextBlock()
+    C.memmove(C.byref(b.warp), C.byref(warp), C.sizeof(_lib.TextWarp))
+    b.off_x, b.off_y, b.rotation = int(offset[0]), int(offset[1]), float(rotation)
+    b.canvas_w, b.canvas_h = int(canvas[0]), int(canvas[1])
+    if pivot is not None:
+        b.has_pivot, b.pivot[0], b.pivot[1] = 1, float(pivot[0]), float(pivot[1])
+    return b
+
+
 def script_check(source: str, w: int = 64, h: int = 64):
     """Language-only evaluation of a script (no device, no image functions; ref: compile_script, scripting.rs:1489): returns
     the console lines or raises PfxError with .line / .col."""
@@ -968,6 +1025,27 @@ class GpuRenderer:
         r = _lib.TextRegion()
         self._check(self._lib.pfx_text_layer_effects_dev(self._h, C.byref(fx), C.c_void_p(text_ptr), C.c_void_p(texture_ptr or None), C.c_void_p(out_ptr), C.byref(r)))
         return r
+
+    # ---- the text block's warps and placement (pfx_text_warp*, pfx_text_rotate*, pfx_text_block_place_dev) ----
+    def text_warp(self, warp, src):
+        """apply_block_warp on the block raster (warp.src_h, warp.src_w, 4): returns the warped image and its plan (pfx_text_warp_geom)"""
+        s = _u8(src)
+        g = text_warp_plan(warp)
+        out = np.empty((g.out_h, g.out_w, 4), np.uint8)
+        self._check(self._lib.pfx_text_warp(self._h, C.byref(warp), _p(s), _p(out), C.c_size_t(out.nbytes), C.byref(g)))
+        return out, g
+
+    def text_warp_dev(self, warp, src_ptr: int, out_ptr: int):
+        """apply_block_warp between two device images: the source and the out_w x out_h of text_warp_plan(warp); asynchronous"""
+        self._check(self._lib.pfx_text_warp_dev(self._h, C.byref(warp), C.c_void_p(src_ptr), C.c_void_p(out_ptr)))
+
+    def text_rotate_dev(self, w: int, h: int, angle: float, src_ptr: int, out_ptr: int, pivot=None):
+        """rotate_glyph_buffer between two device images: w x h and the out_w x out_h of text_rotate_plan; asynchronous"""
+        self._check(self._lib.pfx_text_rotate_dev(self._h, C.c_uint32(w), C.c_uint32(h), C.c_float(angle), _pivot(pivot), C.c_void_p(src_ptr), C.c_void_p(out_ptr)))
+
+    def text_block_place_dev(self, block, src_ptr: int, canvas_ptr: int):
+        """a block raster's way into the layer image: warp, rotate, blit into the device canvas in place; asynchronous"""
+        self._check(self._lib.pfx_text_block_place_dev(self._h, C.byref(block), C.c_void_p(src_ptr), C.c_void_p(canvas_ptr)))
 
     def textfx_disc_dev(self, src_ptr: int, dst_ptr: int, w: int, h: int, radius: float, take_min: bool = False):
         """the text styles' disc kernel alone between two tight w x h u8 planes on the device: the maximum over dilate_mask's disc, or the erosion's minimum

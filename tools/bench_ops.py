@@ -300,6 +300,48 @@ def main() -> int:
     timed("text styles: defaults, a 1 500 x 400 text block on the 8K canvas (the region path)", tfx_timers, lambda: r.text_layer_effects_dev(fx_d, block.data_ptr(), d), px, 8,
           "the bounds pass reads the canvas, the effects run on 1 546 x 446, the canvas is zeroed and the region blitted; Mpx_s and GB/s are per canvas pixel")
     del block
+    # ---------------- the text block's warps and placement (k_textwarp.hip): each warp at its largest ordinary frame (path and envelope clamp at 4096 x 4096, the
+    # arc's sides stay below 8192, the circle's square is 2 (r + h) + 4), the rotation and the placement on the 8K canvas; px = output pixels.  The
+    # displacement warp runs at the envelope's pixel count beside it: the envelope reads no field, so it must not be the slower one (profiles/text_warp.md)
+    from paintfe_amd import text_block, text_rotate_plan, text_warp, text_warp_plan
+
+    def warp_row(label, size, timer, note, **fields):
+        wd = text_warp(size, **fields)
+        gm = text_warp_plan(wd)
+        raster = torch.randint(0, 256, (size[1], size[0], 4), dtype=torch.uint8, device=dev, generator=g)
+        timed(f"text warp: {label}, {size[0]} x {size[1]} -> {gm.out_w} x {gm.out_h}", [timer], lambda: r.text_warp_dev(wd, raster.data_ptr(), d), gm.out_w * gm.out_h, 8, note)
+        return gm
+
+    gm_env = warp_row("envelope", (4088, 4088), "textwarp_envelope", "4 gathered + 4 written; t, top_y and span once per column and workgroup", kind="envelope",
+                      top_curve=[(0.0, 60.0), (1363.0, -20.0), (2725.0, -20.0), (4088.0, 60.0)], bottom_curve=[(0.0, 4028.0), (1363.0, 4108.0), (2725.0, 4108.0), (4088.0, 4028.0)])
+    ew, eh = gm_env.out_w, gm_env.out_h
+    e_disp = torch.empty((eh, ew, 2), dtype=torch.float32, device=dev)
+    e_yy = torch.arange(eh, device=dev, dtype=torch.float32)[:, None]
+    e_xx = torch.arange(ew, device=dev, dtype=torch.float32)[None, :]
+    e_disp[..., 0] = 40.0 * torch.sin(e_yy / 300.0) * torch.cos(e_xx / 500.0)
+    e_disp[..., 1] = 40.0 * torch.cos(e_yy / 400.0) * torch.sin(e_xx / 350.0)
+    del e_yy, e_xx
+    timed(f"text warp's yardstick: liquify displacement warp, {ew} x {eh}", ["warp_displacement"], lambda: r.warp_displacement_dev(s, ew, eh, e_disp.data_ptr(), ew, eh, d),
+          ew * eh, 16, "4 + 8 (field) + 4 B/px at the envelope row's pixel count")
+    del e_disp
+    warp_row("path follow", (3900, 64), "textwarp_path", "65 distances + 17 Bézier evaluations per pixel; most of the frame is far from the text", kind="path",
+             control_points=[(0.0, 0.0), (2000.0, 0.0), (2000.0, 3900.0), (4000.0, 3900.0)])
+    warp_row("arc, bend 0.5", (6500, 1000), "textwarp_arc", "f64 atan2 per pixel whose sy is inside the text", kind="arc", bend=0.5)
+    warp_row("circular, r = 1800", (8000, 200), "textwarp_circular", "f64 atan2 inside the annulus only", kind="circular", radius=1800.0)
+    gm_rot = text_rotate_plan(w, h, 0.3)
+    rot_out = torch.empty((gm_rot.out_h, gm_rot.out_w, 4), dtype=torch.uint8, device=dev)
+    timed(f"text rotate: the 8K canvas by 0.3 -> {gm_rot.out_w} x {gm_rot.out_h}", ["textwarp_rotate"], lambda: r.text_rotate_dev(w, h, 0.3, s, rot_out.data_ptr()),
+          gm_rot.out_w * gm_rot.out_h, 8)
+    del rot_out
+    place_timers = ["textwarp_arc", "textwarp_rotate", "textwarp_blit"]
+    blk_small = text_block(text_warp((1500, 400), kind="arc", bend=0.5), (3000, 2000), (w, h), rotation=0.3)
+    timed("text place: a 1 500 x 400 block, arc 0.5, rotated 0.3, into the 8K canvas", place_timers, lambda: r.text_block_place_dev(blk_small, s, d), 1500 * 400, 8,
+          "three launches on the block's own pixels; Mpx_s per source pixel")
+    blk_full = text_block(text_warp((w, h), kind="none"), (0, 0), (w, h), rotation=0.3)
+    canvas2 = torch.zeros_like(src)
+    timed("text place: an 8K raster rotated 0.3 into the 8K canvas", place_timers, lambda: r.text_block_place_dev(blk_full, s, canvas2.data_ptr()), px, 12,
+          "rotate (4 + 4 B per rotated pixel) and blit (4 read, 4 written where alpha > 0); Mpx_s per canvas pixel")
+    del canvas2
     src_h = src.cpu().numpy()
     import time
     r.execute_script_sync("map_channels(|r, g, b, a| [255 - r, g / 2, (b * 3 + a) / 4, a]);", src_h)   # warm: a process's first launch of k_script's code object loads it (~1 ms)

@@ -298,6 +298,44 @@ PFX_DEV void blend_layer_fast(uint32_t mode, float (&acc)[PX][4], const uint32_t
 // pixel; re-quantisation `k = (q * 255) as u8` followed by `k / 255` of the next blend is requant() below.
 PFX_DEV float requant(float q) { return div255(__builtin_truncf(q * 255.0f)); }
 
+// ---- round 8: two shorter exact forms, one switch each for A/B (tools/build_variant.sh -DPFX_...=0; profiles/r08_tuning.md) ----
+#ifndef PFX_WB_MASK
+#define PFX_WB_MASK 1     // the :1253 early-out as a masked write-back of requant's last FMA instead of a compare and four selects (requant_keep)
+#endif
+#ifndef PFX_OVW_RAW
+#define PFX_OVW_RAW 1     // Overwrite's colour channels are the layer pixel: requant is the identity on RN(k / 255)
+#endif
+// acc[c] = (top3 == 0) ? acc[c] : requant(q[c]) for the four channels.  requant ends in div255's FMA; the four FMAs write the accumulator registers
+// under an EXEC mask of "layer pixel not transparent", so the kept lanes are never written and the discarded lanes' NaN / Inf (0 / 0 when both alphas
+// are 0) never reach a register that lives on.  ONE statement: the compiler does not know that EXEC changes, and anything it could schedule between
+// the narrowing and the restore (another pixel's arithmetic, a ballot, a v_readlane reload of a spilled SGPR) would run under the narrow mask.
+// v_cmpx writes VCC as well as EXEC on gfx9; lanes that are inactive on entry compare as 0, so the mask only ever narrows.
+// Cost beside the instructions saved: two SALU moves per call, and code size — an asm statement is not sunk into a common successor, so the identical
+// tails of a switch's cases, which the compiler used to merge, stay in their cases (flatten_srt_kernel<3>: 121 -> 150 KB; profiles/r08_tuning.md).
+PFX_DEV void requant_keep(float (&acc)[4], float top3, float q0, float q1, float q2, float q3)
+{
+#if PFX_WB_MASK
+    const float C_LO = __builtin_bit_cast(float, 2944335615u);  // div255's low word; its high word 0x3B808081 is the literal of v_fmamk below
+    const float t0 = __builtin_truncf(q0 * 255.0f), t1 = __builtin_truncf(q1 * 255.0f), t2 = __builtin_truncf(q2 * 255.0f), t3 = __builtin_truncf(q3 * 255.0f);
+    const float m0 = t0 * C_LO, m1 = t1 * C_LO, m2 = t2 * C_LO, m3 = t3 * C_LO;
+    uint64_t keep;
+    asm volatile("s_mov_b64 %[keep], exec\n\t"
+                 "v_cmpx_neq_f32_e32 vcc, 0, %[a]\n\t"
+                 "v_fmamk_f32 %[o0], %[t0], 0x3b808081, %[m0]\n\t"
+                 "v_fmamk_f32 %[o1], %[t1], 0x3b808081, %[m1]\n\t"
+                 "v_fmamk_f32 %[o2], %[t2], 0x3b808081, %[m2]\n\t"
+                 "v_fmamk_f32 %[o3], %[t3], 0x3b808081, %[m3]\n\t"
+                 "s_mov_b64 exec, %[keep]"
+                 : [o0] "+v"(acc[0]), [o1] "+v"(acc[1]), [o2] "+v"(acc[2]), [o3] "+v"(acc[3]), [keep] "=&s"(keep)
+                 : [a] "v"(top3), [t0] "v"(t0), [t1] "v"(t1), [t2] "v"(t2), [t3] "v"(t3), [m0] "v"(m0), [m1] "v"(m1), [m2] "v"(m2), [m3] "v"(m3)
+                 : "vcc");
+#else
+    const bool skip = (top3 == 0.0f);
+    const float o0 = requant(q0), o1 = requant(q1), o2 = requant(q2), o3 = requant(q3);
+    acc[0] = skip ? acc[0] : o0; acc[1] = skip ? acc[1] : o1; acc[2] = skip ? acc[2] : o2; acc[3] = skip ? acc[3] : o3;
+#endif
+}
+
 // blend function of the normalised form: Soft Light through the LDS table (the kernel must have run soft_d_fill + a barrier)
 template <uint32_t M> PFX_DEV float blend_fn_nx(float b, float t)
 {
@@ -323,9 +361,19 @@ PFX_DEV void blend_nx(float (&acc)[4], const float (&top)[4], float opacity_raw,
     const bool skip = (top[3] == 0.0f);                                // :1253  -> keep base
     const float top_r = top[0], top_g = top[1], top_b = top[2];
     const float top_a = top[3] * opc;                                  // :1272
-    float o0, o1, o2, o3;
+    // :1258, Normal at opacity >= 1 over an opaque layer pixel returns `top`.  No select is needed for it in this representation: top_a =
+    // 1.0 * 1.0, ita = 0, so n = top_c * 1 + x * 0 = top_c, den = 1 + base_a * 0 = 1, n / 1 = n (rdiv: y = 1, residual 0) and
+    // requant(RN(k / 255)) = RN(k / 255) for all 256 k (tests/test_host_logic.py::test_requant_is_identity_on_byte_values): the general
+    // formula already yields the layer pixel, bit for bit.
+    (void)opacity_raw;
     if constexpr (M == M_OVERWRITE) {                                  // :1275
-        o0 = requant(top_r); o1 = requant(top_g); o2 = requant(top_b); o3 = requant(top_a);
+#if PFX_OVW_RAW
+        // the colour channels arrive as RN(k / 255), on which requant is the identity (same test); top_a = top[3] * opc is no byte value
+        const float o0 = top_r, o1 = top_g, o2 = top_b, o3 = requant(top_a);
+#else
+        const float o0 = requant(top_r), o1 = requant(top_g), o2 = requant(top_b), o3 = requant(top_a);
+#endif
+        acc[0] = skip ? acc[0] : o0; acc[1] = skip ? acc[1] : o1; acc[2] = skip ? acc[2] : o2; acc[3] = skip ? acc[3] : o3;
     } else {
         constexpr bool UNIT = OB != 0 && M != M_XOR;                   // out_a == 1.0 exactly (see blend_px)
         const float base_r = acc[0], base_g = acc[1], base_b = acc[2];
@@ -355,29 +403,23 @@ PFX_DEV void blend_nx(float (&acc)[4], const float (&top)[4], float opacity_raw,
             ng = g * top_a + base_g * base_a * ita;
             nb = b * top_a + base_b * base_a * ita;
         }
-        if constexpr (UNIT) { o0 = requant(nr); o1 = requant(ng); o2 = requant(nb); o3 = 1.0f; }
-        else {
+        if constexpr (UNIT) {
+            // Opaque accumulator: the :1253 early-out needs no select.  A transparent layer pixel has top_a = 0 * opc = 0, ita = 1, so
+            // n = r * 0 + base_c * 1 = base_c for every finite r (all 23 blend functions return finite values in [0, 1], rare sides included),
+            // and requant(base_c) = base_c as above; alpha stays 1.0 in this path anyway.
+            (void)skip;
+            acc[0] = requant(nr); acc[1] = requant(ng); acc[2] = requant(nb);
+        } else {
             const rdiv k = rdiv_prepare(den);
-            o0 = requant(rdiv_apply(k, nr)); o1 = requant(rdiv_apply(k, ng)); o2 = requant(rdiv_apply(k, nb)); o3 = requant(den);
+            float q0 = rdiv_apply(k, nr), q1 = rdiv_apply(k, ng), q2 = rdiv_apply(k, nb), q3 = den;
+            if constexpr (M == M_XOR) {                                // :1285 out_a == 0 -> (0,0,0,0)
+                // the select sits in front of the re-quantisation (requant(0) = +0.0, the value selected behind it before), so that requant's
+                // last FMA stays the last instruction of each channel; the quotients are NaN here (0 / 0)
+                const bool zero = (den == 0.0f);
+                q0 = zero ? 0.0f : q0; q1 = zero ? 0.0f : q1; q2 = zero ? 0.0f : q2; q3 = zero ? 0.0f : q3;
+            }
+            requant_keep(acc, top[3], q0, q1, q2, q3);
         }
-        if constexpr (M == M_XOR) {                                    // :1285 out_a == 0 -> (0,0,0,0)
-            const bool zero = (den == 0.0f);
-            o0 = zero ? 0.0f : o0; o1 = zero ? 0.0f : o1; o2 = zero ? 0.0f : o2; o3 = zero ? 0.0f : o3;
-        }
-    }
-    // :1258, Normal at opacity >= 1 over an opaque layer pixel returns `top`.  No select is needed for it in this representation: top_a =
-    // 1.0 * 1.0, ita = 0, so n = top_c * 1 + x * 0 = top_c, den = 1 + base_a * 0 = 1, n / 1 = n (rdiv: y = 1, residual 0) and
-    // requant(RN(k / 255)) = RN(k / 255) for all 256 k (tests/test_host_logic.py::test_requant_is_identity_on_byte_values): the general
-    // formula already yields the layer pixel, bit for bit.
-    (void)opacity_raw;
-    if constexpr (OB != 0 && M != M_XOR && M != M_OVERWRITE) {
-        // Opaque accumulator: the :1253 early-out needs no select either.  A transparent layer pixel has top_a = 0 * opc = 0, ita = 1, so
-        // n = r * 0 + base_c * 1 = base_c for every finite r (all 23 blend functions return finite values in [0, 1], rare sides included),
-        // and requant(base_c) = base_c as above; alpha stays 1.0 in this path anyway.
-        (void)skip;
-        acc[0] = o0; acc[1] = o1; acc[2] = o2;
-    } else {
-        acc[0] = skip ? acc[0] : o0; acc[1] = skip ? acc[1] : o1; acc[2] = skip ? acc[2] : o2; acc[3] = skip ? acc[3] : o3;
     }
 }
 
@@ -523,15 +565,13 @@ PFX_DEV void comp_nx(float (&acc)[4], const float (&top)[4], const float (&f)[3]
         acc[1] = requant(f[1] * top_a + acc[1] * ita);
         acc[2] = requant(f[2] * top_a + acc[2] * ita);
     } else {
-        const bool skip = (top[3] == 0.0f);                            // :1253  -> keep base
         const float base_a = acc[3];
         const float den = top_a + base_a * ita;                        // :1407
         const float nr = f[0] * top_a + acc[0] * base_a * ita;         // :1412
         const float ng = f[1] * top_a + acc[1] * base_a * ita;
         const float nb = f[2] * top_a + acc[2] * base_a * ita;
         const rdiv k = rdiv_prepare(den);
-        const float o0 = requant(rdiv_apply(k, nr)), o1 = requant(rdiv_apply(k, ng)), o2 = requant(rdiv_apply(k, nb)), o3 = requant(den);
-        acc[0] = skip ? acc[0] : o0; acc[1] = skip ? acc[1] : o1; acc[2] = skip ? acc[2] : o2; acc[3] = skip ? acc[3] : o3;
+        requant_keep(acc, top[3], rdiv_apply(k, nr), rdiv_apply(k, ng), rdiv_apply(k, nb), den); // :1253 top[3] == 0 -> keep base
     }
 }
 template <uint32_t M, int PX>
@@ -580,6 +620,8 @@ PFX_DEV void blend_two_stage(uint32_t m, uint32_t v, float (&acc)[PX][4], const 
 #undef PFX_CASE
     default: fN_nx<M_NORMAL, PX>(f, acc, top); break;   // Normal, and BlendMode::from_u8's fallback (layers.rs:183)
     }
+    // Four more cases for a layer opacity of exactly 1.0 (top[3] * 1.0 is top[3]: one multiply less per pixel) were measured in round 8 and dropped: two more
+    // spilled SGPRs, twice the v_readlane reloads, more executed VALU instructions than without them (profiles/r08_tuning.md).
     switch (v) {
     case 0u: compN_nx<PX, 0, 0, 0>(acc, top, f, opc); break;
     case 1u: compN_nx<PX, 1, 1, 0>(acc, top, f, opc); break;

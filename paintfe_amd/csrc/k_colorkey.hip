@@ -12,7 +12,7 @@
 //                     tile's interior is written back: an interior pixel of level <= k has its whole shortest path within L1 radius k of itself, so inside the
 //                     window; halo pixels may end up wrong and are never written (DESIGN.md "Colour removal").
 //   write-out         step 3 (:344-415) rides in the last ring launch's write-back; at smoothness 0 it is a streaming kernel over the core map.
-#include "k_common.h"
+#include "k_tools.h"
 #include "pfx_kernels.h"
 
 using namespace pfxk;
@@ -63,26 +63,19 @@ PFX_DEV uint32_t cta_px(uint32_t p, const pfxk_cta& S)
 template <bool VEC>
 __global__ __launch_bounds__(256) void color_to_alpha_kernel(const uint32_t* src, uint32_t* dst, const uint8_t* __restrict__ mask, size_t n, pfxk_cta S)
 {
-    const size_t first = (size_t)blockIdx.x * 256u + threadIdx.x, stride = (size_t)gridDim.x * 256u;
-    size_t done = 0;
-    if constexpr (VEC) {
-        const size_t groups = n / 4u;
-        for (size_t g = first; g < groups; g += stride) {
-            const uint4 v = reinterpret_cast<const uint4*>(src)[g];
-            const uint32_t m = mask ? reinterpret_cast<const uint32_t*>(mask)[g] : 0xffffffffu;
-            uint4 o;
-            o.x = (m & 0xffu) ? cta_px(v.x, S) : v.x;
-            o.y = (m & 0xff00u) ? cta_px(v.y, S) : v.y;
-            o.z = (m & 0xff0000u) ? cta_px(v.z, S) : v.z;
-            o.w = (m >> 24) ? cta_px(v.w, S) : v.w;
-            reinterpret_cast<uint4*>(dst)[g] = o;
-        }
-        done = groups * 4u;
-    }
-    for (size_t i = done + first; i < n; i += stride) {
+    stream_walk<VEC, size_t>(n, [&](size_t g) {
+        const uint4 v = reinterpret_cast<const uint4*>(src)[g];
+        const uint32_t m = mask ? reinterpret_cast<const uint32_t*>(mask)[g] : 0xffffffffu;
+        uint4 o;
+        o.x = (m & 0xffu) ? cta_px(v.x, S) : v.x;
+        o.y = (m & 0xff00u) ? cta_px(v.y, S) : v.y;
+        o.z = (m & 0xff0000u) ? cta_px(v.z, S) : v.z;
+        o.w = (m >> 24) ? cta_px(v.w, S) : v.w;
+        reinterpret_cast<uint4*>(dst)[g] = o;
+    }, [&](size_t i) {
         const uint32_t p = src[i];
         dst[i] = (!mask || mask[i] != 0u) ? cta_px(p, S) : p;
-    }
+    });
 }
 
 PFX_DEV uint32_t passable_cost(uint32_t p, uint32_t sel, const pfxk_ckey& P)
@@ -97,19 +90,12 @@ PFX_DEV uint32_t passable_cost(uint32_t p, uint32_t sel, const pfxk_ckey& P)
 template <bool VEC>
 __global__ __launch_bounds__(256) void passable_kernel(const uint32_t* __restrict__ src, const uint8_t* __restrict__ sel, uint8_t* __restrict__ out, size_t n, pfxk_ckey P)
 {
-    const size_t first = (size_t)blockIdx.x * 256u + threadIdx.x, stride = (size_t)gridDim.x * 256u;
-    size_t done = 0;
-    if constexpr (VEC) {
-        const size_t groups = n / 4u;
-        for (size_t g = first; g < groups; g += stride) {
-            const uint4 v = reinterpret_cast<const uint4*>(src)[g];
-            const uint32_t m = sel ? reinterpret_cast<const uint32_t*>(sel)[g] : 0xffffffffu;
-            reinterpret_cast<uint32_t*>(out)[g] = passable_cost(v.x, m & 0xffu, P) | (passable_cost(v.y, m & 0xff00u, P) << 8) |
-                                                  (passable_cost(v.z, m & 0xff0000u, P) << 16) | (passable_cost(v.w, m >> 24, P) << 24);
-        }
-        done = groups * 4u;
-    }
-    for (size_t i = done + first; i < n; i += stride) out[i] = (uint8_t)passable_cost(src[i], sel ? sel[i] : 255u, P);
+    stream_walk<VEC, size_t>(n, [&](size_t g) {
+        const uint4 v = reinterpret_cast<const uint4*>(src)[g];
+        const uint32_t m = sel ? reinterpret_cast<const uint32_t*>(sel)[g] : 0xffffffffu;
+        reinterpret_cast<uint32_t*>(out)[g] = passable_cost(v.x, m & 0xffu, P) | (passable_cost(v.y, m & 0xff00u, P) << 8) |
+                                              (passable_cost(v.z, m & 0xff0000u, P) << 16) | (passable_cost(v.w, m >> 24, P) << 24);
+    }, [&](size_t i) { out[i] = (uint8_t)passable_cost(src[i], sel ? sel[i] : 255u, P); });
 }
 
 // step 3 for a pixel of the dilated mask at ring `lvl` (0 = core)
@@ -133,26 +119,19 @@ PFX_DEV uint32_t remove_px(uint32_t p, uint32_t lvl, const pfxk_ckey& P)
 template <bool VEC>
 __global__ __launch_bounds__(256) void apply_core_kernel(const uint32_t* src, const uint8_t* __restrict__ core, uint32_t* dst, size_t n, pfxk_ckey P)
 {
-    const size_t first = (size_t)blockIdx.x * 256u + threadIdx.x, stride = (size_t)gridDim.x * 256u;
-    size_t done = 0;
-    if constexpr (VEC) {
-        const size_t groups = n / 4u;
-        for (size_t g = first; g < groups; g += stride) {
-            const uint4 v = reinterpret_cast<const uint4*>(src)[g];
-            const uint32_t c = reinterpret_cast<const uint32_t*>(core)[g];
-            uint4 o;
-            o.x = (c & 0xffu) ? v.x : remove_px(v.x, 0u, P);
-            o.y = (c & 0xff00u) ? v.y : remove_px(v.y, 0u, P);
-            o.z = (c & 0xff0000u) ? v.z : remove_px(v.z, 0u, P);
-            o.w = (c >> 24) ? v.w : remove_px(v.w, 0u, P);
-            reinterpret_cast<uint4*>(dst)[g] = o;
-        }
-        done = groups * 4u;
-    }
-    for (size_t i = done + first; i < n; i += stride) {
+    stream_walk<VEC, size_t>(n, [&](size_t g) {
+        const uint4 v = reinterpret_cast<const uint4*>(src)[g];
+        const uint32_t c = reinterpret_cast<const uint32_t*>(core)[g];
+        uint4 o;
+        o.x = (c & 0xffu) ? v.x : remove_px(v.x, 0u, P);
+        o.y = (c & 0xff00u) ? v.y : remove_px(v.y, 0u, P);
+        o.z = (c & 0xff0000u) ? v.z : remove_px(v.z, 0u, P);
+        o.w = (c >> 24) ? v.w : remove_px(v.w, 0u, P);
+        reinterpret_cast<uint4*>(dst)[g] = o;
+    }, [&](size_t i) {
         const uint32_t p = src[i];
         dst[i] = core[i] != 0u ? p : remove_px(p, 0u, P);
-    }
+    });
 }
 
 // 0x80 in every byte of x that is zero, 0 elsewhere (exact: no borrow crosses a byte)
@@ -239,40 +218,27 @@ __global__ __launch_bounds__(256) void ring_kernel(const uint8_t* __restrict__ c
     }
 }
 
-inline uint32_t stream_blocks(size_t items)
-{
-    const size_t b = (items + 255u) / 256u;
-    return (uint32_t)(b < 1u ? 1u : (b > 8192u ? 8192u : b));
-}
-inline bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1u)) == 0u; }
-
 } // namespace
 
 extern "C" hipError_t pfxk_color_to_alpha(hipStream_t s, const uint8_t* d_src, uint8_t* d_dst, const uint8_t* d_mask, size_t n, const pfxk_cta* S)
 {
     if (n == 0) return hipSuccess;
-    if (aligned_to(d_src, 16) && aligned_to(d_dst, 16) && aligned_to(d_mask, 4))
-        color_to_alpha_kernel<true><<<stream_blocks((n + 3u) / 4u), 256, 0, s>>>((const uint32_t*)d_src, (uint32_t*)d_dst, d_mask, n, *S);
-    else color_to_alpha_kernel<false><<<stream_blocks(n), 256, 0, s>>>((const uint32_t*)d_src, (uint32_t*)d_dst, d_mask, n, *S);
-    return hipGetLastError();
+    return launch_stream(aligned_to(d_src, 16) && aligned_to(d_dst, 16) && aligned_to(d_mask, 4), n, s, color_to_alpha_kernel<true>, color_to_alpha_kernel<false>,
+                         (const uint32_t*)d_src, (uint32_t*)d_dst, d_mask, n, *S);
 }
 
 extern "C" hipError_t pfxk_ckey_passable(hipStream_t s, const uint8_t* d_src, const uint8_t* d_sel, uint8_t* d_out, size_t n, const pfxk_ckey* P)
 {
     if (n == 0) return hipSuccess;
-    if (aligned_to(d_src, 16) && aligned_to(d_sel, 4) && aligned_to(d_out, 4))
-        passable_kernel<true><<<stream_blocks((n + 3u) / 4u), 256, 0, s>>>((const uint32_t*)d_src, d_sel, d_out, n, *P);
-    else passable_kernel<false><<<stream_blocks(n), 256, 0, s>>>((const uint32_t*)d_src, d_sel, d_out, n, *P);
-    return hipGetLastError();
+    return launch_stream(aligned_to(d_src, 16) && aligned_to(d_sel, 4) && aligned_to(d_out, 4), n, s, passable_kernel<true>, passable_kernel<false>,
+                         (const uint32_t*)d_src, d_sel, d_out, n, *P);
 }
 
 extern "C" hipError_t pfxk_ckey_apply_core(hipStream_t s, const uint8_t* d_src, const uint8_t* d_core, uint8_t* d_dst, size_t n, const pfxk_ckey* P)
 {
     if (n == 0) return hipSuccess;
-    if (aligned_to(d_src, 16) && aligned_to(d_dst, 16) && aligned_to(d_core, 4))
-        apply_core_kernel<true><<<stream_blocks((n + 3u) / 4u), 256, 0, s>>>((const uint32_t*)d_src, d_core, (uint32_t*)d_dst, n, *P);
-    else apply_core_kernel<false><<<stream_blocks(n), 256, 0, s>>>((const uint32_t*)d_src, d_core, (uint32_t*)d_dst, n, *P);
-    return hipGetLastError();
+    return launch_stream(aligned_to(d_src, 16) && aligned_to(d_dst, 16) && aligned_to(d_core, 4), n, s, apply_core_kernel<true>, apply_core_kernel<false>,
+                         (const uint32_t*)d_src, d_core, (uint32_t*)d_dst, n, *P);
 }
 
 extern "C" hipError_t pfxk_ckey_rings(hipStream_t s, const uint8_t* d_core, const uint16_t* d_lin, const uint8_t* d_sel, uint16_t* d_lout, const uint8_t* d_src,

@@ -12,7 +12,7 @@
 //   pointwise        threshold_alpha :415 + merge_magic_wand_masks :486, build_fill_preview_region :550, and the preview blended into the layer in one
 //                    kernel (commit_fill_preview_impl :1414-1446: blend_pixel_static(layer, preview, mode, 1.0) where the preview's alpha is > 0).
 //   bounding boxes   ThresholdRegionIndex::from_distances (state.rs:693): per-distance min / max in LDS, merged into a 256 x 4 table with atomics.
-#include "k_common.h"
+#include "k_tools.h"
 #include "k_blend.h"
 #include "pfx_kernels.h"
 
@@ -24,8 +24,6 @@ constexpr int T = PFXK_FLOOD_TILE;
 constexpr int PITCH = 68;   // bytes per LDS row: 17 dwords, so the 64 rows of one column fall on different banks
 
 PFX_DEV uint32_t absdiff_u(uint32_t a, uint32_t b) { return a > b ? a - b : b - a; }
-PFX_DEV uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
-PFX_DEV uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
 
 template <int MODE>
 PFX_DEV uint32_t color_distance(uint32_t p, const pfxk_flood_target& G, const float* lin)
@@ -59,18 +57,11 @@ __global__ __launch_bounds__(256) void color_distance_kernel(const uint32_t* __r
         lin[threadIdx.x] = table[threadIdx.x];
         __syncthreads();
     }
-    const size_t first = (size_t)blockIdx.x * 256u + threadIdx.x, stride = (size_t)gridDim.x * 256u;
-    size_t done = 0;
-    if constexpr (VEC) {
-        const size_t groups = n / 4u;
-        for (size_t g = first; g < groups; g += stride) {
-            const uint4 v = reinterpret_cast<const uint4*>(src)[g];
-            reinterpret_cast<uint32_t*>(out)[g] = color_distance<MODE>(v.x, G, lin) | (color_distance<MODE>(v.y, G, lin) << 8) |
-                                                  (color_distance<MODE>(v.z, G, lin) << 16) | (color_distance<MODE>(v.w, G, lin) << 24);
-        }
-        done = groups * 4u;
-    }
-    for (size_t i = done + first; i < n; i += stride) out[i] = (uint8_t)color_distance<MODE>(src[i], G, lin);
+    stream_walk<VEC, size_t>(n, [&](size_t g) {
+        const uint4 v = reinterpret_cast<const uint4*>(src)[g];
+        reinterpret_cast<uint32_t*>(out)[g] = color_distance<MODE>(v.x, G, lin) | (color_distance<MODE>(v.y, G, lin) << 8) |
+                                              (color_distance<MODE>(v.z, G, lin) << 16) | (color_distance<MODE>(v.w, G, lin) << 24);
+    }, [&](size_t i) { out[i] = (uint8_t)color_distance<MODE>(src[i], G, lin); });
 }
 
 // the first pass's list is the seed's tile.  d[seed] itself stays 255 in memory: the first pass lowers it to c[seed] inside the tile (flood_pass_kernel), so
@@ -280,20 +271,13 @@ PFX_DEV uint32_t wand_px(uint32_t dv, uint32_t base, uint32_t threshold, uint32_
 template <bool VEC>
 __global__ __launch_bounds__(256) void wand_mask_kernel(const uint8_t* dist, const uint8_t* base, uint8_t* out, size_t n, uint32_t threshold, uint32_t band, int combine)
 {
-    const size_t first = (size_t)blockIdx.x * 256u + threadIdx.x, stride = (size_t)gridDim.x * 256u;
-    size_t done = 0;
-    if constexpr (VEC) {
-        const size_t groups = n / 4u;
-        for (size_t g = first; g < groups; g += stride) {
-            const uint32_t dv = reinterpret_cast<const uint32_t*>(dist)[g], bv = base ? reinterpret_cast<const uint32_t*>(base)[g] : 0u;
-            uint32_t o = 0u;
+    stream_walk<VEC, size_t>(n, [&](size_t g) {
+        const uint32_t dv = reinterpret_cast<const uint32_t*>(dist)[g], bv = base ? reinterpret_cast<const uint32_t*>(base)[g] : 0u;
+        uint32_t o = 0u;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) o |= wand_px((dv >> (8 * k)) & 0xffu, (bv >> (8 * k)) & 0xffu, threshold, band, combine) << (8 * k);
-            reinterpret_cast<uint32_t*>(out)[g] = o;
-        }
-        done = groups * 4u;
-    }
-    for (size_t i = done + first; i < n; i += stride) out[i] = (uint8_t)wand_px(dist[i], base ? base[i] : 0u, threshold, band, combine);
+        for (int k = 0; k < 4; ++k) o |= wand_px((dv >> (8 * k)) & 0xffu, (bv >> (8 * k)) & 0xffu, threshold, band, combine) << (8 * k);
+        reinterpret_cast<uint32_t*>(out)[g] = o;
+    }, [&](size_t i) { out[i] = (uint8_t)wand_px(dist[i], base ? base[i] : 0u, threshold, band, combine); });
 }
 
 // the preview pixel: fill.rgb with alpha (fill.a * coverage + 127) / 255 at coverage 255 (:580)
@@ -304,22 +288,15 @@ __global__ __launch_bounds__(256) void fill_preview_kernel(const uint8_t* __rest
                                                            uint32_t threshold, uint32_t fill)
 {
     const uint32_t px = preview_px(fill);
-    const size_t first = (size_t)blockIdx.x * 256u + threadIdx.x, stride = (size_t)gridDim.x * 256u;
-    size_t done = 0;
-    if constexpr (VEC) {
-        const size_t groups = n / 4u;
-        for (size_t g = first; g < groups; g += stride) {
-            const uint32_t dv = reinterpret_cast<const uint32_t*>(dist)[g], sv = sel ? reinterpret_cast<const uint32_t*>(sel)[g] : 0xffffffffu;
-            uint4 o;
-            o.x = ((dv & 0xffu) <= threshold && (sv & 0xffu) != 0u) ? px : 0u;
-            o.y = (((dv >> 8) & 0xffu) <= threshold && ((sv >> 8) & 0xffu) != 0u) ? px : 0u;
-            o.z = (((dv >> 16) & 0xffu) <= threshold && ((sv >> 16) & 0xffu) != 0u) ? px : 0u;
-            o.w = ((dv >> 24) <= threshold && (sv >> 24) != 0u) ? px : 0u;
-            reinterpret_cast<uint4*>(out)[g] = o;
-        }
-        done = groups * 4u;
-    }
-    for (size_t i = done + first; i < n; i += stride) out[i] = (dist[i] <= threshold && (!sel || sel[i] != 0u)) ? px : 0u;
+    stream_walk<VEC, size_t>(n, [&](size_t g) {
+        const uint32_t dv = reinterpret_cast<const uint32_t*>(dist)[g], sv = sel ? reinterpret_cast<const uint32_t*>(sel)[g] : 0xffffffffu;
+        uint4 o;
+        o.x = ((dv & 0xffu) <= threshold && (sv & 0xffu) != 0u) ? px : 0u;
+        o.y = (((dv >> 8) & 0xffu) <= threshold && ((sv >> 8) & 0xffu) != 0u) ? px : 0u;
+        o.z = (((dv >> 16) & 0xffu) <= threshold && ((sv >> 16) & 0xffu) != 0u) ? px : 0u;
+        o.w = ((dv >> 24) <= threshold && (sv >> 24) != 0u) ? px : 0u;
+        reinterpret_cast<uint4*>(out)[g] = o;
+    }, [&](size_t i) { out[i] = (dist[i] <= threshold && (!sel || sel[i] != 0u)) ? px : 0u; });
 }
 
 __global__ __launch_bounds__(256) void fill_commit_kernel(uint32_t* __restrict__ layer, const uint8_t* __restrict__ dist, const uint8_t* __restrict__ sel, size_t n,
@@ -337,13 +314,6 @@ __global__ __launch_bounds__(256) void fill_commit_kernel(uint32_t* __restrict__
     }
 }
 
-inline uint32_t stream_blocks(size_t items)
-{
-    const size_t b = (items + 255u) / 256u;
-    return (uint32_t)(b < 1u ? 1u : (b > 8192u ? 8192u : b));
-}
-inline bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1u)) == 0u; }
-
 } // namespace
 
 extern "C" hipError_t pfxk_color_distance(hipStream_t s, const uint8_t* d_src, uint8_t* d_out, size_t n, int mode, const pfxk_flood_target* G, const float* d_table)
@@ -351,16 +321,9 @@ extern "C" hipError_t pfxk_color_distance(hipStream_t s, const uint8_t* d_src, u
     if (n == 0) return hipSuccess;
     if ((mode != 0 && mode != 1) || (mode == 1 && !d_table)) return hipErrorInvalidValue;
     const bool vec = aligned_to(d_src, 16) && aligned_to(d_out, 4);
-    const uint32_t blocks = stream_blocks(vec ? (n + 3u) / 4u : n);
     const uint32_t* src = (const uint32_t*)d_src;
-    if (mode == 0) {
-        if (vec) color_distance_kernel<0, true><<<blocks, 256, 0, s>>>(src, d_out, n, *G, d_table);
-        else color_distance_kernel<0, false><<<blocks, 256, 0, s>>>(src, d_out, n, *G, d_table);
-    } else {
-        if (vec) color_distance_kernel<1, true><<<blocks, 256, 0, s>>>(src, d_out, n, *G, d_table);
-        else color_distance_kernel<1, false><<<blocks, 256, 0, s>>>(src, d_out, n, *G, d_table);
-    }
-    return hipGetLastError();
+    if (mode == 0) return launch_stream(vec, n, s, color_distance_kernel<0, true>, color_distance_kernel<0, false>, src, d_out, n, *G, d_table);
+    return launch_stream(vec, n, s, color_distance_kernel<1, true>, color_distance_kernel<1, false>, src, d_out, n, *G, d_table);
 }
 
 extern "C" hipError_t pfxk_flood_seed(hipStream_t s, uint32_t w, uint32_t seed_x, uint32_t seed_y, uint32_t* d_list)
@@ -394,19 +357,15 @@ extern "C" hipError_t pfxk_wand_mask(hipStream_t s, const uint8_t* d_dist, const
     if (n == 0) return hipSuccess;
     if (combine < 0 || combine > 3 || threshold > 255u) return hipErrorInvalidValue;
     const uint32_t band = aa ? (threshold < 255u ? threshold + 1u : 255u) : 0xffffffffu;
-    const bool vec = aligned_to(d_dist, 4) && aligned_to(d_out, 4) && aligned_to(d_base, 4);
-    if (vec) wand_mask_kernel<true><<<stream_blocks((n + 3u) / 4u), 256, 0, s>>>(d_dist, d_base, d_out, n, threshold, band, combine);
-    else wand_mask_kernel<false><<<stream_blocks(n), 256, 0, s>>>(d_dist, d_base, d_out, n, threshold, band, combine);
-    return hipGetLastError();
+    return launch_stream(aligned_to(d_dist, 4) && aligned_to(d_out, 4) && aligned_to(d_base, 4), n, s, wand_mask_kernel<true>, wand_mask_kernel<false>,
+                         d_dist, d_base, d_out, n, threshold, band, combine);
 }
 
 extern "C" hipError_t pfxk_fill_preview(hipStream_t s, const uint8_t* d_dist, const uint8_t* d_sel, uint8_t* d_out, size_t n, uint32_t threshold, uint32_t fill_rgba)
 {
     if (n == 0) return hipSuccess;
-    const bool vec = aligned_to(d_dist, 4) && aligned_to(d_sel, 4) && aligned_to(d_out, 16);
-    if (vec) fill_preview_kernel<true><<<stream_blocks((n + 3u) / 4u), 256, 0, s>>>(d_dist, d_sel, (uint32_t*)d_out, n, threshold, fill_rgba);
-    else fill_preview_kernel<false><<<stream_blocks(n), 256, 0, s>>>(d_dist, d_sel, (uint32_t*)d_out, n, threshold, fill_rgba);
-    return hipGetLastError();
+    return launch_stream(aligned_to(d_dist, 4) && aligned_to(d_sel, 4) && aligned_to(d_out, 16), n, s, fill_preview_kernel<true>, fill_preview_kernel<false>,
+                         d_dist, d_sel, (uint32_t*)d_out, n, threshold, fill_rgba);
 }
 
 extern "C" hipError_t pfxk_fill_commit(hipStream_t s, uint8_t* d_layer, const uint8_t* d_dist, const uint8_t* d_sel, size_t n, uint32_t threshold, uint32_t fill_rgba,

@@ -7,6 +7,7 @@
 // the anti-diagonals x + y with a block barrier between them (forward passes read the left / up neighbours' NNF, backward passes right / down, so pixels of one
 // diagonal never read each other), and every other step is a map over the boundary list.  One wave per boundary pixel: the patch's pixels spread over the lanes.
 #include "k_libm.h"
+#include "k_tools.h"
 #include "pfx_kernels.h"
 
 namespace {
@@ -419,7 +420,7 @@ pm_geom make_geom(const pfxk_pm_geom* g)
 }
 bool geom_ok(const pfxk_pm_geom* g)
 {
-    return g && g->w && g->h && (uint64_t)g->w * g->h <= 256000000ull && g->bw && g->bh && (uint64_t)g->x0 + g->bw <= g->w && (uint64_t)g->y0 + g->bh <= g->h &&
+    return g && dims_ok(g->w, g->h) && g->bw && g->bh && (uint64_t)g->x0 + g->bw <= g->w && (uint64_t)g->y0 + g->bh <= g->h &&
            g->half >= 1 && g->half <= 5;
 }
 

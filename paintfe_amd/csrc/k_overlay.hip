@@ -12,7 +12,7 @@
 //   preview     render_preview :2168 over every pixel of the document (the output is written whole): NEAREST-scaled pixels straight from the source.
 //   lift        extract_to_overlay :769-777 over the selection's box; any_alpha is its `has_content` :796.
 // No LDS anywhere.  Pixels are indexed in 32 bits: every image here is within pfx_dims_ok (256 Mpx).
-#include "k_common.h"
+#include "k_tools.h"
 #include "pfx_kernels.h"
 
 using namespace pfxk;
@@ -99,7 +99,7 @@ PFX_DEV bool mask_allows(const uint8_t* __restrict__ mask, const pfxk_overlay& P
 template <bool AA, int OVR>
 __global__ __launch_bounds__(256) void commit_kernel(const uint32_t* __restrict__ scaled, const uint8_t* __restrict__ mask, uint32_t* img, uint32_t tiles_x, pfxk_overlay P)
 {
-    const uint32_t bx = (blockIdx.x % tiles_x) * BX + threadIdx.x, by = (blockIdx.x / tiles_x) * BY + threadIdx.y;
+    const auto [bx, by] = tile_xy<BX, BY>(tiles_x, threadIdx.x, threadIdx.y);
     if (bx >= P.box_w || by >= P.box_h) return;
     const uint32_t dx = (uint32_t)P.x0 + bx, dy = (uint32_t)P.y0 + by;
     uint32_t src;
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void commit_kernel(const uint32_t* __restrict_
 template <bool AA>
 __global__ __launch_bounds__(256) void rasterize_kernel(const uint32_t* __restrict__ scaled, uint32_t* __restrict__ out, uint32_t tiles_x, pfxk_overlay P, uint32_t* any)
 {
-    const uint32_t bx = (blockIdx.x % tiles_x) * BX + threadIdx.x, by = (blockIdx.x / tiles_x) * BY + threadIdx.y;
+    const auto [bx, by] = tile_xy<BX, BY>(tiles_x, threadIdx.x, threadIdx.y);
     bool stored = false;
     if (bx < P.box_w && by < P.box_h) {
         uint32_t src;
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void rasterize_kernel(const uint32_t* __restri
 template <bool TRANSLATE>
 __global__ __launch_bounds__(256) void preview_kernel(const uint32_t* __restrict__ source, uint32_t* __restrict__ out, uint32_t doc_w, uint32_t doc_h, uint32_t tiles_x, pfxk_overlay P)
 {
-    const uint32_t x = (blockIdx.x % tiles_x) * BX + threadIdx.x, y = (blockIdx.x / tiles_x) * BY + threadIdx.y;
+    const auto [x, y] = tile_xy<BX, BY>(tiles_x, threadIdx.x, threadIdx.y);
     if (x >= doc_w || y >= doc_h) return;
     uint32_t px = 0u;
     // the box in unsigned arithmetic: x - x0 wraps to a large value left of it (x0 >= 0 here)
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256) void preview_kernel(const uint32_t* __restrict
 __global__ __launch_bounds__(256) void lift_kernel(const uint32_t* __restrict__ layer, const uint8_t* __restrict__ sel, uint32_t* __restrict__ clip, uint8_t* __restrict__ clip_mask,
                                                    uint32_t w, uint32_t x0, uint32_t y0, uint32_t bw, uint32_t bh, uint32_t tiles_x)
 {
-    const uint32_t bx = (blockIdx.x % tiles_x) * BX + threadIdx.x, by = (blockIdx.x / tiles_x) * BY + threadIdx.y;
+    const auto [bx, by] = tile_xy<BX, BY>(tiles_x, threadIdx.x, threadIdx.y);
     if (bx >= bw || by >= bh) return;
     const uint32_t at = (y0 + by) * w + x0 + bx;
     const bool on = sel[at] != 0u;
@@ -166,13 +166,6 @@ __global__ __launch_bounds__(256) void any_alpha_kernel(const uint32_t* __restri
     if (__any(found) && (threadIdx.x & 63u) == 0u) atomicOr(any, 1u);
 }
 
-// blocks of 64 x 4 over bw x bh pixels; 0 = nothing to launch or too many blocks (not within pfx_dims_ok)
-inline uint32_t tile_grid(uint32_t bw, uint32_t bh, uint32_t* tiles_x)
-{
-    *tiles_x = (bw + BX - 1u) / BX;
-    const uint64_t tiles = (uint64_t)*tiles_x * ((bh + BY - 1u) / BY);
-    return tiles > 0x7fffffffull ? 0u : (uint32_t)tiles;
-}
 inline bool box_ok(const pfxk_overlay* P) { return P && P->scaled_w && P->scaled_h && P->source_w && P->source_h && (uint64_t)P->box_w * P->box_h <= 256000000ull; }
 
 } // namespace
@@ -181,7 +174,7 @@ extern "C" hipError_t pfxk_overlay_commit(hipStream_t s, const uint8_t* d_scaled
 {
     if (!box_ok(P) || overwrite < 0 || overwrite > 2 || (overwrite == 2 && !d_mask) || P->x0 < 0 || P->y0 < 0) return hipErrorInvalidValue;
     uint32_t tiles_x;
-    const uint32_t blocks = tile_grid(P->box_w, P->box_h, &tiles_x);
+    const uint32_t blocks = tile_grid<BX, BY>(P->box_w, P->box_h, &tiles_x);
     if (!blocks) return P->box_w && P->box_h ? hipErrorInvalidValue : hipSuccess;
     const dim3 block(BX, BY);
     const uint32_t* sc = (const uint32_t*)d_scaled;
@@ -202,7 +195,7 @@ extern "C" hipError_t pfxk_overlay_rasterize(hipStream_t s, const uint8_t* d_sca
 {
     if (!box_ok(P) || !d_any) return hipErrorInvalidValue;
     uint32_t tiles_x;
-    const uint32_t blocks = tile_grid(P->box_w, P->box_h, &tiles_x);
+    const uint32_t blocks = tile_grid<BX, BY>(P->box_w, P->box_h, &tiles_x);
     if (!blocks) return P->box_w && P->box_h ? hipErrorInvalidValue : hipSuccess;
     if (aa) rasterize_kernel<true><<<blocks, dim3(BX, BY), 0, s>>>((const uint32_t*)d_scaled, (uint32_t*)d_out, tiles_x, *P, d_any);
     else rasterize_kernel<false><<<blocks, dim3(BX, BY), 0, s>>>((const uint32_t*)d_scaled, (uint32_t*)d_out, tiles_x, *P, d_any);
@@ -211,10 +204,10 @@ extern "C" hipError_t pfxk_overlay_rasterize(hipStream_t s, const uint8_t* d_sca
 
 extern "C" hipError_t pfxk_overlay_preview(hipStream_t s, const uint8_t* d_source, uint8_t* d_out, uint32_t doc_w, uint32_t doc_h, const pfxk_overlay* P, int translate)
 {
-    if (!box_ok(P) || !doc_w || !doc_h || (uint64_t)doc_w * doc_h > 256000000ull) return hipErrorInvalidValue;
+    if (!box_ok(P) || !dims_ok(doc_w, doc_h)) return hipErrorInvalidValue;
     if (P->box_w && P->box_h && (P->x0 < 0 || P->y0 < 0 || (uint64_t)P->x0 + P->box_w > doc_w || (uint64_t)P->y0 + P->box_h > doc_h)) return hipErrorInvalidValue;
     uint32_t tiles_x;
-    const uint32_t blocks = tile_grid(doc_w, doc_h, &tiles_x);
+    const uint32_t blocks = tile_grid<BX, BY>(doc_w, doc_h, &tiles_x);
     if (!blocks) return hipErrorInvalidValue;
     if (translate) preview_kernel<true><<<blocks, dim3(BX, BY), 0, s>>>((const uint32_t*)d_source, (uint32_t*)d_out, doc_w, doc_h, tiles_x, *P);
     else preview_kernel<false><<<blocks, dim3(BX, BY), 0, s>>>((const uint32_t*)d_source, (uint32_t*)d_out, doc_w, doc_h, tiles_x, *P);
@@ -226,7 +219,7 @@ extern "C" hipError_t pfxk_overlay_lift(hipStream_t s, const uint8_t* d_layer, c
 {
     if (!bw || !bh || (uint64_t)x0 + bw > w) return hipErrorInvalidValue;
     uint32_t tiles_x;
-    const uint32_t blocks = tile_grid(bw, bh, &tiles_x);
+    const uint32_t blocks = tile_grid<BX, BY>(bw, bh, &tiles_x);
     if (!blocks) return hipErrorInvalidValue;
     lift_kernel<<<blocks, dim3(BX, BY), 0, s>>>((const uint32_t*)d_layer, d_sel, (uint32_t*)d_clip, d_clip_mask, w, x0, y0, bw, bh, tiles_x);
     return hipGetLastError();
@@ -235,7 +228,6 @@ extern "C" hipError_t pfxk_overlay_lift(hipStream_t s, const uint8_t* d_layer, c
 extern "C" hipError_t pfxk_overlay_any_alpha(hipStream_t s, const uint8_t* d_img, size_t n, uint32_t* d_any)
 {
     if (n == 0) return hipSuccess;
-    const size_t b = (n + 255u) / 256u;
-    any_alpha_kernel<<<(uint32_t)(b > 8192u ? 8192u : b), 256, 0, s>>>((const uint32_t*)d_img, n, d_any);
+    any_alpha_kernel<<<stream_blocks(n), 256, 0, s>>>((const uint32_t*)d_img, n, d_any);
     return hipGetLastError();
 }

@@ -12,7 +12,7 @@
 //               walks its row segment in steps, V slides a running sum down a band of rows.  Neither does work per pixel that grows with the radius: the
 //               host scales the segment and the band with r.
 //   streaming   translate, bounds (block reduction + four atomics), fill / delete of an RGBA8 layer through a grey mask.
-#include "k_common.h"
+#include "k_tools.h"
 #include "pfx_kernels.h"
 
 using namespace pfxk;
@@ -21,9 +21,6 @@ namespace {
 
 constexpr uint32_t STEP = PFXK_SELECT_SEG;   // threads of a row-walking workgroup = pixels per step
 constexpr uint32_t RING = 2048;              // feather H: prefix sums kept; >= 2 * PFXK_SELECT_FEATHER_MAX + 1 + 2 * STEP - 1
-
-PFX_DEV uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
-PFX_DEV uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
 
 // the one combine rule (apply_selection_shape :1743-1801 and the lasso merge :41-86 agree on it for every byte of base; tests/test_select_model_host.py)
 PFX_DEV uint32_t combine_px(uint32_t base, bool raw, int mode)
@@ -44,26 +41,19 @@ PFX_DEV bool shape_px(const pfxk_select_shape& S, uint32_t x, uint32_t y)
 template <bool VEC>
 __global__ __launch_bounds__(256) void shape_combine_kernel(const uint8_t* base, uint8_t* out, uint32_t w, uint32_t n, pfxk_select_shape S, int mode)
 {
-    const uint32_t first = blockIdx.x * 256u + threadIdx.x, stride = gridDim.x * 256u;
-    uint32_t done = 0;
-    if constexpr (VEC) {
-        const uint32_t groups = n / 4u;
-        for (uint32_t g = first; g < groups; g += stride) {
-            const uint32_t bv = base ? reinterpret_cast<const uint32_t*>(base)[g] : 0u;
-            uint32_t y = (g * 4u) / w, x = g * 4u - y * w, o = 0u;
+    stream_walk<VEC, uint32_t>(n, [&](uint32_t g) {
+        const uint32_t bv = base ? reinterpret_cast<const uint32_t*>(base)[g] : 0u;
+        uint32_t y = (g * 4u) / w, x = g * 4u - y * w, o = 0u;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                o |= combine_px((bv >> (8 * k)) & 0xffu, shape_px(S, x, y), mode) << (8 * k);
-                if (++x == w) { x = 0; ++y; }
-            }
-            reinterpret_cast<uint32_t*>(out)[g] = o;
+        for (int k = 0; k < 4; ++k) {
+            o |= combine_px((bv >> (8 * k)) & 0xffu, shape_px(S, x, y), mode) << (8 * k);
+            if (++x == w) { x = 0; ++y; }
         }
-        done = groups * 4u;
-    }
-    for (uint32_t i = done + first; i < n; i += stride) {
+        reinterpret_cast<uint32_t*>(out)[g] = o;
+    }, [&](uint32_t i) {
         const uint32_t y = i / w, x = i - y * w;
         out[i] = (uint8_t)combine_px(base ? base[i] : 0u, shape_px(S, x, y), mode);
-    }
+    });
 }
 
 // Rust's `v as u32` for a finite v >= 0 (the host refuses coordinates beyond 1e9, so nothing here is near 2^32; the clamp keeps the cast defined anyway)
@@ -314,24 +304,15 @@ __global__ __launch_bounds__(256) void feather_v_kernel(const uint8_t* __restric
     }
 }
 
-inline uint32_t stream_blocks(size_t items)
-{
-    const size_t b = (items + 255u) / 256u;
-    return (uint32_t)(b < 1u ? 1u : (b > 8192u ? 8192u : b));
-}
-inline bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1u)) == 0u; }
 inline uint32_t capped(uint32_t v, uint32_t cap) { return v < cap ? v : cap; }
-inline bool dims_ok(uint32_t w, uint32_t h) { return w != 0 && h != 0 && (uint64_t)w * h <= 0x10000000ull; }   // pixel indices stay below 2^28 (the ABI's limit is 256 000 000)
 
 } // namespace
 
 extern "C" hipError_t pfxk_select_shape_combine(hipStream_t s, const uint8_t* d_base, uint8_t* d_out, uint32_t w, uint32_t h, const pfxk_select_shape* S, int mode)
 {
     if (!dims_ok(w, h) || mode < 0 || mode > 3 || S->kind > 1u) return hipErrorInvalidValue;
-    const uint32_t n = w * h;
-    if (aligned_to(d_base, 4) && aligned_to(d_out, 4)) shape_combine_kernel<true><<<stream_blocks((n + 3u) / 4u), 256, 0, s>>>(d_base, d_out, w, n, *S, mode);
-    else shape_combine_kernel<false><<<stream_blocks(n), 256, 0, s>>>(d_base, d_out, w, n, *S, mode);
-    return hipGetLastError();
+    return launch_stream(aligned_to(d_base, 4) && aligned_to(d_out, 4), (size_t)w * h, s, shape_combine_kernel<true>, shape_combine_kernel<false>, d_base, d_out, w,
+                         w * h, *S, mode);
 }
 
 extern "C" hipError_t pfxk_select_lasso(hipStream_t s, const float* d_points_xy, uint32_t n_points, const uint8_t* d_base, uint8_t* d_out, uint32_t w, uint32_t h, int mode)

@@ -21,7 +21,7 @@
 // Three forms of one kernel: the box buffer (`buf` of the reference), the whole-canvas preview (tests/visual_shapes.rs:18-41: box pixels with a > 0 on
 // a zeroed canvas), and rasterise + commit in place (blend_pixel_static(layer, pixel, mode, 1.0) where a > 0 and the selection allows: what
 // pfx_brush_commit does with the preview) without an intermediate buffer.
-#include "k_common.h"
+#include "k_tools.h"
 #include "k_blend.h"
 #include "pfx_kernels.h"
 
@@ -48,11 +48,6 @@ PFX_DEV float sdf_line_segment(float px, float py, float ax, float ay, float bx,
     const float cx = ax + t * dx, cy = ay + t * dy;
     return __builtin_sqrtf((px - cx) * (px - cx) + (py - cy) * (py - cy));
 }
-
-// glibc's f32 routines evaluated through f64 (see the file header)
-PFX_DEV float libm_atan2(float y, float x) { return (float)atan2((double)y, (double)x); }
-PFX_DEV float libm_cos(float x) { return (float)cos((double)x); }
-PFX_DEV float libm_sin(float x) { return (float)sin((double)x); }
 
 template <int SDF>
 PFX_DEV float shape_sdf(float px, float py, const pfxk_shape_params& P)

@@ -15,7 +15,7 @@
 //   compose   one thread per pixel runs shadow, outline, fill, inside outline, inner shadow in that order on a pixel in registers and stores it once.
 //   bounds    find_tight_bounds_rgba: workgroups walk whole rows, reduce in LDS and issue an atomic maximum only where it would move the box.
 // Pixels are indexed in 32 bits: every image here is within pfx_dims_ok (256 Mpx).
-#include "k_common.h"
+#include "k_tools.h"
 #include "pfx_kernels.h"
 
 using namespace pfxk;
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(DISC_THREADS) void disc_kernel(const uint8_t* __res
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t disc_lds[];   // [levels][ch][ls]
     const uint32_t R = (uint32_t)D.radius, cw = DISC_TW + 2u * R, ch = DISC_TH + 2u * R, ls = (cw + 3u) & ~3u, plane = ls * ch;
-    const uint32_t x0 = (blockIdx.x % tiles_x) * DISC_TW, y0 = (blockIdx.x / tiles_x) * DISC_TH;
+    const auto [x0, y0] = tile_xy<DISC_TW, DISC_TH>(tiles_x);
     constexpr uint32_t DISC_WAVES = DISC_THREADS / 64u;
     const uint32_t lx = threadIdx.x & 63u, ly = threadIdx.x >> 6;   // lane and wave: a wave takes whole tile rows, so no index is ever divided
     for (uint32_t ty = ly; ty < ch; ty += DISC_WAVES) {
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(DISC_THREADS) void disc_kernel(const uint8_t* __res
 __global__ __launch_bounds__(256) void plane_kernel(const uint32_t* __restrict__ text, uint8_t* __restrict__ out, uint32_t w, uint32_t h, uint32_t tiles_x, int32_t dx,
                                                     int32_t dy, uint32_t alpha, int inner)
 {
-    const uint32_t x = (blockIdx.x % tiles_x) * BX + threadIdx.x, y = (blockIdx.x / tiles_x) * BY + threadIdx.y;
+    const auto [x, y] = tile_xy<BX, BY>(tiles_x, threadIdx.x, threadIdx.y);
     if (x >= w || y >= h) return;
     const int64_t sx = (int64_t)x - dx, sy = (int64_t)y - dy;
     const bool inside = sx >= 0 && sy >= 0 && sx < (int64_t)w && sy < (int64_t)h;
@@ -151,7 +151,7 @@ PFX_DEV uint32_t outline_alpha(float a, float b, float oa)
 __global__ __launch_bounds__(256) void compose_kernel(const uint32_t* __restrict__ text, const uint32_t* __restrict__ texture, uint32_t* __restrict__ out, uint32_t tiles_x,
                                                       const pfxk_textfx P)
 {
-    const uint32_t x = (blockIdx.x % tiles_x) * BX + threadIdx.x, y = (blockIdx.x / tiles_x) * BY + threadIdx.y;
+    const auto [x, y] = tile_xy<BX, BY>(tiles_x, threadIdx.x, threadIdx.y);
     if (x >= P.w || y >= P.h) return;
     const size_t at = (size_t)y * P.w + x;
     const uint32_t t = text[at], ta = t >> 24;
@@ -244,14 +244,6 @@ __global__ __launch_bounds__(256) void bounds_kernel(const uint32_t* __restrict_
     if (k == 0u && got[4] == 0u) atomicOr(got + 4, 1u);
 }
 
-inline bool dims_ok(uint32_t w, uint32_t h) { return w && h && (uint64_t)w * h <= 256000000ull; }
-// blocks of 64 x 4 over w x h pixels
-inline uint32_t tile_grid(uint32_t w, uint32_t h, uint32_t* tiles_x)
-{
-    *tiles_x = (w + BX - 1u) / BX;
-    return *tiles_x * ((h + BY - 1u) / BY);
-}
-
 } // namespace
 
 extern "C" hipError_t pfxk_textfx_disc(hipStream_t s, const uint8_t* d_src, uint32_t src_stride, uint32_t src_offset, uint8_t* d_dst, uint32_t w, uint32_t h,
@@ -284,7 +276,7 @@ extern "C" hipError_t pfxk_textfx_plane(hipStream_t s, const uint8_t* d_text, ui
 {
     if (!dims_ok(w, h) || alpha > 255u) return hipErrorInvalidValue;
     uint32_t tiles_x;
-    const uint32_t blocks = tile_grid(w, h, &tiles_x);
+    const uint32_t blocks = tile_grid<BX, BY>(w, h, &tiles_x);
     plane_kernel<<<blocks, dim3(BX, BY), 0, s>>>((const uint32_t*)d_text, d_plane, w, h, tiles_x, dx, dy, alpha, inner);
     return hipGetLastError();
 }
@@ -305,7 +297,7 @@ extern "C" hipError_t pfxk_textfx_compose(hipStream_t s, const uint8_t* d_text, 
         ((f & PFXK_TFX_INNER_BLURRED) && !P->inner) || ((f & PFXK_TFX_TEXTURE) && (!d_texture || !dims_ok(P->tex_w, P->tex_h))))
         return hipErrorInvalidValue;
     uint32_t tiles_x;
-    const uint32_t blocks = tile_grid(P->w, P->h, &tiles_x);
+    const uint32_t blocks = tile_grid<BX, BY>(P->w, P->h, &tiles_x);
     compose_kernel<<<blocks, dim3(BX, BY), 0, s>>>((const uint32_t*)d_text, (const uint32_t*)d_texture, (uint32_t*)d_out, tiles_x, *P);
     return hipGetLastError();
 }

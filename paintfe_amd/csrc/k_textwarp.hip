@@ -12,10 +12,10 @@
 //             in LDS (every lane reads the same word: a broadcast); the coarse search is 65 distances, the eight refinement steps stay per pixel.
 //   envelope  :495-536.  t, top_y and span depend on the column alone, and so does the x half of bilinear_sample: one output column per lane, the column's
 //             part in registers for 32 rows, the taps of four rows in flight together (envelope_kernel).
-//   atan2     the project's device flavour: the f64 atan2 rounded once to f32 (k_shapes.hip's libm_atan2).  It is the register-heavy part, so each warp is a
+//   atan2     the project's device flavour: the f64 atan2 rounded once to f32 (k_tools.h's libm_atan2).  It is the register-heavy part, so each warp is a
 //             kernel of its own and the path and envelope kernels do not carry its registers.
 // This bilinear is neither transform.rs's nor effects.rs's: nothing is shared with k_warp.hip or k_resize.hip.  Pixels are indexed within pfx_dims_ok (256 Mpx).
-#include "k_common.h"
+#include "k_tools.h"
 #include "pfx_kernels.h"
 
 using namespace pfxk;
@@ -24,8 +24,6 @@ namespace {
 
 constexpr uint32_t TW = 256, TH = 16, PX = 4, WAVES = 4;   // tile; pixels per lane; waves per workgroup
 constexpr float TAU = 6.28318530717958647692f;
-
-PFX_DEV float libm_atan2(float y, float x) { return (float)atan2((double)y, (double)x); }
 
 // bilinear_sample :707-740 for 0 <= x < w, 0 <= y < h (the callers' tests).  x0 and y0 are then inside: w is src_w rounded to f32, and the largest f32
 // below it is at most src_w - 1 whichever way that rounded; only the +1 taps can fall past the edge, where they are transparent
@@ -63,7 +61,7 @@ PFX_DEV void store_px(uint32_t* __restrict__ out, uint32_t out_w, uint32_t x, ui
 template <class F>
 PFX_DEV void walk_tile(uint32_t* __restrict__ out, uint32_t out_w, uint32_t out_h, uint32_t tiles_x, F pixel)
 {
-    const uint32_t x = (blockIdx.x % tiles_x) * TW + (threadIdx.x & 63u) * PX, y0 = (blockIdx.x / tiles_x) * TH + (threadIdx.x >> 6);
+    const auto [x, y0] = tile_xy<TW, TH>(tiles_x, (threadIdx.x & 63u) * PX, threadIdx.x >> 6);
     if (x >= out_w) return;
     for (uint32_t y = y0; y < out_h && y < y0 + TH; y += WAVES) {
         uint32_t px[PX];
@@ -288,18 +286,12 @@ __global__ __launch_bounds__(256) void rotate_kernel(const uint32_t* __restrict_
 __global__ __launch_bounds__(256) void blit_kernel(const uint32_t* __restrict__ buf, uint32_t bw, uint32_t bx0, uint32_t by0, uint32_t rw, uint32_t rh,
                                                    uint32_t* __restrict__ canvas, uint32_t cw, uint32_t cx0, uint32_t cy0, uint32_t tiles_x)
 {
-    const uint32_t x = (blockIdx.x % tiles_x) * 64u + threadIdx.x, y = (blockIdx.x / tiles_x) * 4u + threadIdx.y;
+    const auto [x, y] = tile_xy<64, 4>(tiles_x, threadIdx.x, threadIdx.y);
     if (x >= rw || y >= rh) return;
     const uint32_t s = buf[(size_t)(by0 + y) * bw + bx0 + x];
     if (s >> 24) canvas[(size_t)(cy0 + y) * cw + cx0 + x] = s;
 }
 
-inline bool dims_ok(uint32_t w, uint32_t h) { return w && h && (uint64_t)w * h <= 256000000ull; }
-inline uint32_t tile_grid(uint32_t w, uint32_t h, uint32_t* tiles_x)
-{
-    *tiles_x = (w + TW - 1u) / TW;
-    return *tiles_x * ((h + TH - 1u) / TH);
-}
 inline bool warp_ok(const uint8_t* d_src, uint8_t* d_out, const pfxk_textwarp* P)
 {
     return d_src && d_out && P && dims_ok(P->src_w, P->src_h) && dims_ok(P->out_w, P->out_h);
@@ -311,7 +303,7 @@ extern "C" hipError_t pfxk_textwarp_arc(hipStream_t s, const uint8_t* d_src, uin
 {
     if (!warp_ok(d_src, d_out, P)) return hipErrorInvalidValue;
     uint32_t tiles_x;
-    const uint32_t blocks = tile_grid(P->out_w, P->out_h, &tiles_x);
+    const uint32_t blocks = tile_grid<TW, TH>(P->out_w, P->out_h, &tiles_x);
     arc_kernel<<<blocks, 256, 0, s>>>((const uint32_t*)d_src, (uint32_t*)d_out, tiles_x, *P);
     return hipGetLastError();
 }
@@ -322,7 +314,7 @@ extern "C" hipError_t pfxk_textwarp_circular(hipStream_t s, const uint8_t* d_src
     // |pixel_angle| <= pi and |start_angle| <= 8 pi keep each of the kernel's two loops to five steps; anything else is not launched
     if (!(__builtin_fabsf(P->start_angle) <= 25.2f) || !(P->dir == 1.0f || P->dir == -1.0f)) return hipErrorInvalidValue;
     uint32_t tiles_x;
-    const uint32_t blocks = tile_grid(P->out_w, P->out_h, &tiles_x);
+    const uint32_t blocks = tile_grid<TW, TH>(P->out_w, P->out_h, &tiles_x);
     circular_kernel<<<blocks, 256, 0, s>>>((const uint32_t*)d_src, (uint32_t*)d_out, tiles_x, *P);
     return hipGetLastError();
 }
@@ -331,7 +323,7 @@ extern "C" hipError_t pfxk_textwarp_path(hipStream_t s, const uint8_t* d_src, ui
 {
     if (!warp_ok(d_src, d_out, P) || !T) return hipErrorInvalidValue;
     uint32_t tiles_x;
-    const uint32_t blocks = tile_grid(P->out_w, P->out_h, &tiles_x);
+    const uint32_t blocks = tile_grid<TW, TH>(P->out_w, P->out_h, &tiles_x);
     path_kernel<<<blocks, 256, 0, s>>>((const uint32_t*)d_src, (uint32_t*)d_out, tiles_x, *P, *T);
     return hipGetLastError();
 }
@@ -352,7 +344,7 @@ extern "C" hipError_t pfxk_textwarp_rotate(hipStream_t s, const uint8_t* d_src, 
 {
     if (!d_src || !d_out || !R || !dims_ok(R->w, R->h) || !dims_ok(R->new_w, R->new_h)) return hipErrorInvalidValue;
     uint32_t tiles_x;
-    const uint32_t blocks = tile_grid(R->new_w, R->new_h, &tiles_x);
+    const uint32_t blocks = tile_grid<TW, TH>(R->new_w, R->new_h, &tiles_x);
     rotate_kernel<<<blocks, 256, 0, s>>>((const uint32_t*)d_src, (uint32_t*)d_out, tiles_x, *R);
     return hipGetLastError();
 }

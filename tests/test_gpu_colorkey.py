@@ -9,10 +9,10 @@ import pytest
 
 from . import colorkey_cases as CC
 from . import colorkey_model as M
+from .dev_buffers import SENTINEL, DevBuffers, sentinel_like
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
 OK, ERR_INVALID, ERR_UNSUPPORTED = 0, -1, -5
 
 
@@ -20,27 +20,6 @@ OK, ERR_INVALID, ERR_UNSUPPORTED = 0, -1, -5
 def gpu():
     from paintfe_amd import GpuRenderer
     return GpuRenderer(0)
-
-
-class DevBuffers:
-    """arrays uploaded to device allocations, freed on exit"""
-    def __init__(self, gpu, *arrays):
-        self.gpu, self.arrays, self.ptrs = gpu, [np.ascontiguousarray(a, np.uint8) for a in arrays], []
-
-    def __enter__(self):
-        for a in self.arrays:
-            p = self.gpu.dev_alloc(a.nbytes)
-            self.ptrs.append(p)
-            self.gpu.dev_upload(p, a)
-        return self.ptrs
-
-    def __exit__(self, *exc):
-        for p in self.ptrs:
-            self.gpu.dev_free(p)
-
-
-def sentinel_like(img):
-    return np.full(img.shape, SENTINEL, np.uint8)
 
 
 def status_of(fn):

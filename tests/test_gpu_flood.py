@@ -6,34 +6,17 @@ import pytest
 
 from . import flood_cases as FC
 from . import flood_model as M
+from .dev_buffers import SENTINEL, DevBuffers
 
 pytestmark = pytest.mark.gpu
 
 NORMAL, MULTIPLY, OVERWRITE = 0, 1, 14
-SENTINEL = 0xA5
 
 
 @pytest.fixture(scope="module")
 def gpu():
     from paintfe_amd import GpuRenderer
     return GpuRenderer(0)
-
-
-class DevBuffers:
-    """arrays uploaded to device allocations, freed on exit"""
-    def __init__(self, gpu, *arrays):
-        self.gpu, self.arrays, self.ptrs = gpu, [np.ascontiguousarray(a, np.uint8) for a in arrays], []
-
-    def __enter__(self):
-        for a in self.arrays:
-            p = self.gpu.dev_alloc(a.nbytes)
-            self.ptrs.append(p)
-            self.gpu.dev_upload(p, a)
-        return self.ptrs
-
-    def __exit__(self, *exc):
-        for p in self.ptrs:
-            self.gpu.dev_free(p)
 
 
 def pass_cap(w, h):

@@ -7,6 +7,7 @@ import pytest
 
 from . import inpaint_cases as IC
 from . import inpaint_model as M
+from .dev_buffers import DevBuffers
 
 pytestmark = pytest.mark.gpu
 
@@ -20,23 +21,6 @@ def gpu():
 @pytest.fixture(scope="module")
 def goldens():
     return IC.load_goldens()
-
-
-class DevBuffers:
-    """arrays uploaded to device allocations, freed on exit"""
-    def __init__(self, gpu, *arrays):
-        self.gpu, self.arrays, self.ptrs = gpu, [np.ascontiguousarray(a, np.uint8) for a in arrays], []
-
-    def __enter__(self):
-        for a in self.arrays:
-            p = self.gpu.dev_alloc(a.nbytes)
-            self.ptrs.append(p)
-            self.gpu.dev_upload(p, a)
-        return self.ptrs
-
-    def __exit__(self, *exc):
-        for p in self.ptrs:
-            self.gpu.dev_free(p)
 
 
 def instant_dev(gpu, src, mask, out, dabs):

@@ -8,13 +8,12 @@ import pytest
 
 from . import overlay_cases as OC
 from . import overlay_model as M
+from .dev_buffers import SENTINEL, DevBuffers, differing, sentinel_like
 from .test_overlay_model_host import describe
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
 OK, ERR_INVALID = 0, -1
-TAIL = 64   # sentinel bytes behind every buffer
 
 
 @pytest.fixture(scope="module")
@@ -32,41 +31,6 @@ def stop_after_a_device_error(gpu):
         gpu.synchronize()
     except PfxError as e:
         pytest.exit(f"the device reported an error after this test: {e}", returncode=3)
-
-
-class DevBuffers:
-    """arrays uploaded to device allocations `lead` bytes in, with sentinel bytes before and behind; freed on exit"""
-    def __init__(self, gpu, *arrays, lead=0):
-        self.gpu, self.arrays, self.lead, self.bases = gpu, [np.ascontiguousarray(a, np.uint8) for a in arrays], lead, []
-
-    def __enter__(self):
-        ptrs = []
-        for a in self.arrays:
-            padded = np.concatenate([np.full(self.lead, SENTINEL, np.uint8), a.ravel(), np.full(TAIL, SENTINEL, np.uint8)])
-            p = self.gpu.dev_alloc(padded.nbytes)
-            self.bases.append(p)
-            self.gpu.dev_upload(p, padded)
-            ptrs.append(p + self.lead)
-        return ptrs
-
-    def surroundings_intact(self):
-        for p, a in zip(self.bases, self.arrays):
-            got = self.gpu.dev_download(p, (self.lead + a.size + TAIL,))
-            if not ((got[:self.lead] == SENTINEL).all() and (got[self.lead + a.size:] == SENTINEL).all()):
-                return False
-        return True
-
-    def __exit__(self, *exc):
-        for p in self.bases:
-            self.gpu.dev_free(p)
-
-
-def sentinel_like(img):
-    return np.full(img.shape, SENTINEL, np.uint8)
-
-
-def differing(got, want):
-    return int((got != want).any(axis=-1).sum())
 
 
 # ---- commit --------------------------------------------------------------------------------------------------------------------------------------------------------

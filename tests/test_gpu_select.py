@@ -6,11 +6,10 @@ import pytest
 
 from . import select_cases as SC
 from . import select_model as M
+from .dev_buffers import SENTINEL, Dev
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
-GUARD = 32
 INT32_MIN = -2 ** 31
 ERR_INVALID, ERR_UNSUPPORTED = -1, -5
 MODE_NAMES = ["replace", "add", "subtract", "intersect"]
@@ -21,38 +20,6 @@ sizes = pytest.mark.parametrize("size", SC.SIZES, ids=SC.size_id)
 def gpu():
     from paintfe_amd import GpuRenderer
     return GpuRenderer(0)
-
-
-class Dev:
-    """device copies of arrays between GUARD sentinel bytes, `offset` bytes past a 256-byte aligned address; freed on exit"""
-    def __init__(self, gpu):
-        self.gpu, self.blocks = gpu, {}
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for base, _, _ in self.blocks.values():
-            self.gpu.dev_free(base)
-
-    def put(self, array, offset=0):
-        a = np.ascontiguousarray(array)
-        image = np.full(a.nbytes + 2 * GUARD, SENTINEL, np.uint8)
-        image[GUARD + offset:GUARD + offset + a.nbytes] = a.reshape(-1).view(np.uint8)
-        base = self.gpu.dev_alloc(image.nbytes)
-        self.gpu.dev_upload(base, image)
-        self.blocks[base + GUARD + offset] = (base, a.nbytes, offset)
-        return base + GUARD + offset
-
-    def sentinel(self, shape, offset=0):
-        return self.put(np.full(shape, SENTINEL, np.uint8), offset)
-
-    def get(self, ptr, shape):
-        """the array, after checking that the guard bytes around it are intact"""
-        base, nbytes, offset = self.blocks[ptr]
-        image = self.gpu.dev_download(base, (nbytes + 2 * GUARD,))
-        assert (image[:GUARD + offset] == SENTINEL).all() and (image[GUARD + offset + nbytes:] == SENTINEL).all(), "a write outside the buffer"
-        return image[GUARD + offset:GUARD + offset + nbytes].reshape(shape)
 
 
 def refused(status, call, *args, **kwargs):

@@ -9,7 +9,7 @@ import pytest
 
 from . import textfx_cases as TC
 from . import textfx_model as M
-from .test_gpu_overlay import SENTINEL, DevBuffers, sentinel_like
+from .dev_buffers import SENTINEL, DevBuffers, differing, sentinel_like
 
 pytestmark = pytest.mark.gpu
 
@@ -39,10 +39,6 @@ def stop_after_a_device_error(gpu):
 def describe(size, effects):
     from paintfe_amd import text_effects
     return text_effects(size, **effects)
-
-
-def differing(got, want):
-    return int((got != want).any(axis=-1).sum())
 
 
 def run_dev(gpu, fx, text, texture, call="effects"):

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from . import textfx_disc_cases as DC
-from .test_gpu_overlay import SENTINEL, DevBuffers, sentinel_like
+from .dev_buffers import SENTINEL, DevBuffers, sentinel_like
 
 pytestmark = pytest.mark.gpu
 

@@ -13,7 +13,7 @@ from . import textfx_model as FXM
 from . import textwarp_cases as TC
 from . import textwarp_model as M
 from .libm_checks import LIBM, check_glibc
-from .test_gpu_overlay import SENTINEL, DevBuffers, sentinel_like
+from .dev_buffers import SENTINEL, DevBuffers, differing, sentinel_like
 
 pytestmark = pytest.mark.gpu
 
@@ -35,10 +35,6 @@ def stop_after_a_device_error(gpu):
         gpu.synchronize()
     except PfxError as e:
         pytest.exit(f"the device reported an error after this test: {e}", returncode=3)
-
-
-def differing(got, want):
-    return int((got != want).any(axis=-1).sum())
 
 
 def hold_to_the_libm_models(got, device, ambiguous, glibc, what):

@@ -1169,6 +1169,74 @@ typedef struct pfx_text_block {           /* one block's tight raster on its way
  * the canvas changes nothing */
 int pfx_text_block_place_dev(pfx_ctx* ctx, const pfx_text_block* block, const void* src_dev, void* canvas_dev);
 
+/* ================= gradient tool and perspective crop (ref: src/ui/panels/tools/behavior/raster/perspective_gradient.rs, tools/state.rs:1063-1171,
+ * gradient_text/gradient_controls.rs:63-122) =================
+ * The Gradient tool's drag frame, release and commit, and the PerspectiveCrop tool's re-sampling of every layer.  The gradient follows the reference's CPU
+ * path :386-548 (start and end are NOT divided by the preview scale, unlike its WGSL branch) and that loop's own `t` formulas, not
+ * GradientToolState::compute_t.  A drag frame stays on the device: pfx_gradient_render_dev, then pfx_flatten_preview_dev with that preview
+ * (pfx_preview.is_eraser set in transparency mode).
+ *   LUT      256 RGBA8 entries (1024 bytes), built on the host by pfx_gradient_build_lut as rebuild_lut does: no stop -> zeros; one stop -> its colour;
+ *            else a stable sort by position, entry i at t = i / 255.0f: t <= first position -> first colour, t >= last -> last, else the FIRST pair with
+ *            left <= t <= right, local_t = span > 0 ? (t - left) / span : 0, round(l * (1 - local_t) + r * local_t) per channel.
+ *   render   per generated pixel (x, y) of gen_w x gen_h, gen = ceil(dim / preview_scale): px = x * scale + scale * 0.5 (f32), the selection byte at
+ *            (x * scale, y * scale): 0 leaves (0, 0, 0, 0).  With d = end - start, len_sq = dx dx + dy dy, len = sqrt(len_sq), inv_len = len > 1e-6 ? 1 / len :
+ *            0, inv_len_sq likewise on len_sq, u = d * inv_len, r = p - start:  linear raw = (rx dx + ry dy) * inv_len_sq, t = clamp(raw, 0, 1) or
+ *            raw.rem_euclid(1) with repeat;  reflected t = 1 - |2 clamp(raw, 0, 1) - 1|, or m = raw.rem_euclid(2), t = m > 1 ? 2 - m : m;  radial raw =
+ *            sqrt(rx rx + ry ry) * inv_len;  diamond raw = |rx ux + ry uy| * inv_len + |rx (-uy) + ry ux| * inv_len;  both then clamped or rem_euclid(1).
+ *            idx = (t * 255.0) truncated (NaN -> 0), a = lut[idx].a, a selection byte below 255 gives a = a * sel / 255 in integers; a == 0 leaves
+ *            (0, 0, 0, 0), else the LUT's rgb and a.  In transparency mode the LUT is first baked as :395-409 does (rgb = 255, a = lum * a / 255 with lum =
+ *            (0.299 r + 0.587 g + 0.114 b) truncated): callers hand over the RAW LUT.  The optional second output is preview_flat_buffer :559-572, the
+ *            premultiplied copy ((c * a + 128) / 255, alpha copied).  Every byte of both outputs is written.
+ *   commit   the full-resolution preview onto the layer in place: preview alpha 0 keeps the pixel; transparency mode (is_eraser) a = round(max(cur_a *
+ *            (1 - strength), 0) * 255), rgb kept; colour mode src-over in f32 :99-117, round() half away from zero.  The selection is not consulted.
+ *   apply    render at preview_scale 1 plus commit in one kernel, no preview buffer; equals the two calls.
+ *   crop     pfx_perspective_crop_plan :100-125: min / max over the four corners (TL, TR, BR, BL), clamped to [0, w] x [0, h], out = round(max - min); where
+ *            the reference returns None (out_w < 2 or out_h < 2) the plan is PFX_OK with 0 x 0 and the crop calls return PFX_ERR_INVALID.  Per output pixel
+ *            u = (ox + 0.5) / out_w, v likewise, src = (1-u)(1-v) c0 + u (1-v) c1 + u v c2 + (1-u) v c3, then bilinear_sample :186-233: x0 = clamp(floor(x),
+ *            0, w - 1), x1 = min(x0 + 1, w - 1), fx = x - floor(x) from the unclamped coordinate, three lerps per channel each rounded to u8.  Every layer
+ *            goes through the same map in one launch; outputs are out_w * out_h RGBA8 each, every byte written.
+ * Everything is in the bit-exact class: single correctly rounded f32 operations (+, *, /, sqrt, an exact remainder), comparisons and integer arithmetic.
+ * Refused with PFX_ERR_INVALID before anything is launched and with outputs untouched: a NULL descriptor, LUT or required pointer; a start or end that is
+ * not finite; a shape outside PFX_GRADIENT_*; a mode other than 0 / 1; preview_scale 0 (pfx_gradient_apply_dev: other than 1); w * h outside the document
+ * limit; an RGBA8 device pointer that is not 4-byte aligned; an output that overlaps an input or another output (the layer of commit / apply IS in place;
+ * it must not overlap the preview or the selection); for the crop, a corner that is not finite, n_layers 0 or above PFX_CROP_MAX_LAYERS, a planned size
+ * of 0 x 0.  The context-free helpers return PFX_ERR_INVALID (pfx_gradient_drag_scale: 1) for NULL or non-finite arguments.
+ * `layer_ptrs_dev` / `cropped_ptrs_dev` are host arrays of device pointers, as pfx_flatten_dev's are. */
+enum { PFX_GRADIENT_LINEAR = 0, PFX_GRADIENT_LINEAR_REFLECTED = 1, PFX_GRADIENT_RADIAL = 2, PFX_GRADIENT_DIAMOND = 3 };   /* GradientShape */
+enum { PFX_GRADIENT_MODE_COLOR = 0, PFX_GRADIENT_MODE_TRANSPARENCY = 1 };                                                /* GradientMode */
+enum { PFX_GRADIENT_PRESET_PRIMARY_SECONDARY = 0, PFX_GRADIENT_PRESET_BLACK_WHITE = 1, PFX_GRADIENT_PRESET_FOREGROUND_TRANSPARENT = 2,
+       PFX_GRADIENT_PRESET_RAINBOW = 3 };                                                                                /* GradientPreset, less Custom */
+#define PFX_GRADIENT_MAX_PRESET_STOPS 7
+#define PFX_CROP_MAX_LAYERS 1024
+typedef struct pfx_gradient_stop { float position; uint8_t color[4]; } pfx_gradient_stop;   /* GradientStop */
+typedef struct pfx_gradient {
+    float    start_x, start_y, end_x, end_y;   /* drag_start, drag_end in canvas coordinates */
+    int32_t  shape;                            /* PFX_GRADIENT_* */
+    int32_t  repeat;                           /* 0 / non-zero */
+    int32_t  mode;                             /* PFX_GRADIENT_MODE_* */
+    uint32_t preview_scale;                    /* >= 1; pfx_gradient_drag_scale while dragging, 1 on release */
+} pfx_gradient;
+/* host only, no context */
+int pfx_gradient_build_lut(const pfx_gradient_stop* stops, uint32_t n_stops, uint8_t lut[1024]);   /* stops may be NULL when n_stops is 0 */
+int pfx_gradient_preset_stops(int preset, const uint8_t primary[4], const uint8_t secondary[4], pfx_gradient_stop stops_out[PFX_GRADIENT_MAX_PRESET_STOPS],
+                              uint32_t* n_stops_out);
+int pfx_gradient_bake_eraser_lut(const uint8_t lut[1024], uint8_t baked[1024]);
+uint32_t pfx_gradient_drag_scale(uint32_t w, uint32_t h);   /* :291-300: 1 up to 1 500 000 pixels, else max(2, ceil(sqrt(pixels / 1e6))) in f64 */
+/* sel_dev: w * h bytes or NULL; preview_dev, premul_dev (may be NULL): gen_w * gen_h RGBA8; asynchronous on the context's stream */
+int pfx_gradient_render_dev(pfx_ctx* ctx, const pfx_gradient* g, const uint8_t* lut, const void* sel_dev /* may be NULL */, uint32_t w, uint32_t h,
+                            void* preview_dev, void* premul_dev /* may be NULL */);
+int pfx_gradient_render(pfx_ctx* ctx, const pfx_gradient* g, const uint8_t* lut, const uint8_t* sel /* may be NULL */, uint32_t w, uint32_t h,
+                        uint8_t* preview, uint8_t* premul /* may be NULL */);
+int pfx_gradient_commit_dev(pfx_ctx* ctx, void* active_layer_dev, const void* preview_dev, uint32_t w, uint32_t h, int is_eraser);
+int pfx_gradient_commit(pfx_ctx* ctx, uint8_t* active_layer_inout, const uint8_t* preview, uint32_t w, uint32_t h, int is_eraser);
+int pfx_gradient_apply_dev(pfx_ctx* ctx, const pfx_gradient* g, const uint8_t* lut, const void* sel_dev /* may be NULL */, void* active_layer_dev, uint32_t w,
+                           uint32_t h);
+int pfx_perspective_crop_plan(const float corners_xy[8], uint32_t w, uint32_t h, uint32_t* out_w, uint32_t* out_h);   /* host only, no context */
+int pfx_perspective_crop_dev(pfx_ctx* ctx, const float corners_xy[8], const void* const* layer_ptrs_dev, void* const* cropped_ptrs_dev, uint32_t n_layers,
+                             uint32_t w, uint32_t h);
+/* one layer through host buffers: cropped_bytes >= out_w * out_h * 4 of the plan */
+int pfx_perspective_crop(pfx_ctx* ctx, const float corners_xy[8], const uint8_t* layer, uint8_t* cropped, size_t cropped_bytes, uint32_t w, uint32_t h);
+
 #ifdef __cplusplus
 }
 #endif

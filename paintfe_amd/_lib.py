@@ -131,6 +131,15 @@ class TextBlock(C.Structure):   # pfx_text_block
                 ("canvas_w", C.c_uint32), ("canvas_h", C.c_uint32)]
 
 
+class GradientStop(C.Structure):   # pfx_gradient_stop
+    _fields_ = [("position", C.c_float), ("color", C.c_uint8 * 4)]
+
+
+class Gradient(C.Structure):   # pfx_gradient
+    _fields_ = [("start_x", C.c_float), ("start_y", C.c_float), ("end_x", C.c_float), ("end_y", C.c_float), ("shape", C.c_int32), ("repeat", C.c_int32),
+                ("mode", C.c_int32), ("preview_scale", C.c_uint32)]
+
+
 _lib = None
 
 
@@ -167,5 +176,18 @@ def load() -> C.CDLL:
     lib.pfx_text_rotate_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_float, C.POINTER(C.c_float), C.POINTER(TextWarpGeom)]
     lib.pfx_text_rotate_dev.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
     lib.pfx_text_block_place_dev.argtypes = [C.c_void_p, C.POINTER(TextBlock), C.c_void_p, C.c_void_p]
+    lib.pfx_gradient_build_lut.argtypes = [C.POINTER(GradientStop), C.c_uint32, C.c_void_p]
+    lib.pfx_gradient_preset_stops.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(GradientStop), C.POINTER(C.c_uint32)]
+    lib.pfx_gradient_bake_eraser_lut.argtypes = [C.c_void_p, C.c_void_p]
+    lib.pfx_gradient_drag_scale.restype = C.c_uint32
+    lib.pfx_gradient_drag_scale.argtypes = [C.c_uint32, C.c_uint32]
+    lib.pfx_gradient_render_dev.argtypes = [C.c_void_p, C.POINTER(Gradient), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.pfx_gradient_render.argtypes = [C.c_void_p, C.POINTER(Gradient), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.pfx_gradient_commit_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]
+    lib.pfx_gradient_commit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]
+    lib.pfx_gradient_apply_dev.argtypes = [C.c_void_p, C.POINTER(Gradient), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    lib.pfx_perspective_crop_plan.argtypes = [C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    lib.pfx_perspective_crop_dev.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_uint32]
+    lib.pfx_perspective_crop.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32]
     _lib = lib
     return lib

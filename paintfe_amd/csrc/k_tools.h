@@ -1,4 +1,4 @@
-// k_tools.h — what the tool kernels share: k_shapes, k_inpaint, k_flood, k_select, k_colorkey, k_overlay, k_textfx and k_textwarp include it, no other file does
+// k_tools.h — what the tool kernels share: k_shapes, k_inpaint, k_flood, k_select, k_colorkey, k_overlay, k_textfx, k_textwarp and k_gradient include it, no other file does
 // (the effect bank, the Gaussians and the compositor keep compiling from k_common.h alone).  A new tool kernel starts from here.
 //
 //   launch     stream_blocks / aligned_to / launch_stream for a streaming kernel, tile_grid for one workgroup per tile, dims_ok.
@@ -8,7 +8,8 @@
 // Deliberately NOT here, so that nobody folds them:
 //   the float-to-integer casts (as_u32, cast_u32, as_index, cvt_u32_sat, as_i32, round_u32): each restates a different Rust cast over a different domain — NaN or
 //       not, negative or not, saturating where — and cvt_u32_sat is a single instruction on purpose;
-//   the bilinear samplers: k_textwarp.hip's header says why its sampler shares nothing with k_overlay.hip's, k_warp.hip's or k_resize.hip's;
+//   the bilinear samplers: k_textwarp.hip's header says why its sampler shares nothing with k_overlay.hip's, k_warp.hip's or k_resize.hip's; k_gradient.hip's crop
+//       sampler rounds its horizontal lerps to u8 before the vertical one and takes its fraction from the unclamped coordinate;
 //   the two block_scan's (k_select.hip, k_inpaint.hip): they differ in direction and operator;
 //   the host side's pfx_dims_ok (pfx_internal.h): the entry points' check, which no kernel file includes.
 #pragma once

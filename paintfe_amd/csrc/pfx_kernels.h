@@ -485,6 +485,26 @@ hipError_t pfxk_textwarp_rotate(hipStream_t s, const uint8_t* d_src, uint8_t* d_
 // blit_rgba_buffer: the bw x bh buffer at (off_x, off_y) on the cw x ch canvas; alpha 0 keeps the canvas pixel, any other pixel replaces it
 hipError_t pfxk_textwarp_blit(hipStream_t s, const uint8_t* d_buf, uint32_t bw, uint32_t bh, int64_t off_x, int64_t off_y, uint8_t* d_canvas, uint32_t cw, uint32_t ch);
 
+// ---- k_gradient.hip ---- the gradient tool and the perspective crop (src/ui/panels/tools/behavior/raster/perspective_gradient.rs, gradient_text/
+// gradient_controls.rs:63-122); host side: pfx_gradient.cpp
+// What render_gradient_to_preview's CPU path hoists out of its loops :415-430, derived on the host through the reference's own f32 expressions
+typedef struct pfxk_gradient {
+    float ax, ay, dx, dy;                  // the drag's start; end - start
+    float inv_len, inv_len_sq, ux, uy;     // len > 1e-6 ? 1 / len : 0, likewise on len_sq; dx * inv_len, dy * inv_len
+    float scale_f;                         // preview_scale as f32
+    uint32_t scale, gen_w, gen_h, w;       // preview_scale; the generated size div_ceil(w, scale) x div_ceil(h, scale); the selection's row pitch
+    int32_t shape, repeat, eraser;         // PFX_GRADIENT_*; 0 / 1; transparency mode
+} pfxk_gradient;
+// d_lut: 256 packed RGBA8 entries, already baked in transparency mode.  Every pixel of d_preview (and of d_premul, when given) is written
+hipError_t pfxk_gradient_render(hipStream_t s, const uint32_t* d_lut, const uint8_t* d_sel, uint8_t* d_preview, uint8_t* d_premul, const pfxk_gradient* P);
+// commit_gradient over n pixels, the layer in place
+hipError_t pfxk_gradient_commit(hipStream_t s, uint8_t* d_layer, const uint8_t* d_preview, size_t n, int is_eraser);
+// render at scale 1 and commit in one pass over the layer (P->scale == 1, P->gen_w x P->gen_h the layer's size)
+hipError_t pfxk_gradient_apply(hipStream_t s, const uint32_t* d_lut, const uint8_t* d_sel, uint8_t* d_layer, const pfxk_gradient* P);
+// apply_perspective_crop's loop :150-165 for n_layers images of w x h into as many of out_w x out_h through one map; the pointer arrays live on the device
+typedef struct pfxk_crop { float cx[4], cy[4]; uint32_t w, h, out_w, out_h, n_layers; } pfxk_crop;   // corners TL, TR, BR, BL
+hipError_t pfxk_perspective_crop(hipStream_t s, const uint8_t* const* d_layers, uint8_t* const* d_outs, const pfxk_crop* P);
+
 #ifdef __cplusplus
 }
 #endif

@@ -200,6 +200,73 @@ def overlay_geometry(ov: _lib.Overlay) -> _lib.OverlayGeom:
     return g
 
 
+GRADIENT_SHAPES = ["linear", "linear_reflected", "radial", "diamond"]                        # GradientShape, PFX_GRADIENT_*
+GRADIENT_MODES = ["color", "transparency"]                                                   # GradientMode
+GRADIENT_PRESETS = ["primary_secondary", "black_white", "foreground_transparent", "rainbow"]  # GradientPreset, less Custom
+
+
+def gradient(start, end, shape="linear", repeat: bool = False, mode="color", preview_scale: int = 1) -> _lib.Gradient:
+    """a pfx_gradient: the drag's start and end in canvas coordinates, (x, y) each, and the tool's settings"""
+    sh = GRADIENT_SHAPES.index(shape) if isinstance(shape, str) else int(shape)
+    md = GRADIENT_MODES.index(mode) if isinstance(mode, str) else int(mode)
+    return _lib.Gradient(float(start[0]), float(start[1]), float(end[0]), float(end[1]), sh, int(bool(repeat)), md, int(preview_scale))
+
+
+def _stop_array(stops):
+    rows = [(float(p), _c4(c)) for p, c in stops]
+    return (_lib.GradientStop * max(len(rows), 1))(*[_lib.GradientStop(p, c) for p, c in rows]), len(rows)
+
+
+def gradient_lut(stops) -> np.ndarray:
+    """pfx_gradient_build_lut (rebuild_lut): the (256, 4) RGBA8 table of stops = [(position, (r, g, b, a)), ...]; host only"""
+    arr, n = _stop_array(stops)
+    lut = np.zeros((256, 4), np.uint8)
+    st = _lib.load().pfx_gradient_build_lut(arr, C.c_uint32(n), _p(lut))
+    if st != _lib.OK:
+        raise PfxError(st, "pfx_gradient_build_lut refused the stops")
+    return lut
+
+
+def gradient_preset_stops(preset, primary, secondary):
+    """pfx_gradient_preset_stops (apply_preset): [(position, (r, g, b, a)), ...] of one of GRADIENT_PRESETS; host only"""
+    out, n = (_lib.GradientStop * 7)(), C.c_uint32(0)
+    st = _lib.load().pfx_gradient_preset_stops(_enum(GRADIENT_PRESETS, preset), _c4(primary), _c4(secondary), out, C.byref(n))
+    if st != _lib.OK:
+        raise PfxError(st, "pfx_gradient_preset_stops: unknown preset")
+    return [(float(out[i].position), tuple(int(v) for v in out[i].color)) for i in range(n.value)]
+
+
+def gradient_bake_eraser_lut(lut) -> np.ndarray:
+    """pfx_gradient_bake_eraser_lut: the transparency mode's table (rgb 255, alpha = luminance * alpha / 255) of a raw (256, 4) table; host only"""
+    raw = _u8(lut).reshape(256, 4)
+    baked = np.zeros_like(raw)
+    st = _lib.load().pfx_gradient_bake_eraser_lut(_p(raw), _p(baked))
+    if st != _lib.OK:
+        raise PfxError(st, "pfx_gradient_bake_eraser_lut refused its arguments")
+    return baked
+
+
+def gradient_drag_scale(w: int, h: int) -> int:
+    """pfx_gradient_drag_scale: the reference's preview scale while dragging on a w x h canvas; host only"""
+    return int(_lib.load().pfx_gradient_drag_scale(C.c_uint32(w), C.c_uint32(h)))
+
+
+def _corners(corners):
+    flat = [float(v) for c in corners for v in c]
+    if len(flat) != 8:
+        raise ValueError("corners are four (x, y) pairs: TL, TR, BR, BL")
+    return (C.c_float * 8)(*flat)
+
+
+def perspective_crop_plan(corners, w: int, h: int):
+    """pfx_perspective_crop_plan: (out_w, out_h) of the crop of a w x h canvas through corners = [TL, TR, BR, BL], or None where the reference returns None; host only"""
+    ow, oh = C.c_uint32(0), C.c_uint32(0)
+    st = _lib.load().pfx_perspective_crop_plan(_corners(corners), C.c_uint32(w), C.c_uint32(h), C.byref(ow), C.byref(oh))
+    if st != _lib.OK:
+        raise PfxError(st, "pfx_perspective_crop_plan refused its arguments")
+    return (ow.value, oh.value) if ow.value else None
+
+
 OUTLINE_POSITIONS = ["inside", "outside", "center"]                     # OutlinePosition, PFX_TEXT_OUTLINE_*
 TEXT_FX_OUTLINE, TEXT_FX_SHADOW, TEXT_FX_INNER_SHADOW, TEXT_FX_GRADIENT_FILL, TEXT_FX_TEXTURE_FILL = 1, 2, 4, 8, 16
 TEXT_FX_MAX_RADIUS = 64
@@ -1052,6 +1119,56 @@ class GpuRenderer:
         (pfx_int_textfx_disc_dev; for tests); asynchronous"""
         self._check(self._lib.pfx_int_textfx_disc_dev(self._h, C.c_void_p(src_ptr or None), C.c_void_p(dst_ptr or None), C.c_uint32(w), C.c_uint32(h),
                                                       C.c_float(radius), C.c_int(int(take_min))))
+
+    # ---- the gradient tool and the perspective crop (pfx_gradient_*, pfx_perspective_crop*): `g` is a `gradient(...)` descriptor, `lut` a raw (256, 4) table ----
+    def gradient_render(self, g, lut, w: int, h: int, selection=None, premultiplied: bool = False):
+        """render_gradient_to_preview's CPU path: the (gen_h, gen_w, 4) preview of a w x h canvas, gen = ceil(dim / g.preview_scale); with premultiplied=True
+        also preview_flat_buffer, as a second array"""
+        table = _u8(lut).reshape(256, 4)
+        sel = None if selection is None else _u8(selection)
+        shape = (-(-h // max(g.preview_scale, 1)), -(-w // max(g.preview_scale, 1)), 4)
+        out = np.empty(shape, np.uint8)
+        pm = np.empty(shape, np.uint8) if premultiplied else None
+        self._check(self._lib.pfx_gradient_render(self._h, C.byref(g), _p(table), _p(sel), C.c_uint32(w), C.c_uint32(h), _p(out), _p(pm)))
+        return (out, pm) if premultiplied else out
+
+    def gradient_render_dev(self, g, lut, w: int, h: int, preview_ptr: int, selection_ptr: int = 0, premul_ptr: int = 0):
+        """the same between device buffers (selection w * h bytes; preview and premultiplied copy gen_w * gen_h RGBA8); asynchronous"""
+        table = _u8(lut).reshape(256, 4)
+        self._check(self._lib.pfx_gradient_render_dev(self._h, C.byref(g), _p(table), C.c_void_p(selection_ptr or None), C.c_uint32(w), C.c_uint32(h),
+                                                      C.c_void_p(preview_ptr), C.c_void_p(premul_ptr or None)))
+
+    def gradient_commit(self, layer, preview, is_eraser: bool = False) -> np.ndarray:
+        """commit_gradient: the layer with the full-resolution preview committed onto it"""
+        out, pv = _u8(layer).copy(), _u8(preview)
+        h, w = out.shape[:2]
+        self._check(self._lib.pfx_gradient_commit(self._h, _p(out), _p(pv), C.c_uint32(w), C.c_uint32(h), C.c_int(int(is_eraser))))
+        return out
+
+    def gradient_commit_dev(self, layer_ptr: int, preview_ptr: int, w: int, h: int, is_eraser: bool = False):
+        """commit_gradient on a device layer in place; asynchronous"""
+        self._check(self._lib.pfx_gradient_commit_dev(self._h, C.c_void_p(layer_ptr), C.c_void_p(preview_ptr), C.c_uint32(w), C.c_uint32(h), C.c_int(int(is_eraser))))
+
+    def gradient_apply_dev(self, g, lut, layer_ptr: int, w: int, h: int, selection_ptr: int = 0):
+        """the mouse release in one kernel: render at scale 1 and commit onto the device layer in place (g.mode says which commit); asynchronous"""
+        table = _u8(lut).reshape(256, 4)
+        self._check(self._lib.pfx_gradient_apply_dev(self._h, C.byref(g), _p(table), C.c_void_p(selection_ptr or None), C.c_void_p(layer_ptr), C.c_uint32(w), C.c_uint32(h)))
+
+    def perspective_crop(self, corners, layer) -> np.ndarray:
+        """apply_perspective_crop on one layer (h, w, 4) through corners = [TL, TR, BR, BL]; PfxError where the reference returns None"""
+        src = _u8(layer)
+        h, w = src.shape[:2]
+        plan = perspective_crop_plan(corners, w, h) or (0, 0)
+        out = np.empty((plan[1], plan[0], 4), np.uint8)
+        self._check(self._lib.pfx_perspective_crop(self._h, _corners(corners), _p(src), _p(out), C.c_size_t(out.nbytes), C.c_uint32(w), C.c_uint32(h)))
+        return out
+
+    def perspective_crop_dev(self, corners, layer_ptrs, cropped_ptrs, w: int, h: int):
+        """every layer of a w x h document through the same quad in one launch: device pointers in, device pointers (out_w * out_h RGBA8 of the plan) out"""
+        n = len(layer_ptrs)
+        ins = (C.c_void_p * max(n, 1))(*[int(p) for p in layer_ptrs])
+        outs = (C.c_void_p * max(n, 1))(*[int(p) for p in cropped_ptrs])
+        self._check(self._lib.pfx_perspective_crop_dev(self._h, _corners(corners), ins, outs, C.c_uint32(n), C.c_uint32(w), C.c_uint32(h)))
 
     # ------------------------------------------------------------------ script front-end
     def resize_image(self, img, new_w: int, new_h: int, filter="bilinear"):   # transform.rs:347 (imageops::resize)

@@ -342,6 +342,59 @@ def main() -> int:
     timed("text place: an 8K raster rotated 0.3 into the 8K canvas", place_timers, lambda: r.text_block_place_dev(blk_full, s, canvas2.data_ptr()), px, 12,
           "rotate (4 + 4 B per rotated pixel) and blit (4 read, 4 written where alpha > 0); Mpx_s per canvas pixel")
     del canvas2
+    # ---------------- the gradient tool and the perspective crop (k_gradient.hip), 8K, device-resident.  The render only writes (4 B/px; 5 with a selection), so a
+    # memset of one frame runs beside it; commit and the fused apply read and write the layer (12 and 8 B/px) beside invert (8 B/px); the crop is a four-tap
+    # gather and one write per layer beside the bilinear affine transform.  No time here is an acceptance criterion (profiles/gradient.md)
+    if not args.only or "gradient" in args.only:
+        import ctypes as C
+
+        from paintfe_amd import gradient, gradient_drag_scale, gradient_lut, perspective_crop_plan
+        g_lut = gradient_lut([(0.0, (255, 0, 0, 255)), (0.3, (0, 255, 0, 0)), (0.35, (0, 0, 255, 0)), (0.7, (10, 20, 200, 128)), (1.0, (255, 255, 255, 255))])
+        g_ends = ((w * 0.31 + 0.3, h * 0.24 + 0.2), (w * 0.52 + 0.7, h * 0.71 + 0.4))
+        pm = torch.empty_like(src)
+        for shape in ("linear", "linear_reflected", "radial", "diamond"):
+            gd = gradient(*g_ends, shape=shape, repeat=True)
+            timed(f"gradient: render, {shape}, repeat, full resolution", ["gradient_render"], lambda: r.gradient_render_dev(gd, g_lut, w, h, d), px, 4, "write only: one 16-byte store per lane")
+        gd = gradient(*g_ends, shape="linear", repeat=True)
+        timed("gradient: render, linear, with a 70 % selection", ["gradient_render"], lambda: r.gradient_render_dev(gd, g_lut, w, h, d, selection_ptr=m), px, 5)
+        timed("gradient: render, linear, with the premultiplied copy", ["gradient_render"], lambda: r.gradient_render_dev(gd, g_lut, w, h, d, premul_ptr=pm.data_ptr()), px, 8,
+              "the fast path's preview_flat_buffer: a second 16-byte store")
+        drag = gradient_drag_scale(w, h)
+        gdrag = gradient(*g_ends, shape="linear", repeat=True, preview_scale=drag)
+        gen_px = -(-w // drag) * -(-h // drag)
+        timed(f"gradient: render at the drag scale {drag} ({-(-w // drag)} x {-(-h // drag)})", ["gradient_render"], lambda: r.gradient_render_dev(gdrag, g_lut, w, h, d), gen_px, 4,
+              "what a drag frame costs; Mpx_s per generated pixel")
+        r.gradient_render_dev(gd, g_lut, w, h, pm.data_ptr())
+        timed("gradient: commit, colour mode", ["gradient_commit"], lambda: r.gradient_commit_dev(d, pm.data_ptr(), w, h, False), px, 12,
+              "4 preview + 4 layer read, 4 written; the layer converges over the repetitions (it is committed onto again)")
+        timed("gradient: commit, transparency mode", ["gradient_commit"], lambda: r.gradient_commit_dev(d, pm.data_ptr(), w, h, True), px, 12)
+        timed("gradient: fused apply (render + commit), colour mode", ["gradient_apply"], lambda: r.gradient_apply_dev(gd, g_lut, d, w, h), px, 8, "4 read + 4 written, no preview buffer")
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        memset = lambda: r._lib.pfx_dev_memset(r.handle, C.c_void_p(d), C.c_int(0), C.c_size_t(px * 4))
+        for _ in range(20):
+            memset()
+        ev0.record()
+        for _ in range(args.reps):
+            memset()
+        ev1.record()
+        torch.cuda.synchronize()
+        ms = ev0.elapsed_time(ev1) / args.reps
+        rows.append({"op": "gradient orientation: pfx_dev_memset of one 8K frame", "ms": round(ms, 4), "Mpx_s": round(px / ms / 1e3, 1), "alg_bytes_px": 4,
+                     "achieved_GBs": round(4 * px / (ms * 1e-3) / 1e9, 1), "hbm_frac": round(4 * px / (ms * 1e-3) / 1e9 / HBM_PEAK, 4),
+                     "note": "the write-only yardstick; stream events around the calls (the memset has no pfx_timing scope)"})
+        print(rows[-1], flush=True)
+        timed("gradient orientation: invert", ["adjust"], lambda: r.adjust_dev(s, d, w, h, "invert", []), px, 8, "the 8 B/px yardstick for commit and apply")
+        quad = [(w * 0.08 + 0.3, h * 0.08), (w * 0.9 + 0.2, h * 0.18), (w * 0.87 + 0.1, h * 0.92), (w * 0.11 + 0.7, h * 0.84)]
+        cw, ch = perspective_crop_plan(quad, w, h)
+        crop_in = [src] + [torch.randint(0, 256, (h, w, 4), dtype=torch.uint8, device=dev, generator=g) for _ in range(3)]
+        crop_out = [torch.empty((ch, cw, 4), dtype=torch.uint8, device=dev) for _ in range(4)]
+        for n in (1, 4):
+            ins, outs = [t_.data_ptr() for t_ in crop_in[:n]], [t_.data_ptr() for t_ in crop_out[:n]]
+            timed(f"gradient: perspective crop of {n} layer{'s' if n > 1 else ''}, 8K -> {cw} x {ch}", ["perspective_crop"], lambda: r.perspective_crop_dev(quad, ins, outs, w, h),
+                  cw * ch * n, 8, "4 gathered + 4 written per layer and output pixel; Mpx_s counts every layer's pixels")
+        timed("gradient orientation: affine transform, bilinear, rotation_z 0.3 rad, 8K", ["affine"],
+              lambda: r.affine_transform_dev(s, w, h, d, w, h, rotation_z=math.degrees(0.3)), px, 8, "the four-tap yardstick for the crop")
+        del pm, crop_in, crop_out
     src_h = src.cpu().numpy()
     import time
     r.execute_script_sync("map_channels(|r, g, b, a| [255 - r, g / 2, (b * 3 + a) / 4, a]);", src_h)   # warm: a process's first launch of k_script's code object loads it (~1 ms)

@@ -1623,10 +1623,11 @@ extern "C" hipError_t pfxk_brush_commit(hipStream_t s, uint8_t* d_layer, const u
 extern "C" hipError_t pfxk_flatten(hipStream_t stream, const pfxk_layer_desc* d_layers, uint32_t n_layers,
                                    const float* d_adj_table, int general, int fast_div, uint8_t* d_chunk_active,
                                    int chunk_active_ready, uint32_t w, uint32_t h, uint8_t* d_dst, const pfxk_preview* preview, const pfxk_region* region,
-                                   const pfxk_dle_cands* cands, const uint8_t* d_chunk_start, int typed_store_ok, int mode_class)
+                                   const pfxk_dle_cands* cands, const uint8_t* d_chunk_start, int typed_store_ok, int mode_class, int* path_out)
 {
     size_t n_quads = ((size_t)w * h + 3) / 4;
     if (n_quads == 0) return hipSuccess;
+    auto report = [&](int path) { if (path_out) *path_out = path; };
     pfxk_preview PV{};
     if (preview && preview->pixels) { PV = *preview; general = 1; }
     pfxk_region RG{};
@@ -1708,6 +1709,7 @@ extern "C" hipError_t pfxk_flatten(hipStream_t stream, const pfxk_layer_desc* d_
                 else if (dle_cfg == 1) flatten_srt_kernel<2> PFX_ARGS;
                 else flatten_srt_kernel<3> PFX_ARGS;
 #undef PFX_ARGS
+                report(PFXK_FLATTEN_SRT | PFXK_FLATTEN_FAST_DIV);
                 return hipGetLastError();
             }
             // one wave per workgroup: a wave's stream is independent of its neighbours' (no barrier, private LDS slice), and a 4-wave
@@ -1717,6 +1719,7 @@ extern "C" hipError_t pfxk_flatten(hipStream_t stream, const pfxk_layer_desc* d_
             else if (dle_cfg == 1) flatten_dle_kernel<2, 9, 1, 3> PFX_ARGS;
             else flatten_dle_kernel<3, 10, 1, 2> PFX_ARGS;
 #undef PFX_ARGS
+            report(PFXK_FLATTEN_DLE | PFXK_FLATTEN_FAST_DIV);
             return hipGetLastError();
         }
         switch (variant) {
@@ -1730,6 +1733,7 @@ extern "C" hipError_t pfxk_flatten(hipStream_t stream, const pfxk_layer_desc* d_
         default: PFX_STREAM(3, 3, 1); break;
 #undef PFX_STREAM
         }
+        report(PFXK_FLATTEN_STREAM | PFXK_FLATTEN_FAST_DIV | (d_chunk_start ? PFXK_FLATTEN_CHUNK_START : 0));
         return hipGetLastError();
     }
     size_t blocks = (n_quads + block - 1) / block;
@@ -1739,5 +1743,7 @@ extern "C" hipError_t pfxk_flatten(hipStream_t stream, const pfxk_layer_desc* d_
     if (general) { if (fast_div) PFX_LAUNCH(true, true); else PFX_LAUNCH(true, false); }
     else         { if (fast_div) PFX_LAUNCH(false, true); else PFX_LAUNCH(false, false); }
 #undef PFX_LAUNCH
+    report(PFXK_FLATTEN_TEMPLATE | (general ? PFXK_FLATTEN_GENERAL : 0) | (fast_div ? PFXK_FLATTEN_FAST_DIV : 0) | (RG.rw ? PFXK_FLATTEN_REGION : 0) |
+           (PV.pixels ? PFXK_FLATTEN_PREVIEW : 0));
     return hipGetLastError();
 }

@@ -359,7 +359,7 @@ int flatten_common(pfx_ctx* ctx, const void* const* layer_ptrs, const void* cons
         pfx_timer t(ctx, "flatten");
         PFX_HIP(ctx, pfxk_flatten(ctx->stream, (const pfxk_layer_desc*)ctx->d_desc.p, n_desc, (const float*)ctx->d_adj.p,
                                   general ? 1 : 0, fast_div ? 1 : 0, d_chunks, chunks_ready ? 1 : 0, w, h, (uint8_t*)dst_dev, PV.pixels ? &PV : nullptr, region, &cands, d_chunk_start,
-                                  parking_ok, ctx->stack_mode_class));
+                                  parking_ok, ctx->stack_mode_class, &ctx->last_flatten_path));
     }
     if (probe_now) {   // behind the composite (it may have been in place: the probe reads layers, and a layer that was the destination now holds the result — a hint all the same)
         if (!ctx->h_dle_verdict) {
@@ -433,6 +433,8 @@ int pfx_int_flatten_with_chunk_keys_dev(pfx_ctx* ctx, const void* const* layer_p
     PFX_TRY(pfx_use(ctx));
     return flatten_common(ctx, layer_ptrs_dev, nullptr, layers, n_layers, w, h, false, dst_dev, nullptr, nullptr, chunk_keys_host);
 }
+
+int pfx_int_flatten_last_path(pfx_ctx* ctx) { return !ctx ? -1 : ctx->last_flatten_path; }
 
 int pfx_gaussian_blur_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, float sigma, void* tmp_dev)
 {

@@ -49,6 +49,7 @@ struct pfx_ctx {
     int median_bits_min = 3;   // pfx_tune "median_bits_min", the one per-context knob of pfx_stencil.cpp (see pfx_int_median_path there)
     int last_median_path = -1, last_box_plan = -1;   // what pfx_stencil_median / _box last launched; pfx_int_stencil_last_path reads them, nothing else does
     int last_resize_path = -1, last_resize_span = -1;   // what pfx_resize_image_dev last launched; pfx_int_resize_last reads them, nothing else does
+    int last_flatten_path = -1;                         // what pfxk_flatten last launched for this context; pfx_int_flatten_last_path reads it, nothing else does
     int last_brush_path = -1;                           // what pfx_brush_stamps_ex_dev last did; pfx_int_brush_last reads it, nothing else does
     pfx_devbuf fx_a, fx_b; // effect-bank scratch (crystallize cell table, drop-shadow planes)
     // small parameter buffers
@@ -194,6 +195,10 @@ struct pfx_timer {
 // flatten of device-resident flat layers + the union of the visible layers' TiledImage chunk keys (pfx_api.cpp)
 extern "C" int pfx_int_flatten_with_chunk_keys_dev(pfx_ctx* ctx, const void* const* layer_ptrs_dev, const pfx_layer_info* layers, uint32_t n_layers,
                                                    uint32_t w, uint32_t h, void* dst_dev, const uint8_t* chunk_keys_host);
+// for the tests, what the context's last composite launched (every pfx_composite* / pfx_flatten*_dev entry point ends in pfxk_flatten): a PFXK_FLATTEN_* kernel
+// (0 the flatten_kernel<GENERAL, F> template, 1 streaming, 2 elimination, 3 class-sorting) | GENERAL << 4 | fast_div << 5 | region << 6 | preview << 7 |
+// chunk-start table used << 8 (pfx_kernels.h); -1 = none yet (not in include/pfx.h)
+extern "C" int pfx_int_flatten_last_path(pfx_ctx* ctx);
 
 // ---- the Gaussian's host side (pfx_gauss.cpp): the tap-table caches, the one decision which kernel runs, the launches ----
 enum { PFX_GAUSS_PLAIN = 0, PFX_GAUSS_SHARPEN = 1, PFX_GAUSS_GLOW = 2, PFX_GAUSS_CHAIN = 3, PFX_GAUSS_PLANE = 4 };   // what rides in the Gaussian's store

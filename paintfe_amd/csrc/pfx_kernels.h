@@ -58,7 +58,12 @@ hipError_t pfxk_flatten(hipStream_t stream, const pfxk_layer_desc* d_layers, uin
                         const uint8_t* d_chunk_start /* may be NULL: per-chunk first layer that can show (pfxk_chunk_start) */,
                         int typed_store_ok /* the device's float -> UNORM8 typed-store conversion is verified (pfxk_unorm_store_check): the class-sorting
                                               kernel may write its result that way (k_flatten.hip: flatten_srt_kernel) */,
-                        int mode_class /* arithmetic weight of the stack's blend modes: 0 heavy (or unknown), 1 medium, 2 light: picks the streaming kernel's shape */);
+                        int mode_class /* arithmetic weight of the stack's blend modes: 0 heavy (or unknown), 1 medium, 2 light: picks the streaming kernel's shape */,
+                        int* path_out /* may be NULL: what was launched, PFXK_FLATTEN_* kernel | flag bits (the tests' seam, pfx_int_flatten_last_path) */);
+// *path_out of pfxk_flatten: the kernel in the low four bits, then the template kernel's GENERAL and F arguments (the streaming and elimination kernels
+// always run under the fast-division precondition, without GENERAL), a dirty rectangle, a tool preview, the per-chunk start table
+enum { PFXK_FLATTEN_TEMPLATE = 0, PFXK_FLATTEN_STREAM = 1, PFXK_FLATTEN_DLE = 2, PFXK_FLATTEN_SRT = 3,
+       PFXK_FLATTEN_GENERAL = 1 << 4, PFXK_FLATTEN_FAST_DIV = 1 << 5, PFXK_FLATTEN_REGION = 1 << 6, PFXK_FLATTEN_PREVIEW = 1 << 7, PFXK_FLATTEN_CHUNK_START = 1 << 8 };
 // per-chunk alpha summary of a stored layer (bit 0: all 255, bit 1: none 0) over the chunk rectangle [cx0, cx0+ncx) x [cy0, cy0+ncy), and the
 // per-chunk start table of a stack (want[k]: 1 = Normal at opacity >= 1 needs bit 0, 2 = Overwrite needs bit 1, 0 = layer k never resets)
 hipError_t pfxk_chunk_alpha_flags(hipStream_t s, const uint8_t* d_px, uint32_t w, uint32_t h, uint32_t cx0, uint32_t cy0, uint32_t ncx, uint32_t ncy,

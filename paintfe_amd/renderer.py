@@ -1304,6 +1304,19 @@ class GpuRenderer:
         self._check(self._lib.pfx_flatten_dev(self._h, lp, mp, arr, C.c_uint32(n), C.c_uint32(w), C.c_uint32(h),
                                               C.c_void_p(dst_ptr)))
 
+    def flatten_preview_dev(self, layer_ptrs: Sequence[int], layer_info: Iterable, w: int, h: int, dst_ptr: int, preview_ptr: int, active_layer: int,
+                            blend_mode: int = 0, is_eraser: bool = False, replaces_layer: bool = False, chunk_present_ptr: int = 0, mask_ptrs=None):
+        """flatten_dev with the tool preview (a w x h RGBA image on the device) folded into layer_info[active_layer]; chunk_present_ptr: one byte per
+        64 x 64 chunk on the device, 0 = derive it from the preview's alpha (pfx_flatten_preview_dev; ref: canvas_state.rs:541-548, 593-658)"""
+        arr, n = self._infos(layer_info)
+        lp = (C.c_void_p * max(n, 1))(*[C.c_void_p(p) for p in layer_ptrs])
+        mp = None
+        if mask_ptrs is not None:
+            mp = (C.c_void_p * max(n, 1))(*[C.c_void_p(p or 0) for p in mask_ptrs])
+        pv = _lib.Preview(active_layer, blend_mode, int(is_eraser), int(replaces_layer), 0)
+        self._check(self._lib.pfx_flatten_preview_dev(self._h, lp, mp, arr, C.c_uint32(n), C.c_uint32(w), C.c_uint32(h), C.c_void_p(preview_ptr or None),
+                                                      C.c_void_p(chunk_present_ptr or None), C.byref(pv), C.c_void_p(dst_ptr)))
+
     def gaussian_blur_dev(self, src_ptr: int, dst_ptr: int, w: int, h: int, sigma: float, tmp_ptr: int = 0, first_row: int = 0):
         """first_row: index of the buffer's row 0 in the whole image when the buffer is a band of it (pfx_gaussian_blur_band_dev)"""
         self._check(self._lib.pfx_gaussian_blur_band_dev(self._h, C.c_void_p(src_ptr), C.c_void_p(dst_ptr), C.c_uint32(w),

@@ -16,7 +16,6 @@
 //   * the three `/ out_a` of a pixel share one refined reciprocal (rdiv below): the exact operation sequence
 //     hipcc emits for an IEEE f32 divide, with the per-denominator part hoisted — bit-identical to `/`.
 #include <algorithm>
-#include <atomic>
 #include <type_traits>
 #include "k_common.h"
 #include "pfx_kernels.h"
@@ -390,7 +389,7 @@ __device__ unsigned long long g_dle_stats[16];
 #ifndef PFX_DLE_SGPR_ATTR
 #define PFX_DLE_SGPR_ATTR
 #endif
-struct dle_sched { uint32_t wavesA, UA, wavesB, UB, UC; }; // waves [0, wavesA) own UA units each, the next wavesB UB, the rest UC
+struct dle_sched : pfxk_dle_sched {};   // the fields: pfx_kernels.h; the name here keeps the kernels' symbols
 
 template <int PX, int NB, int AUX = 0>
 PFX_DEV void dle_layers(float (&acc)[PX][4], const pfxk_layer_desc* __restrict__ layers, uint32_t lb, uint32_t le, uint32_t bytes,
@@ -665,7 +664,7 @@ PFX_DEV void stream_layer_groups(float (&acc)[PX][4], const float (&t)[PX][4], u
 // pixels to the lanes when that completes another wave-uniform opaque group.  A re-deal moves the accumulators, the pixel offsets and the one layer
 // that is already in flight (requested with the old offsets) through the LDS tile; the next request uses the new offsets.
 // Scalar work per layer is kept short — the CU's one scalar unit serves all 24 waves, and round 4's counters show it more than half busy: the descriptor
-// pointer advances instead of being indexed, nothing clamps it (the host appends PFXK_DESC_PAD copies of the last descriptor: pfx_api.cpp:build_stack; a pass reads up to descriptor le + 2; what is
+// pointer advances instead of being indexed, nothing clamps it (the host appends PFXK_DESC_PAD copies of the last descriptor: pfx_flatten.cpp:build_stack; a pass reads up to descriptor le + 2; what is
 // fetched through them or beyond `le` is never blended), the whole 32-byte descriptor comes with one scalar load, the resource needs no mask.
 // Since round 7 this loop and srt_early serve only the PFX_SRT_PIPE 0 and TR builds: the shipped path is srt_layers_pipe / srt_early_pipe below,
 // which request nothing past le - 1 and read no descriptor past `le`.
@@ -1084,7 +1083,7 @@ PFX_DEV void srt_early_pipe(float (&acc)[PX][4], float (&tn)[2][PX][4], const pf
 // actual accumulators.  The unit goes back to lane order and leaves as four v_cvt_pk_u8_f32 and a dword store per pixel (the typed format
 // store, float -> UNORM8 in the texture path, measured 1 % slower: PFX_SRT_TYPED_STORE; the context's one-time check of the texture path's conversions,
 // pfxk_unorm_store_check, still gates this kernel — it reads every layer through the same conversions).
-struct dle_plan { uint32_t s1, seg; }; // re-deal attempts in front of layers s1, s1 + seg, s1 + 2 seg, ... (seg == 0: none)
+struct dle_plan : pfxk_dle_plan {};
 
 // 63 VGPRs and no spills once the uniform regions are left unstructurized (Makefile: FLAGS_k_flatten): the eighth wave per SIMD
 #ifndef PFX_SRT_PRIO
@@ -1325,7 +1324,7 @@ __global__ __launch_bounds__(64) PFX_SRT_ATTR void flatten_srt_kernel(const pfxk
 // Does dead-layer elimination pay on this stack?  (Stacks below the depth threshold: the class-sorting kernel wins where reset layers are spatially coherent — an
 // opaque photo layer covers whole units, which then start at that layer and read nothing below — and loses on per-pixel-random alpha, where every unit is split.)
 // One workgroup samples 256 units spread over the image against the topmost candidate and writes its verdict to pinned host memory, where a LATER composite of
-// the same stack reads it (pfx_api.cpp: flatten_common; the decision is a performance hint, every kernel is bit-exact).
+// the same stack reads it (pfx_flatten.cpp: flatten_common; the decision is a performance hint, every kernel is bit-exact).
 __global__ __launch_bounds__(1024) void dle_probe_kernel(const pfxk_layer_desc* __restrict__ layers, uint32_t cand_layer, uint32_t cand_kind, uint32_t n_px,
                                                          uint32_t* __restrict__ verdict_pinned, uint32_t tag)
 {
@@ -1372,14 +1371,6 @@ __global__ __launch_bounds__(256) void unorm_store_check_kernel(uint8_t* __restr
                     __builtin_bit_cast(uint32_t, b.z) == __builtin_bit_cast(uint32_t, v.z) && __builtin_bit_cast(uint32_t, b.w) == __builtin_bit_cast(uint32_t, v.w);
     if (!ok) atomicAdd(out, 1ull);
 }
-
-// Development knobs (pfx_tune): PROCESS-WIDE on purpose — they select among bit-identical kernel shapes for A/B runs and tests, not
-// per-document behaviour; atomics because batch workers and device groups run one context per thread.
-std::atomic<int> g_dle_stats_on{0}, g_dle_cfg{0}, g_dle_sched{1}, g_dle_fracA{75}, g_dle_fracB{20};
-std::atomic<int> g_dle_units{0}; // units per wave (0 = default)
-std::atomic<int> g_dle_kernel{0}; // 0 = class sorting inside a unit (flatten_srt_kernel), 1 = round 3's flatten_dle_kernel
-std::atomic<int> g_dle_s1{-1}, g_dle_s2{-1}; // re-deal plan: first attempt this many layers above the topmost candidate (-1: 1; 0: never), then every g_dle_s2 layers (-1: 3)
-std::atomic<int> g_flatten_variant{0}; // tuning knob (pfxk_flatten_set_variant): 0 = shipped (2 px x 2 sets, grid stride up to 16 layers), 1-5 = PX / register-set variants, 6 = 3 px x 3 sets (the round-2 shape), +10 = grid-stride launch, 8 = no elimination kernel, 9 = the general kernel
 
 // per 64 x 64 chunk of a layer: bit 0 = every alpha is 255, bit 1 = no alpha is 0 (computed when a layer enters the layer store)
 __global__ __launch_bounds__(256) void chunk_alpha_flags_kernel(const uint8_t* __restrict__ px, uint32_t w, uint32_t h, uint32_t cx0, uint32_t cy0,
@@ -1523,7 +1514,6 @@ __global__ __launch_bounds__(256) void round_pack_check_kernel(unsigned long lon
 
 } // namespace
 
-extern "C" void pfxk_flatten_set_variant(int v) { g_flatten_variant = v; }
 extern "C" hipError_t pfxk_chunk_alpha_flags(hipStream_t s, const uint8_t* d_px, uint32_t w, uint32_t h, uint32_t cx0, uint32_t cy0, uint32_t ncx, uint32_t ncy,
                                              uint8_t* d_flags)
 {
@@ -1547,28 +1537,6 @@ extern "C" hipError_t pfxk_flatten_dle_stats(unsigned long long* out16, int rese
         e = hipMemcpyToSymbol(HIP_SYMBOL(g_dle_stats), z, sizeof z);
     }
     return e;
-}
-extern "C" void pfxk_flatten_set_dle(int units_per_wave, int ring_log2)
-{
-    if (units_per_wave >= 0) g_dle_units = units_per_wave;
-    (void)ring_log2;
-}
-extern "C" void pfxk_flatten_set_dle_dev(int stats_on, int cfg)
-{
-    if (stats_on >= 0) g_dle_stats_on = stats_on;
-    if (cfg >= 0) g_dle_cfg = cfg;
-}
-extern "C" void pfxk_flatten_set_dle_sched(int sched, int fracA, int fracB)
-{
-    if (sched >= 0) g_dle_sched = sched;
-    if (fracA >= 0 && fracA <= 100) g_dle_fracA = fracA;
-    if (fracB >= 0 && fracB <= 100 - g_dle_fracA) g_dle_fracB = fracB;
-}
-extern "C" void pfxk_flatten_set_dle_plan(int kernel, int s1, int s2)
-{
-    if (kernel >= 0) g_dle_kernel = kernel;
-    if (s1 >= -1) g_dle_s1 = s1;
-    if (s2 >= -1) g_dle_s2 = s2;
 }
 extern "C" hipError_t pfxk_dle_probe(hipStream_t s, const pfxk_layer_desc* d_layers, uint32_t cand_layer, uint32_t cand_kind, uint32_t n_px, uint32_t* verdict_pinned,
                                      uint32_t tag)
@@ -1620,130 +1588,54 @@ extern "C" hipError_t pfxk_brush_commit(hipStream_t s, uint8_t* d_layer, const u
     return hipGetLastError();
 }
 
-extern "C" hipError_t pfxk_flatten(hipStream_t stream, const pfxk_layer_desc* d_layers, uint32_t n_layers,
-                                   const float* d_adj_table, int general, int fast_div, uint8_t* d_chunk_active,
-                                   int chunk_active_ready, uint32_t w, uint32_t h, uint8_t* d_dst, const pfxk_preview* preview, const pfxk_region* region,
-                                   const pfxk_dle_cands* cands, const uint8_t* d_chunk_start, int typed_store_ok, int mode_class, int* path_out)
+// Launches what the plan says (pfx_int_flatten_plan, pfx_flatten.cpp: every choice and the measurements behind it are there): one case per instantiation.
+extern "C" hipError_t pfxk_flatten(hipStream_t stream, const pfxk_flatten_plan* plan, const pfxk_layer_desc* d_layers, uint32_t n_layers, const float* d_adj_table,
+                                   uint8_t* d_chunk_active, int chunk_active_ready, uint32_t w, uint32_t h, uint8_t* d_dst, const pfxk_preview* preview,
+                                   const pfxk_region* region, const pfxk_dle_cands* cands, const uint8_t* d_chunk_start)
 {
-    size_t n_quads = ((size_t)w * h + 3) / 4;
-    if (n_quads == 0) return hipSuccess;
-    auto report = [&](int path) { if (path_out) *path_out = path; };
+    const pfxk_flatten_plan& p = *plan;
+    const size_t n_px = (size_t)w * h;
+    if (n_px == 0) return hipSuccess;
     pfxk_preview PV{};
-    if (preview && preview->pixels) { PV = *preview; general = 1; }
+    if (preview && preview->pixels) PV = *preview;
     pfxk_region RG{};
-    if (region && region->rw && region->rh) { RG = *region; general = 1; n_quads = (size_t)((RG.rw + 3u) / 4u) * RG.rh; }
-    if (general && d_chunk_active && !chunk_active_ready) {
+    if (region && region->rw && region->rh) RG = *region;
+    if (p.general && d_chunk_active && !chunk_active_ready) {
         const uint32_t nchunks = ((w + 63u) / 64u) * ((h + 63u) / 64u);
         chunk_active_kernel<<<nchunks, 256, 0, stream>>>(d_layers, n_layers, w, h, d_chunk_active, PV.pixels ? PV.chunk_present : nullptr);
     }
     const uint32_t block = 256;
-    const size_t cap = 256u * 8u * 4u; // 256 CUs x 8 blocks, x4 waves of grid-stride work granularity
-    const size_t n_px = (size_t)w * h;
-    const int flatten_variant = g_flatten_variant, dle_cfg = g_dle_cfg, dle_units = g_dle_units, dle_sched_mode = g_dle_sched, fracA = g_dle_fracA, fracB = g_dle_fracB;
-    if (!general && fast_div && n_layers > 0 && n_px < (1u << 30) && flatten_variant != 9) {
-        // one 64*PX-pixel tile per wave while that stays below the cap (the dispatcher balances the tail), grid-stride beyond
-        // Shipped shape (variant 0), from tools/ab_shallow.py at 8K on stacks of 2 .. 32 layers, with and without an opaque background: 2 pixels
-        // per lane and 2 register sets everywhere (against 3 x 3: -2 % at 32 layers, -8 % at 9, -20 % at 4); up to 16 layers the waves also
-        // walk the image with a grid stride instead of taking one tile each (a 4-layer tile is over before its launch cost is: -5 .. -10 % more)
-        int variant = flatten_variant % 10;
-        bool stride = flatten_variant >= 10;
-        if (flatten_variant == 0 || flatten_variant == 8) {
-            variant = 1; stride = n_layers <= 16;
-            // Round 4, tools/lab/shallow_modes_ab.py (8K, 9 and 12 layers, every mode, S2 data; profiles/r04_shallow_modes_ab.txt) and tools/ab_shallow.py (2 .. 9 layers):
-            // 4 pixels per lane pay where the blend arithmetic is light — Normal, Multiply, Additive, Difference, Lighten / Darken, Overwrite, Subtract, Linear Burn:
-            // one tile per wave -5 .. -7 % from 7 layers up (Normal at 9 layers 0.312 -> 0.290 ms), grid-stride -2 .. -3 % at 5 - 6 layers and for the medium modes
-            // (Screen, Overlay, Negation, Hard Light, Exclusion, Linear Light, Hard Mix); the heavy modes (Reflect .. Color Dodge, Xor, Soft Light, Divide, Vivid
-            // Light, Pin Light) keep 2 pixels per lane (Vivid Light +9 % with 4), and so do stacks of up to 4 layers
-            if (n_layers >= 5 && mode_class == 2) { variant = 3; stride = n_layers < 7; }
-            else if (n_layers >= 5 && mode_class == 1) { variant = 3; stride = true; }
-        }
-        auto grid = [&](uint32_t px_per_wave) {
-            size_t tiles = (n_px + px_per_wave - 1) / px_per_wave, b = (tiles + 3) / 4;
-            const size_t lim = stride ? cap : (size_t)1 << 20;
-            return (uint32_t)(b > lim ? lim : b);
-        };
-        // dead-layer elimination when the stack holds a reset layer above the bottom one (variant 8 switches it off)
-        if (cands && cands->n > 0 && flatten_variant != 8) {
-            // dle_cfg: 0 = 3 pixels per lane, 2 register sets (6 waves per SIMD; measured best), 1 = 2 pixels per lane, 2 = 3 pixels per lane, 3 sets (old kernel only);
-            // dle_sched 0 = equal streams of dle_units
-            const bool srt_kernel = g_dle_kernel == 0 && typed_store_ok;
-            const uint32_t px = dle_cfg == 1 ? 2u : 3u;
-            const uint32_t upx = 64u * px;
-            const uint32_t units = (uint32_t)((n_px + upx - 1) / upx);
-            const uint32_t umax = 65535u / upx; // queue entries are 16-bit pixel offsets
-            dle_sched SC{};
-            if (dle_sched_mode == 0) {
-                SC.UA = SC.UB = SC.UC = std::min(dle_units > 0 ? (uint32_t)dle_units : 8u, umax);
-                SC.wavesA = (units + SC.UA - 1) / SC.UA;
-            } else {
-                // the long streams fill the chip about once (256 CUs x 24 waves): measured best (profiles/r03_tuning.md).  No floor: a floor of 4 units left small
-                // launches (a 64-row dirty rectangle, a thin band of a sharded document) with a quarter of the waves the chip holds — 8K x 64 rows 0.091 -> 0.037 ms,
-                // 8K x 256 rows 0.115 -> 0.081 (tools/lab/band_units_sweep.py, profiles/r04_band_units_sweep.txt)
-                // No ceiling above 8 either since the class-sorting kernel (no queue across units: a stream's length only sets how the launch drains): at 8K
-                // 22 units per wave left the long streams at 0.82 of a chip-full, 8 runs 1.1 % faster (18 — a hair over one chip-full — 3 % slower),
-                // 8K x 2176 rows 11 -> 8: -1.4 % (tools/lab/units_ab.py, randomised order, profiles/r04_units_ab.txt)
-                // (round 3's queue kernel keeps its rule: its compacted rounds need long streams)
-                const uint32_t ua_fill = ((uint32_t)((uint64_t)units * (uint32_t)fracA / 100u) + 6143u) / 6144u;
-                const uint32_t ua_auto = srt_kernel ? std::min(std::max(ua_fill, 1u), 8u) : std::max(ua_fill, 4u);
-                SC.UA = std::min(dle_units > 0 ? (uint32_t)dle_units : ua_auto, umax);
-                SC.UB = std::max(SC.UA / 4u, 1u);
-                SC.UC = 1u;
-                SC.wavesA = (uint32_t)((uint64_t)units * (uint32_t)fracA / 100u) / SC.UA;
-                SC.wavesB = (uint32_t)((uint64_t)units * (uint32_t)fracB / 100u) / SC.UB;
-            }
-            const uint32_t rest = units - std::min(units, SC.wavesA * SC.UA + SC.wavesB * SC.UB);
-            const uint32_t waves = SC.wavesA + SC.wavesB + (rest + SC.UC - 1) / SC.UC;
-            pfxk_dle_cands C = *cands;
-            C.stats = (uint32_t)g_dle_stats_on;
-            if (srt_kernel) {
-                // re-deal attempts start right above the topmost candidate (below it the early pixels' rounds and the reset layer itself run) and
-                // repeat every `seg` layers
-                dle_plan P{};
-                const int o1 = g_dle_s1, o2 = g_dle_s2;
-                P.s1 = C.layer[C.n - 1u] + (o1 > 0 ? (uint32_t)o1 : 1u);
-                P.seg = o2 < 0 ? 3u : (o2 == 0 ? 1000u : (uint32_t)o2);   // 0: a single attempt
-                if (o1 == 0) P.seg = 0u;                                   // no attempts at all: round 3's natural pass + parking in the destination
-#define PFX_ARGS <<<waves, 64, 0, stream>>>(d_layers, n_layers, (uint32_t)n_px, d_dst, C, SC, P)
-                if (C.stats & 4u) flatten_srt_kernel<3, false, true> PFX_ARGS; // diagnostic: per-phase wave clocks (tools/lab/srt_phases.py)
-                else if (C.stats & 2u) flatten_srt_kernel<3, true> PFX_ARGS;   // diagnostic: the load stream without the arithmetic
-                else if (dle_cfg == 1) flatten_srt_kernel<2> PFX_ARGS;
-                else flatten_srt_kernel<3> PFX_ARGS;
+    pfxk_dle_cands C{};
+    if (cands) C = *cands;
+    C.stats = p.stats;
+    const dle_sched SC{p.sched};
+    const dle_plan P{p.redeal};
+    // one wave per workgroup in the elimination kernels: a wave's stream is independent of its neighbours' (no barrier, private LDS slice), and a 4-wave
+    // workgroup would hold its LDS and wave slots until its slowest stream ends
+    // (the cases stand in the order the kernels have always been instantiated in, which is their order in the code object)
+    switch (p.kernel << 12 | (p.kernel == PFXK_FLATTEN_TEMPLATE ? p.general << 1 | p.fast_div : p.px << 8 | p.nb << 4 | p.diag)) {
+#define PFX_ARGS <<<p.waves, 64, 0, stream>>>(d_layers, n_layers, (uint32_t)n_px, d_dst, C, SC, P)
+    case PFXK_FLATTEN_SRT << 12 | 3 << 8 | 4: flatten_srt_kernel<3, false, true> PFX_ARGS; break; // diagnostic: per-phase wave clocks (tools/lab/srt_phases.py)
+    case PFXK_FLATTEN_SRT << 12 | 3 << 8 | 2: flatten_srt_kernel<3, true> PFX_ARGS; break;        // diagnostic: the load stream without the arithmetic
+    case PFXK_FLATTEN_SRT << 12 | 2 << 8: flatten_srt_kernel<2> PFX_ARGS; break;
+    case PFXK_FLATTEN_SRT << 12 | 3 << 8: flatten_srt_kernel<3> PFX_ARGS; break;
 #undef PFX_ARGS
-                report(PFXK_FLATTEN_SRT | PFXK_FLATTEN_FAST_DIV);
-                return hipGetLastError();
-            }
-            // one wave per workgroup: a wave's stream is independent of its neighbours' (no barrier, private LDS slice), and a 4-wave
-            // workgroup would hold its LDS and wave slots until its slowest stream ends
-#define PFX_ARGS <<<waves, 64, 0, stream>>>(d_layers, n_layers, (uint32_t)n_px, d_dst, C, SC)
-            if (dle_cfg == 2) flatten_dle_kernel<3, 10, 1, 3> PFX_ARGS;
-            else if (dle_cfg == 1) flatten_dle_kernel<2, 9, 1, 3> PFX_ARGS;
-            else flatten_dle_kernel<3, 10, 1, 2> PFX_ARGS;
+#define PFX_ARGS <<<p.waves, 64, 0, stream>>>(d_layers, n_layers, (uint32_t)n_px, d_dst, C, SC)
+    case PFXK_FLATTEN_DLE << 12 | 3 << 8 | 3 << 4: flatten_dle_kernel<3, 10, 1, 3> PFX_ARGS; break;
+    case PFXK_FLATTEN_DLE << 12 | 2 << 8 | 3 << 4: flatten_dle_kernel<2, 9, 1, 3> PFX_ARGS; break;
+    case PFXK_FLATTEN_DLE << 12 | 3 << 8 | 2 << 4: flatten_dle_kernel<3, 10, 1, 2> PFX_ARGS; break;
 #undef PFX_ARGS
-            report(PFXK_FLATTEN_DLE | PFXK_FLATTEN_FAST_DIV);
-            return hipGetLastError();
-        }
-        switch (variant) {
-#define PFX_STREAM(PX, NB, MINW) flatten_stream_kernel<PX, NB, MINW><<<grid(64 * PX), block, 0, stream>>>(d_layers, n_layers, (uint32_t)n_px, d_dst, d_chunk_start, w)
-        case 1: PFX_STREAM(2, 2, 1); break;
-        case 2: PFX_STREAM(2, 3, 1); break;
-        case 3: PFX_STREAM(4, 2, 1); break;
-        case 4: PFX_STREAM(4, 3, 1); break;
-        case 5: PFX_STREAM(1, 3, 1); break;
-        case 6: PFX_STREAM(3, 3, 1); break;
-        default: PFX_STREAM(3, 3, 1); break;
+#define PFX_STREAM(PX, NB) case PFXK_FLATTEN_STREAM << 12 | PX << 8 | NB << 4: \
+        flatten_stream_kernel<PX, NB, 1><<<p.grid, block, 0, stream>>>(d_layers, n_layers, (uint32_t)n_px, d_dst, d_chunk_start, w); break
+    PFX_STREAM(2, 2); PFX_STREAM(2, 3); PFX_STREAM(4, 2); PFX_STREAM(4, 3); PFX_STREAM(1, 3); PFX_STREAM(3, 3);
 #undef PFX_STREAM
-        }
-        report(PFXK_FLATTEN_STREAM | PFXK_FLATTEN_FAST_DIV | (d_chunk_start ? PFXK_FLATTEN_CHUNK_START : 0));
-        return hipGetLastError();
-    }
-    size_t blocks = (n_quads + block - 1) / block;
-    if (blocks > cap) blocks = cap;
-    const uint32_t g = (uint32_t)blocks;
-#define PFX_LAUNCH(G, F) flatten_kernel<G, F><<<g, block, 0, stream>>>(d_layers, n_layers, d_adj_table, (G) ? d_chunk_active : nullptr, w, h, d_dst, PV, RG)
-    if (general) { if (fast_div) PFX_LAUNCH(true, true); else PFX_LAUNCH(true, false); }
-    else         { if (fast_div) PFX_LAUNCH(false, true); else PFX_LAUNCH(false, false); }
+#define PFX_LAUNCH(G, F) flatten_kernel<G, F><<<p.grid, block, 0, stream>>>(d_layers, n_layers, d_adj_table, (G) ? d_chunk_active : nullptr, w, h, d_dst, PV, RG)
+    case PFXK_FLATTEN_TEMPLATE << 12 | 3: PFX_LAUNCH(true, true); break;
+    case PFXK_FLATTEN_TEMPLATE << 12 | 2: PFX_LAUNCH(true, false); break;
+    case PFXK_FLATTEN_TEMPLATE << 12 | 1: PFX_LAUNCH(false, true); break;
+    case PFXK_FLATTEN_TEMPLATE << 12 | 0: PFX_LAUNCH(false, false); break;
 #undef PFX_LAUNCH
-    report(PFXK_FLATTEN_TEMPLATE | (general ? PFXK_FLATTEN_GENERAL : 0) | (fast_div ? PFXK_FLATTEN_FAST_DIV : 0) | (RG.rw ? PFXK_FLATTEN_REGION : 0) |
-           (PV.pixels ? PFXK_FLATTEN_PREVIEW : 0));
+    default: return hipErrorInvalidValue;   // a plan no instantiation exists for: a missing kernel is an error
+    }
     return hipGetLastError();
 }

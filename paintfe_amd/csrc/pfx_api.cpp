@@ -1,4 +1,4 @@
-// pfx_api.cpp — the C ABI (include/pfx.h): argument checking, host<->device staging, kernel sequencing.
+// pfx_api.cpp — the C ABI (include/pfx.h): argument checking, host<->device staging, kernel sequencing (the compositor's entry points: pfx_flatten.cpp).
 // Host-buffer entry points = upload -> the `_dev` entry point -> download -> stream sync; `dst` is written only
 // after every step succeeded (the reference's "never poison the document" rule).
 #include <algorithm>
@@ -18,12 +18,6 @@ static_assert((int)PFX_RHAI_COUNT == (int)PFXK_RHAI_COUNT && (int)PFX_RHAI_LEVEL
 static_assert((int)PFX_ADJ_CHANNEL_MIXER == (int)PFXK_ADJ_CHANNEL_MIXER, "layer kinds out of sync");
 
 namespace {
-
-// FAST instantiation of the compositor (k_flatten.hip): requires opacity.clamp(0,1) in [2^-40, 1] for every layer, so
-// that (a) every division operand of blend_pixel_static stays in the normal range where v_div_scale / v_div_fixup
-// are identities and (b) top_a > 0 for every non-skipped pixel (out_a > 0: no zero check, no clamp).  Anything else
-// (zero, negative, tiny or NaN opacity) runs the plain instantiation with IEEE '/', clamps and zero checks.
-inline bool opacity_allows_fast_div(float opacity) { return opacity >= 9.094947017729282e-13f; /* 2^-40 */ }
 
 // The filter family's declaration: a w x h src and dst.  In a `_dev` call dst shares no byte with src — a kernel that reads a halo while other workgroups write
 // the same memory would race silently — unless the header allows in place (same_ok) and the two are the same pointer; the host tier works on staged copies.
@@ -111,270 +105,6 @@ int upload_lut(pfx_ctx* ctx, const uint8_t* lut_host, size_t bytes)
     return pfx_h2d(ctx, ctx->d_lut.p, padded, 1024);
 }
 
-// layer stack -> device descriptors
-// preview layer of a composite call (device pointers; see pfx_preview in include/pfx.h)
-struct preview_arg {
-    const void* d_pixels = nullptr;
-    const void* d_chunk_present = nullptr; // NULL: derive with the from_rgba_image rule
-    pfx_preview info{};
-};
-
-int build_stack(pfx_ctx* ctx, const void* const* layer_ptrs, const void* const* mask_ptrs, const pfx_layer_info* layers,
-                uint32_t n, uint32_t w, uint32_t h, bool from_store, uint32_t* n_desc, bool* general, bool* has_adj,
-                uint32_t track_info = 0xFFFFFFFFu, uint32_t* track_pos = nullptr, const uint8_t** track_pixels = nullptr,
-                pfxk_dle_cands* cands = nullptr, std::vector<uint8_t>* chunk_meta = nullptr, bool* shallow = nullptr)
-{
-    std::vector<const uint8_t*> flag_ptrs; // per descriptor: the stored layer's chunk alpha summary (NULL: none)
-    std::vector<pfxk_layer_desc> desc;
-    std::vector<float> adj;
-    desc.reserve(n);
-    *general = false;
-    *has_adj = false;
-    if (track_pos) *track_pos = 0xFFFFFFFFu;
-    for (uint32_t i = 0; i < n; ++i) {
-        const pfx_layer_info& L = layers[i];
-        if (!L.visible) continue; // layer_effectively_visible == false: skipped entirely (canvas_state.rs:576)
-        pfxk_layer_desc d{};
-        d.opacity = L.opacity;
-        d.mode = L.blend_mode > 24 ? 0u : (uint32_t)L.blend_mode; // BlendMode::from_u8 fallback
-        d.kind = L.kind;
-        if (L.kind != PFX_LAYER_RASTER) {
-            if (L.kind > PFX_ADJ_CHANNEL_MIXER) return pfx_fail(ctx, PFX_ERR_INVALID, "layer %u: unknown kind %u", i, L.kind);
-            d.adj_off = (uint32_t)adj.size();
-            float a[16];
-            std::memcpy(a, L.adj, sizeof a);
-            if (L.kind == PFX_ADJ_EXPOSURE) a[0] = pfx_host_exposure_gain(L.adj[0]);
-            if (L.kind == PFX_ADJ_BRIGHTNESS_CONTRAST) a[1] = pfx_host_bc_factor(L.adj[1]);
-            adj.insert(adj.end(), a, a + 16);
-            *general = true;
-            *has_adj = true;
-        } else if (from_store) {
-            auto it = ctx->layers.find(L.layer_idx);
-            if (it == ctx->layers.end()) continue; // not uploaded: skipped like the reference (renderer.rs:556)
-            if (it->second.w != w || it->second.h != h)
-                return pfx_fail(ctx, PFX_ERR_INVALID, "layer %u is %ux%u, canvas is %ux%u", L.layer_idx, it->second.w, it->second.h, w, h);
-            d.pixels = (const uint8_t*)it->second.pixels.p;
-            if (it->second.has_mask) { d.mask = (const uint8_t*)it->second.mask.p; *general = true; }
-            flag_ptrs.resize(desc.size() + 1, nullptr);
-            flag_ptrs[desc.size()] = it->second.has_mask ? nullptr : (const uint8_t*)it->second.chunk_flags.p;
-        } else {
-            d.pixels = (const uint8_t*)layer_ptrs[i];
-            if (!d.pixels) return pfx_fail(ctx, PFX_ERR_INVALID, "layer %u: null device pointer", i);
-            if (mask_ptrs && mask_ptrs[i]) { d.mask = (const uint8_t*)mask_ptrs[i]; *general = true; }
-        }
-        if (d.kind == PFX_LAYER_RASTER) { // Rust f32::clamp(0.0, 1.0); NaN stays NaN (such a stack never takes the streaming kernels)
-            const float c = d.opacity < 0.0f ? 0.0f : (d.opacity > 1.0f ? 1.0f : d.opacity);
-            std::memcpy(&d.adj_off, &c, 4);
-        }
-        if (i == track_info && track_pos && d.kind == PFX_LAYER_RASTER) { *track_pos = (uint32_t)desc.size(); *track_pixels = d.pixels; }
-        desc.push_back(d);
-    }
-    *n_desc = (uint32_t)desc.size();
-    if (chunk_meta) {
-        // [n_desc summary pointers | n_desc wanted bits]: Normal at opacity >= 1 resets a chunk whose alpha is all 255 (canvas_state.rs:1258),
-        // Overwrite one without a zero alpha (:1275); layer 0 has nothing below it
-        chunk_meta->clear();
-        flag_ptrs.resize(desc.size(), nullptr);
-        std::vector<uint8_t> want(desc.size(), 0);
-        bool any = false;
-        for (size_t p = 1; p < desc.size(); ++p) {
-            if (desc[p].kind != PFX_LAYER_RASTER || desc[p].mask || !flag_ptrs[p]) continue;
-            if (desc[p].mode == 14u) want[p] = 2;
-            else if (desc[p].mode == 0u && desc[p].opacity >= 1.0f) want[p] = 1;
-            any = any || want[p] != 0;
-        }
-        if (any) {
-            chunk_meta->resize(desc.size() * sizeof(void*) + desc.size());
-            std::memcpy(chunk_meta->data(), flag_ptrs.data(), desc.size() * sizeof(void*));
-            std::memcpy(chunk_meta->data() + desc.size() * sizeof(void*), want.data(), desc.size());
-        }
-    }
-    {   // arithmetic weight of the stack's blend modes (k_blend.h instruction counts, profiles/r03_blend_isa.md): the streaming compositor's register shape follows it
-        static const uint8_t cls_of_mode[25] = {2, 2, 1, 2, 0, 0, 0, 0, 1, 2, 1, 2, 2, 0, 2, 1, 0, 1, 2, 0, 2, 0, 1, 0, 1};
-        int cls = 2;
-        for (const pfxk_layer_desc& d : desc) cls = std::min(cls, d.kind == PFX_LAYER_RASTER && d.mode < 25u ? (int)cls_of_mode[d.mode] : 0);
-        ctx->stack_mode_class = desc.empty() ? 0 : cls;
-    }
-    if (cands) {
-        // reset layers (k_flatten.hip: dead-layer elimination): the topmost PFXK_DLE_MAX raster layers above the bottom one that are
-        // Overwrite (canvas_state.rs:1275) or Normal at opacity >= 1 (:1258); only used by the raster-only streaming path
-        std::memset(cands, 0, sizeof *cands);
-        std::vector<std::pair<uint32_t, uint32_t>> found;
-        for (uint32_t p = 1; p < desc.size(); ++p) {
-            const pfxk_layer_desc& d = desc[p];
-            if (d.kind != PFX_LAYER_RASTER || d.mask) continue;
-            if (d.mode == 14u) found.emplace_back(p, 0u);
-            else if (d.mode == 0u && d.opacity >= 1.0f) found.emplace_back(p, 1u);
-        }
-        // Every candidate the kernel inspects costs a layer's worth of reads for the units it examines, and the elimination kernel's load
-        // stream is less efficient than the plain streaming kernel's (4.7 against 5+ TB/s with the arithmetic taken out): it pays where the
-        // blend arithmetic dominates — deep stacks — and loses up to 30 % on shallow, memory-bound ones (tools/ab_docs_dle.py: nine Normal
-        // layers with S2's alpha 0.43 against 0.33 ms).  Stacks below 16 layers keep the plain kernel (pfx_tune "dle_min_layers").
-        // ... unless the caller can decide per stack (flatten_common: a probe of the candidate's alpha, `shallow` tells it the threshold applied)
-        if (desc.size() < (size_t)ctx->dle_min_layers) { if (shallow && ctx->dle_adaptive) *shallow = true; else found.clear(); }
-        const size_t kmax = std::min<size_t>(PFXK_DLE_MAX, std::max<size_t>(1, desc.size() / 6));
-        const size_t first = found.size() > kmax ? found.size() - kmax : 0;
-        for (size_t k = first; k < found.size(); ++k) {
-            cands->layer[cands->n] = found[k].first;
-            cands->kind[cands->n] = found[k].second;
-            cands->n++;
-        }
-    }
-    // PFXK_DESC_PAD copies of the last descriptor behind the stack: the class-sorting compositor requests descriptors ahead of the layer it blends without
-    // clamping the index (k_flatten.hip: srt_layers: every fetch() loads the next descriptor, and the loop runs its fetches in pairs, so a pass over an
-    // odd number of layers that ends at the top of the stack has read descriptor n + 2; srt_early<NB> runs NB - 1 layers ahead in groups of NB; what is
-    // fetched through the copies is never blended)
-    if (!desc.empty()) { const pfxk_layer_desc last = desc.back(); desc.insert(desc.end(), PFXK_DESC_PAD, last); }
-    // the tables only travel when they differ from what the device already holds (a render loop re-composites the same stack: the
-    // small pageable-memory copy in front of every launch was a ~10 us bubble on the stream)
-    const size_t desc_bytes = desc.size() * sizeof(pfxk_layer_desc), adj_bytes = adj.size() * sizeof(float);
-    const bool same_desc = ctx->d_desc.p && ctx->desc_cache.size() == desc_bytes && (desc_bytes == 0 || std::memcmp(ctx->desc_cache.data(), desc.data(), desc_bytes) == 0);
-    if (!same_desc) {
-        ctx->desc_cache.clear();
-        PFX_TRY(pfx_reserve(ctx, ctx->d_desc, std::max<size_t>(desc.size(), 1) * sizeof(pfxk_layer_desc)));
-        PFX_TRY(pfx_h2d(ctx, ctx->d_desc.p, desc.data(), desc_bytes));
-        ctx->desc_cache.assign((const uint8_t*)desc.data(), (const uint8_t*)desc.data() + desc_bytes);
-    }
-    if (!adj.empty()) {
-        const bool same_adj = ctx->d_adj.p && ctx->adj_cache.size() == adj_bytes && std::memcmp(ctx->adj_cache.data(), adj.data(), adj_bytes) == 0;
-        if (!same_adj) {
-            ctx->adj_cache.clear();
-            PFX_TRY(pfx_reserve(ctx, ctx->d_adj, adj_bytes));
-            PFX_TRY(pfx_h2d(ctx, ctx->d_adj.p, adj.data(), adj_bytes));
-            ctx->adj_cache.assign((const uint8_t*)adj.data(), (const uint8_t*)adj.data() + adj_bytes);
-        }
-    }
-    return PFX_OK;
-}
-
-int flatten_common(pfx_ctx* ctx, const void* const* layer_ptrs, const void* const* mask_ptrs, const pfx_layer_info* layers,
-                   uint32_t n_layers, uint32_t w, uint32_t h, bool from_store, void* dst_dev, const preview_arg* pv = nullptr,
-                   const pfxk_region* region = nullptr, const uint8_t* chunk_keys_host = nullptr)
-{
-    PFX_REQUIRE(ctx, n_layers <= PFX_MAX_LAYERS, "too many layers");
-    PFX_REQUIRE(ctx, n_layers == 0 || layers, "null layer list");
-    // in place is allowed — dst may BE one of the layers (every kernel reads a pixel of every layer before it writes that pixel) — a partial overlap is not:
-    // a workgroup would read pixels another one has already replaced
-    if (!from_store && layer_ptrs && dst_dev)
-        for (uint32_t l = 0; l < n_layers; ++l)
-            if (layer_ptrs[l] && layer_ptrs[l] != dst_dev && pfx_ranges_overlap(layer_ptrs[l], pfx_img_bytes(w, h), dst_dev, pfx_img_bytes(w, h)))
-                return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_flatten_dev: dst partially overlaps layer %u (it may be a layer, or disjoint from all)", l);
-    uint32_t n_desc = 0, active_pos = 0xFFFFFFFFu;
-    const uint8_t* active_pixels = nullptr;
-    bool general = false, has_adj = false;
-    pfxk_dle_cands cands{};
-    std::vector<uint8_t> chunk_meta;
-    bool shallow = false;
-    PFX_TRY(build_stack(ctx, layer_ptrs, mask_ptrs, layers, n_layers, w, h, from_store, &n_desc, &general, &has_adj,
-                        pv ? pv->info.active_layer : 0xFFFFFFFFu, &active_pos, &active_pixels, &cands, from_store ? &chunk_meta : nullptr,
-                        from_store ? nullptr : &shallow));
-    bool probe_now = false;
-    uint32_t probe_layer = 0, probe_kind = 0;
-    if (shallow && cands.n > 0) {
-        // Below the depth threshold the elimination kernel runs only where a probe of THIS stack found its topmost reset layer coherent (an opaque photo layer,
-        // a filled background above old layers: most units start there and read nothing below; per-pixel-random alpha splits every unit and loses 30 %).  The
-        // probe runs once per stack, behind the composite that found none, and reports through pinned memory: later composites of the same stack use it.
-        const bool usable = !general && !region && !(pv && pv->d_pixels) && (uint64_t)w * h < (1ull << 30);
-        std::vector<uint8_t> key(ctx->desc_cache);
-        key.insert(key.end(), (const uint8_t*)&w, (const uint8_t*)&w + 4); key.insert(key.end(), (const uint8_t*)&h, (const uint8_t*)&h + 4);
-        const bool same = ctx->dle_probe_state != 0 && key == ctx->dle_probe_key;
-        if (same && ctx->dle_probe_state == 1 && hipEventQuery(ctx->ev_dle_probe) == hipSuccess)
-            ctx->dle_probe_state = *ctx->h_dle_verdict == (ctx->dle_probe_tag | 0x80000000u) ? 2 : 3;
-        if (usable && !same) { probe_now = true; ctx->dle_probe_key.swap(key); ctx->dle_probe_state = 0; }
-        probe_layer = cands.layer[cands.n - 1u]; probe_kind = cands.kind[cands.n - 1u];
-        if (!(usable && same && ctx->dle_probe_state == 2)) cands.n = 0;   // the plain streaming kernel
-    }
-    const size_t nchunks = (size_t)((w + 63) / 64) * ((h + 63) / 64);
-    uint8_t* d_chunks = nullptr;
-    bool chunks_ready = false;
-    if (has_adj) { // adjustment layers only run on chunks populated in some visible layer (canvas_state.rs:529-550)
-        PFX_TRY(pfx_reserve(ctx, ctx->d_chunks, nchunks));
-        d_chunks = (uint8_t*)ctx->d_chunks.p;
-        // a caller that still has the layers' TiledImage chunk keys (a loaded document) passes their union: a chunk that is present
-        // but fully transparent counts, exactly as in the reference; flat layers can only offer "some alpha != 0" (the kernel's pre-pass)
-        if (chunk_keys_host && !(pv && pv->d_pixels)) { PFX_TRY(pfx_h2d(ctx, d_chunks, chunk_keys_host, nchunks)); chunks_ready = true; }
-    }
-    pfxk_preview PV{};
-    if (pv && pv->d_pixels) { // chunk flags: [preview present | active layer present] (canvas_state.rs:541-548,587,593-597)
-        PFX_TRY(pfx_reserve(ctx, ctx->fx_a, 2 * nchunks));
-        uint8_t* flags = (uint8_t*)ctx->fx_a.p;
-        if (pv->d_chunk_present) PFX_HIP(ctx, hipMemcpyAsync(flags, pv->d_chunk_present, nchunks, hipMemcpyDeviceToDevice, ctx->stream));
-        else PFX_HIP(ctx, pfxk_chunk_populated(ctx->stream, (const uint8_t*)pv->d_pixels, w, h, flags));
-        if (active_pixels) PFX_HIP(ctx, pfxk_chunk_populated(ctx->stream, active_pixels, w, h, flags + nchunks));
-        PV.pixels = (const uint8_t*)pv->d_pixels;
-        PV.chunk_present = flags;
-        PV.layer_chunk_present = flags + nchunks;
-        PV.active_pos = active_pos; // 0xFFFFFFFF when the active layer is hidden: only its chunk keys count
-        PV.mode = pv->info.blend_mode > 24 ? 0u : pv->info.blend_mode;
-        PV.is_eraser = pv->info.is_eraser != 0;
-        PV.replaces = pv->info.replaces_layer != 0;
-    }
-    bool fast_div = true; // k_flatten.hip:rdiv is bit-identical to '/' unless an opacity is a positive value < 2^-40
-    for (uint32_t i = 0; i < n_layers; ++i) fast_div = fast_div && opacity_allows_fast_div(layers[i].opacity);
-    // stored layers: the per-chunk start table (which layer is the first that can show in a 64 x 64 chunk) from their alpha summaries —
-    // only the plain streaming kernel takes it (whole-frame, raster-only stacks)
-    const uint8_t* d_chunk_start = nullptr;
-    if (ctx->use_chunk_start && !chunk_meta.empty() && !general && fast_div && !region && !PV.pixels && cands.n == 0 && n_desc < 255) {
-        if (!ctx->h_chunk_useful) {
-            PFX_HIP(ctx, hipHostMalloc((void**)&ctx->h_chunk_useful, sizeof(uint32_t), hipHostMallocDefault));
-            *ctx->h_chunk_useful = 0;
-            PFX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_chunk_useful, hipEventDisableTiming));
-        }
-        const bool same = ctx->chunk_state != 0 && ctx->chunk_epoch == ctx->store_epoch && ctx->chunk_meta_cache == chunk_meta &&
-                          ctx->d_chunk_start.cap >= nchunks;
-        if (same && ctx->chunk_state == 1 && hipEventQuery(ctx->ev_chunk_useful) == hipSuccess)
-            ctx->chunk_state = (*ctx->h_chunk_useful == ctx->chunk_tag) ? 2 : 3; // the table kernel of an earlier call has finished: its verdict is in
-        if (!same) {
-            ctx->chunk_meta_cache.clear();
-            PFX_TRY(pfx_reserve(ctx, ctx->d_chunk_meta, chunk_meta.size()));
-            PFX_TRY(pfx_h2d(ctx, ctx->d_chunk_meta.p, chunk_meta.data(), chunk_meta.size()));
-            ctx->chunk_meta_cache = chunk_meta;
-            PFX_TRY(pfx_reserve(ctx, ctx->d_chunk_start, nchunks));
-            ctx->chunk_tag += 1u;
-            PFX_HIP(ctx, pfxk_chunk_start(ctx->stream, (const uint8_t* const*)ctx->d_chunk_meta.p, (const uint8_t*)ctx->d_chunk_meta.p + (size_t)n_desc * sizeof(void*),
-                                          n_desc, (uint32_t)nchunks, (uint8_t*)ctx->d_chunk_start.p, ctx->h_chunk_useful, ctx->chunk_tag));
-            PFX_HIP(ctx, hipEventRecord(ctx->ev_chunk_useful, ctx->stream));
-            ctx->chunk_state = 1;
-            ctx->chunk_epoch = ctx->store_epoch;
-        }
-        if (ctx->chunk_state != 3) d_chunk_start = (const uint8_t*)ctx->d_chunk_start.p; // pending or useful: the table of THIS stack is in the buffer
-    }
-    // The class-sorting compositor (k_flatten.hip: flatten_srt_kernel) reads every layer through typed UNORM8 buffer loads and keeps its accumulators as
-    // RN(k / 255); its result leaves as v_cvt_pk_u8_f32 + dword stores (the typed format store measured 1 % slower).  The device's UNORM8 <-> float
-    // conversions must be exact for all 256 byte values, which is checked once per context on the device itself.  Otherwise round 3's kernel runs.
-    int parking_ok = 0;
-    if (cands.n > 0 && !general && fast_div && !region && !PV.pixels) {
-        if (ctx->unorm_store_ok < 0) {
-            PFX_TRY(pfx_reserve(ctx, ctx->d_misc, 2048));
-            PFX_HIP(ctx, hipMemsetAsync(ctx->d_misc.p, 0, 2048, ctx->stream));
-            PFX_HIP(ctx, pfxk_unorm_store_check(ctx->stream, (uint8_t*)ctx->d_misc.p, (unsigned long long*)((uint8_t*)ctx->d_misc.p + 1024)));
-            unsigned long long bad = 1;
-            PFX_TRY(pfx_d2h(ctx, &bad, (uint8_t*)ctx->d_misc.p + 1024, sizeof bad));
-            PFX_TRY(pfx_sync(ctx)); // once per context
-            ctx->unorm_store_ok = bad == 0 ? 1 : 0;
-        }
-        parking_ok = ctx->unorm_store_ok == 1;
-    }
-    {
-        pfx_timer t(ctx, "flatten");
-        PFX_HIP(ctx, pfxk_flatten(ctx->stream, (const pfxk_layer_desc*)ctx->d_desc.p, n_desc, (const float*)ctx->d_adj.p,
-                                  general ? 1 : 0, fast_div ? 1 : 0, d_chunks, chunks_ready ? 1 : 0, w, h, (uint8_t*)dst_dev, PV.pixels ? &PV : nullptr, region, &cands, d_chunk_start,
-                                  parking_ok, ctx->stack_mode_class, &ctx->last_flatten_path));
-    }
-    if (probe_now) {   // behind the composite (it may have been in place: the probe reads layers, and a layer that was the destination now holds the result — a hint all the same)
-        if (!ctx->h_dle_verdict) {
-            PFX_HIP(ctx, hipHostMalloc((void**)&ctx->h_dle_verdict, sizeof(uint32_t), hipHostMallocDefault));
-            *ctx->h_dle_verdict = 0;
-        }
-        if (!ctx->ev_dle_probe) PFX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_dle_probe, hipEventDisableTiming));
-        ctx->dle_probe_tag = (ctx->dle_probe_tag + 1u) & 0x7fffffffu;
-        PFX_HIP(ctx, pfxk_dle_probe(ctx->stream, (const pfxk_layer_desc*)ctx->d_desc.p, probe_layer, probe_kind, (uint32_t)((size_t)w * h), ctx->h_dle_verdict, ctx->dle_probe_tag));
-        PFX_HIP(ctx, hipEventRecord(ctx->ev_dle_probe, ctx->stream));
-        ctx->dle_probe_state = 1;
-    }
-    return PFX_OK;
-}
-
 // the displacement warp's declaration: an sw x sh source sampled into a w x h output through a w x h field.  The SOURCE's extent counts, it may be larger
 // than the output; the field is only required (these calls have never looked at where it lies)
 int check_warp(pfx_ctx* ctx, const char* who, bool dev, const void* src, uint32_t sw, uint32_t sh, const void* disp, uint32_t w, uint32_t h, const void* dst)
@@ -414,28 +144,6 @@ int brush_prepare(pfx_ctx* ctx, const pfx_brush* b, pfxk_brush& B, bool& skip)
 extern "C" {
 
 // ======================================================================= device tier
-int pfx_flatten_dev(pfx_ctx* ctx, const void* const* layer_ptrs_dev, const void* const* mask_ptrs_dev,
-                    const pfx_layer_info* layers, uint32_t n_layers, uint32_t w, uint32_t h, void* dst_dev)
-{
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, dst_dev && pfx_dims_ok(w, h) && (n_layers == 0 || layer_ptrs_dev), "pfx_flatten_dev: bad arguments");
-    PFX_TRY(pfx_use(ctx));
-    return flatten_common(ctx, layer_ptrs_dev, mask_ptrs_dev, layers, n_layers, w, h, false, dst_dev);
-}
-
-// pfx_flatten_dev for a document whose layers are TiledImages: chunk_keys_host[c] != 0 where some visible raster layer HOLDS chunk c
-// (canvas_state.rs:528-550 `chunk_keys()`), whatever its pixels are
-int pfx_int_flatten_with_chunk_keys_dev(pfx_ctx* ctx, const void* const* layer_ptrs_dev, const pfx_layer_info* layers, uint32_t n_layers,
-                                        uint32_t w, uint32_t h, void* dst_dev, const uint8_t* chunk_keys_host)
-{
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, dst_dev && w && h && (n_layers == 0 || layer_ptrs_dev), "pfx_int_flatten_with_chunk_keys_dev: bad arguments");
-    PFX_TRY(pfx_use(ctx));
-    return flatten_common(ctx, layer_ptrs_dev, nullptr, layers, n_layers, w, h, false, dst_dev, nullptr, nullptr, chunk_keys_host);
-}
-
-int pfx_int_flatten_last_path(pfx_ctx* ctx) { return !ctx ? -1 : ctx->last_flatten_path; }
-
 int pfx_gaussian_blur_dev(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, float sigma, void* tmp_dev)
 {
     return pfx_gaussian_blur_band_dev(ctx, src_dev, dst_dev, w, h, sigma, tmp_dev, 0);
@@ -1153,67 +861,6 @@ int pfx_auto_levels(pfx_ctx* ctx, const uint8_t* src, uint8_t* dst, uint32_t w, 
     return pfx_unstage(ctx, dst, ctx->st_out, pfx_img_bytes(w, h));
 }
 
-int pfx_composite_region(pfx_ctx* ctx, uint32_t w, uint32_t h, const pfx_layer_info* layers, uint32_t n_layers, uint32_t x,
-                         uint32_t y, uint32_t rw, uint32_t rh, uint8_t* dst_region)
-{
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, dst_region && pfx_dims_ok(w, h) && pfx_rect_inside(x, y, rw, rh, w, h), "pfx_composite: bad arguments");
-    PFX_TRY(pfx_use(ctx));
-    PFX_TRY(pfx_reserve(ctx, ctx->st_out, pfx_img_bytes(w, h)));
-    if (rw == w && rh == h) {
-        PFX_TRY(flatten_common(ctx, nullptr, nullptr, layers, n_layers, w, h, true, ctx->st_out.p));
-        return pfx_unstage(ctx, dst_region, ctx->st_out, pfx_img_bytes(w, h));
-    }
-    // dirty rectangle (composite_dirty_readback, renderer.rs:588): only its pixels are composited, into a compact rw x rh image
-    const pfxk_region rg{x, y, rw, rh};
-    PFX_TRY(flatten_common(ctx, nullptr, nullptr, layers, n_layers, w, h, true, ctx->st_out.p, nullptr, &rg));
-    PFX_TRY(pfx_d2h(ctx, dst_region, ctx->st_out.p, (size_t)rw * rh * 4));
-    return pfx_sync(ctx);
-}
-
-int pfx_composite(pfx_ctx* ctx, uint32_t w, uint32_t h, const pfx_layer_info* layers, uint32_t n_layers, uint8_t* dst)
-{
-    return pfx_composite_region(ctx, w, h, layers, n_layers, 0, 0, w, h, dst);
-}
-
-// composite with the tool preview layer folded into the active layer (canvas_state.rs:541-548,593-658)
-int pfx_composite_preview(pfx_ctx* ctx, uint32_t w, uint32_t h, const pfx_layer_info* layers, uint32_t n_layers, const uint8_t* preview_pixels,
-                          const uint8_t* preview_chunk_present, const pfx_preview* preview, uint8_t* dst)
-{
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, dst && pfx_dims_ok(w, h), "pfx_composite_preview: bad arguments");
-    if (!preview_pixels) return pfx_composite(ctx, w, h, layers, n_layers, dst);
-    PFX_REQUIRE(ctx, preview != nullptr, "pfx_composite_preview: null preview description");
-    PFX_TRY(pfx_use(ctx));
-    const size_t nchunks = (size_t)((w + 63) / 64) * ((h + 63) / 64);
-    PFX_TRY(pfx_reserve(ctx, ctx->st_out, pfx_img_bytes(w, h)));
-    PFX_TRY(pfx_reserve(ctx, ctx->fx_b, pfx_img_bytes(w, h) + nchunks));
-    PFX_TRY(pfx_h2d(ctx, ctx->fx_b.p, preview_pixels, pfx_img_bytes(w, h)));
-    preview_arg pv;
-    pv.d_pixels = ctx->fx_b.p;
-    if (preview_chunk_present) {
-        PFX_TRY(pfx_h2d(ctx, (uint8_t*)ctx->fx_b.p + pfx_img_bytes(w, h), preview_chunk_present, nchunks));
-        pv.d_chunk_present = (const uint8_t*)ctx->fx_b.p + pfx_img_bytes(w, h);
-    }
-    pv.info = *preview;
-    PFX_TRY(flatten_common(ctx, nullptr, nullptr, layers, n_layers, w, h, true, ctx->st_out.p, &pv));
-    return pfx_unstage(ctx, dst, ctx->st_out, pfx_img_bytes(w, h));
-}
-
-int pfx_flatten_preview_dev(pfx_ctx* ctx, const void* const* layer_ptrs_dev, const void* const* mask_ptrs_dev, const pfx_layer_info* layers,
-                            uint32_t n_layers, uint32_t w, uint32_t h, const void* preview_dev, const void* preview_chunk_present_dev,
-                            const pfx_preview* preview, void* dst_dev)
-{
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, dst_dev && pfx_dims_ok(w, h) && (n_layers == 0 || layer_ptrs_dev) && (!preview_dev || preview), "pfx_flatten_preview_dev: bad arguments");
-    PFX_TRY(pfx_use(ctx));
-    preview_arg pv;
-    pv.d_pixels = preview_dev;
-    pv.d_chunk_present = preview_chunk_present_dev;
-    if (preview) pv.info = *preview;
-    return flatten_common(ctx, layer_ptrs_dev, mask_ptrs_dev, layers, n_layers, w, h, false, dst_dev, preview_dev ? &pv : nullptr);
-}
-
 int pfx_blend_pixels(pfx_ctx* ctx, const uint8_t* base, const uint8_t* top, uint8_t* dst, size_t n_pixels, uint8_t blend_mode, float opacity)
 {
     const size_t bytes = n_pixels * 4;
@@ -1413,23 +1060,10 @@ int pfx_tune(pfx_ctx* ctx, const char* key, int value)
     if (std::strcmp(key, "gauss_v_cfg") == 0) { pfxk_gauss_set_v_config(value); return PFX_OK; }
     if (std::strcmp(key, "gauss_mfma_segments") == 0) { pfxk_gauss_set_mfma_segments(value); return PFX_OK; }
     if (std::strcmp(key, "gauss_parts") == 0) { pfxk_gauss_set_mfma_parts(value / 10, value % 10); return PFX_OK; } // f16 pieces per weight, per horizontal result: 22, 12, 11
-    if (std::strcmp(key, "flatten_variant") == 0) { pfxk_flatten_set_variant(value); return PFX_OK; }
-    if (std::strcmp(key, "dle_units") == 0) { pfxk_flatten_set_dle(value, -1); return PFX_OK; }
-    if (std::strcmp(key, "dle_ring") == 0) { pfxk_flatten_set_dle(-1, value); return PFX_OK; }
-    if (std::strcmp(key, "dle_stats") == 0) { pfxk_flatten_set_dle_dev(value, -1); return PFX_OK; }
-    if (std::strcmp(key, "chunk_start") == 0) { ctx->use_chunk_start = value != 0; return PFX_OK; }
-    if (std::strcmp(key, "dle_min_layers") == 0) { ctx->dle_min_layers = value; return PFX_OK; }
-    if (std::strcmp(key, "dle_sched") == 0) { pfxk_flatten_set_dle_sched(value, -1, -1); return PFX_OK; }
-    if (std::strcmp(key, "dle_frac_a") == 0) { pfxk_flatten_set_dle_sched(-1, value, -1); return PFX_OK; }
-    if (std::strcmp(key, "dle_frac_b") == 0) { pfxk_flatten_set_dle_sched(-1, -1, value); return PFX_OK; }
-    if (std::strcmp(key, "dle_cfg") == 0) { pfxk_flatten_set_dle_dev(-1, value); return PFX_OK; }
-    if (std::strcmp(key, "dle_kernel") == 0) { pfxk_flatten_set_dle_plan(value, -2, -2); return PFX_OK; }   // 0 = class sorting, 1 = round-3 kernel
-    if (std::strcmp(key, "dle_s1") == 0) { pfxk_flatten_set_dle_plan(-1, value, -2); return PFX_OK; }       // re-deal attempts: first one this many layers above the topmost candidate (-1: 1, 0: never)
-    if (std::strcmp(key, "dle_s2") == 0) { pfxk_flatten_set_dle_plan(-1, -2, value); return PFX_OK; }       // ... then every this many layers (-1: 3, 0: only the first)
+    if (std::strcmp(key, "flatten_variant") == 0 || std::strncmp(key, "dle_", 4) == 0 || std::strcmp(key, "chunk_start") == 0) return pfx_flatten_tune(ctx, key, value);   // the knobs live in pfx_flatten.cpp
     if (std::strncmp(key, "median_", 7) == 0 || std::strncmp(key, "box_", 4) == 0) return pfx_stencil_tune(ctx, key, value);   // the knobs live in pfx_stencil.cpp
     if (std::strcmp(key, "outline_bits") == 0) { ctx->outline_bits = value != 0; return PFX_OK; }
     if (std::strcmp(key, "brush_binning") == 0) { ctx->brush_binning = value != 0; return PFX_OK; }   // 0: long strokes on the bounding-box kernel too
-    if (std::strcmp(key, "dle_adaptive") == 0) { ctx->dle_adaptive = value != 0; ctx->dle_probe_state = 0; return PFX_OK; }   // 0 = shallow stacks never take the elimination kernel
     if (std::strcmp(key, "gauss_fused_exact") == 0) { pfxk_gauss_set_fused_exact(value); return PFX_OK; }  // 0 = the bit-exact Gaussian always through the two kernels
     if (std::strcmp(key, "mesh_xcd") == 0) { pfxk_warp_set_mesh_xcd(value); return PFX_OK; }            // 0 = the fused mesh warp's plain 2-D tile order
     if (std::strcmp(key, "shadow_plane") == 0) { ctx->shadow_plane_blur = value != 0; return PFX_OK; } // drop shadow: blur the alpha plane (1) or the RGBA expansion (0); identical results
@@ -1439,27 +1073,6 @@ int pfx_tune(pfx_ctx* ctx, const char* key, int value)
     if (std::strcmp(key, "gauss_fast_effects") == 0) { ctx->gauss_fast_effects = value != 0; return PFX_OK; } // sharpen / glow / shadow on the default-mode Gaussian (+-amount LSB)
     if (std::strcmp(key, "resize_two_pass") == 0) { ctx->resize_two_pass = value != 0; return PFX_OK; } // A/B and the parity test of the fused kernel
     return pfx_fail(ctx, PFX_ERR_INVALID, "pfx_tune: unknown key %s", key);
-}
-
-int pfx_flatten_stats(pfx_ctx* ctx, uint64_t out[8], int reset)
-{
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, out != nullptr, "pfx_flatten_stats: null output");
-    PFX_TRY(pfx_sync(ctx));
-    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "counter width");
-    unsigned long long all[16];
-    PFX_HIP(ctx, pfxk_flatten_dle_stats(all, reset));
-    for (int i = 0; i < 8; ++i) out[i] = all[i];
-    return PFX_OK;
-}
-
-int pfx_flatten_trace(pfx_ctx* ctx, uint64_t out[16], int reset)
-{
-    if (!ctx) return PFX_ERR_INVALID;
-    PFX_REQUIRE(ctx, out != nullptr, "pfx_flatten_trace: null output");
-    PFX_TRY(pfx_sync(ctx));
-    PFX_HIP(ctx, pfxk_flatten_dle_stats((unsigned long long*)out, reset));
-    return PFX_OK;
 }
 
 int pfx_selftest_division(pfx_ctx* ctx, uint64_t seed, uint32_t n_millions, uint64_t* mismatches)

@@ -49,7 +49,7 @@ struct pfx_ctx {
     int median_bits_min = 3;   // pfx_tune "median_bits_min", the one per-context knob of pfx_stencil.cpp (see pfx_int_median_path there)
     int last_median_path = -1, last_box_plan = -1;   // what pfx_stencil_median / _box last launched; pfx_int_stencil_last_path reads them, nothing else does
     int last_resize_path = -1, last_resize_span = -1;   // what pfx_resize_image_dev last launched; pfx_int_resize_last reads them, nothing else does
-    int last_flatten_path = -1;                         // what pfxk_flatten last launched for this context; pfx_int_flatten_last_path reads it, nothing else does
+    pfxk_flatten_plan last_flatten_plan = {-1, -1};     // what pfxk_flatten last launched for this context (path -1: nothing yet); pfx_int_flatten_last_path / _plan read it, nothing else does
     int last_brush_path = -1;                           // what pfx_brush_stamps_ex_dev last did; pfx_int_brush_last reads it, nothing else does
     pfx_devbuf fx_a, fx_b; // effect-bank scratch (crystallize cell table, drop-shadow planes)
     // small parameter buffers
@@ -85,8 +85,8 @@ struct pfx_ctx {
     uint32_t wts_sigma_bits = 0, wsplit_sigma_bits = 0;
     bool use_chunk_start = true; // stored layers: per-chunk start table from their alpha summaries (pfx_tune "chunk_start")
     int unorm_store_ok = -1;  // -1 not checked yet, 1 = typed UNORM8 stores round-trip RN(k / 255) exactly on this device (pfxk_unorm_store_check), 0 = they do not
-    int stack_mode_class = 0; // set by build_stack: 0 heavy / unknown, 1 medium, 2 light blend arithmetic (pfxk_flatten picks the streaming kernel's shape from it)
-    int dle_min_layers = 16;  // stacks at least this deep may take the compositor's dead-layer elimination kernel (pfx_api.cpp:build_stack)
+    int stack_mode_class = 0; // set by build_stack: 0 heavy / unknown, 1 medium, 2 light blend arithmetic (pfx_int_flatten_plan picks the streaming kernel's shape from it)
+    int dle_min_layers = 16;  // stacks at least this deep may take the compositor's dead-layer elimination kernel (pfx_flatten.cpp: pfx_int_flatten_cands)
     bool wts_valid = false, wsplit_valid = false; // explicit flags: every 32-bit pattern is some sigma (0xffffffff is a NaN)
     float wsplit_inv_scale = 1.0f, wsplit_bias = 0.0f, wsplit_bias_single = 0.0f;
     pfx_devbuf d_wsplit;
@@ -192,13 +192,37 @@ struct pfx_timer {
     ~pfx_timer();
 };
 
-// flatten of device-resident flat layers + the union of the visible layers' TiledImage chunk keys (pfx_api.cpp)
+// ---- the compositor's host side (pfx_flatten.cpp): pfx_tune's knobs, the layer stack, the one decision which kernel runs and in what shape, the entry points ----
+// FAST instantiation of the compositor (k_flatten.hip): requires opacity.clamp(0,1) in [2^-40, 1] for every layer, so
+// that (a) every division operand of blend_pixel_static stays in the normal range where v_div_scale / v_div_fixup
+// are identities and (b) top_a > 0 for every non-skipped pixel (out_a > 0: no zero check, no clamp).  Anything else
+// (zero, negative, tiny or NaN opacity) runs the plain instantiation with IEEE '/', clamps and zero checks.
+inline bool opacity_allows_fast_div(float opacity) { return opacity >= 9.094947017729282e-13f; /* 2^-40 */ }
+struct pfx_flatten_case {   // plain ints: the test seam fills it from Python
+    // the stack: visible layers that became descriptors; the canvas; a live mask or an adjustment layer; a tool preview; the dirty rectangle (0 x 0: whole canvas);
+    // every opacity of the call allows the shared-reciprocal division; arithmetic weight of the blend modes (0 heavy / unknown, 1 medium, 2 light)
+    int n_desc; uint32_t w, h; int general, has_preview; uint32_t rw, rh; int fast_div, mode_class;
+    // reset-layer candidates that survived the depth threshold and the probe, the topmost one's position; the device's UNORM8 conversions are verified exact
+    // (pfxk_unorm_store_check: the class-sorting kernel may run); the per-chunk start table is handed to the streaming kernel
+    int n_cands, cand_top, unorm_ok, chunk_start;
+    // the process-wide knobs as the call found them: pfx_tune "flatten_variant", then "dle_" + units, cfg, sched, frac_a, frac_b, kernel, s1, s2, stats
+    int variant, units, cfg, sched, fracA, fracB, kernel, s1, s2, stats;
+};
+// the decisions, pure, exported as test seams (not in include/pfx.h): the plan's kernel with *plan filled (pfx_kernels.h); the candidate count with *cands and
+// *shallow (the stack is below min_layers and `adaptive` leaves the decision to the probe) filled; bit 0 the stack keeps its candidates, bit 1 it is probed now
+extern "C" int pfx_int_flatten_plan(const pfx_flatten_case* c, pfxk_flatten_plan* plan);
+extern "C" int pfx_int_flatten_cands(const int* modes /* < 0: not a raster layer */, const float* opacities, const uint8_t* masked, uint32_t n, int min_layers, int adaptive,
+                                     pfxk_dle_cands* cands, int* shallow);
+extern "C" int pfx_int_flatten_verdict(int usable, int same, int probe_state);
+// for the tests, what the context's last composite launched (every pfx_composite* / pfx_flatten*_dev entry point ends in pfxk_flatten): the plan, and its path word
+// alone — a PFXK_FLATTEN_* kernel (0 the flatten_kernel<GENERAL, F> template, 1 streaming, 2 elimination, 3 class-sorting) | GENERAL << 4 | fast_div << 5 |
+// region << 6 | preview << 7 | chunk-start table used << 8 (pfx_kernels.h); -1 = none yet
+extern "C" int pfx_int_flatten_last_path(pfx_ctx* ctx);
+extern "C" int pfx_int_flatten_last_plan(pfx_ctx* ctx, pfxk_flatten_plan* plan);
+int pfx_flatten_tune(pfx_ctx* ctx, const char* key, int value);   // pfx_tune's flatten_variant, dle_* and chunk_start keys
+// flatten of device-resident flat layers + the union of the visible layers' TiledImage chunk keys
 extern "C" int pfx_int_flatten_with_chunk_keys_dev(pfx_ctx* ctx, const void* const* layer_ptrs_dev, const pfx_layer_info* layers, uint32_t n_layers,
                                                    uint32_t w, uint32_t h, void* dst_dev, const uint8_t* chunk_keys_host);
-// for the tests, what the context's last composite launched (every pfx_composite* / pfx_flatten*_dev entry point ends in pfxk_flatten): a PFXK_FLATTEN_* kernel
-// (0 the flatten_kernel<GENERAL, F> template, 1 streaming, 2 elimination, 3 class-sorting) | GENERAL << 4 | fast_div << 5 | region << 6 | preview << 7 |
-// chunk-start table used << 8 (pfx_kernels.h); -1 = none yet (not in include/pfx.h)
-extern "C" int pfx_int_flatten_last_path(pfx_ctx* ctx);
 
 // ---- the Gaussian's host side (pfx_gauss.cpp): the tap-table caches, the one decision which kernel runs, the launches ----
 enum { PFX_GAUSS_PLAIN = 0, PFX_GAUSS_SHARPEN = 1, PFX_GAUSS_GLOW = 2, PFX_GAUSS_CHAIN = 3, PFX_GAUSS_PLANE = 4 };   // what rides in the Gaussian's store

@@ -50,37 +50,43 @@ typedef struct pfxk_region { uint32_t x0, y0, rw, rh; } pfxk_region;
 // opacity >= 1, alpha == 255 (:1258).  The compositor skips the layers below a pixel's topmost reset (k_flatten.hip, flatten_dle_kernel).
 #define PFXK_DLE_MAX 4
 #define PFXK_DESC_PAD 16 /* copies of the last layer descriptor the host appends (valid indices end at n + PFXK_DESC_PAD - 1): the shipped compositor loops (k_flatten.hip: srt_layers_pipe, srt_early_pipe) read up to descriptor n and fetch nothing through it; the PFX_SRT_PIPE 0 and TR builds' srt_layers reads up to n + 2, srt_early<NB> up to n + 2 NB - 2 */
-typedef struct pfxk_dle_cands { uint32_t n; uint32_t layer[PFXK_DLE_MAX]; uint32_t kind[PFXK_DLE_MAX]; uint32_t stats; /* set by the launcher */ } pfxk_dle_cands;
-hipError_t pfxk_flatten(hipStream_t stream, const pfxk_layer_desc* d_layers, uint32_t n_layers,
-                        const float* d_adj_table, int general, int fast_div, uint8_t* d_chunk_active, int chunk_active_ready, uint32_t w,
-                        uint32_t h, uint8_t* d_dst, const pfxk_preview* preview /* may be NULL */,
-                        const pfxk_region* region /* may be NULL */, const pfxk_dle_cands* cands /* may be NULL: no elimination */,
-                        const uint8_t* d_chunk_start /* may be NULL: per-chunk first layer that can show (pfxk_chunk_start) */,
-                        int typed_store_ok /* the device's float -> UNORM8 typed-store conversion is verified (pfxk_unorm_store_check): the class-sorting
-                                              kernel may write its result that way (k_flatten.hip: flatten_srt_kernel) */,
-                        int mode_class /* arithmetic weight of the stack's blend modes: 0 heavy (or unknown), 1 medium, 2 light: picks the streaming kernel's shape */,
-                        int* path_out /* may be NULL: what was launched, PFXK_FLATTEN_* kernel | flag bits (the tests' seam, pfx_int_flatten_last_path) */);
-// *path_out of pfxk_flatten: the kernel in the low four bits, then the template kernel's GENERAL and F arguments (the streaming and elimination kernels
-// always run under the fast-division precondition, without GENERAL), a dirty rectangle, a tool preview, the per-chunk start table
+typedef struct pfxk_dle_cands { uint32_t n; uint32_t layer[PFXK_DLE_MAX]; uint32_t kind[PFXK_DLE_MAX]; uint32_t stats; /* set by the launcher from the plan */ } pfxk_dle_cands;
+// What pfxk_flatten launches, decided by pfx_int_flatten_plan (pfx_flatten.cpp) and by nothing else.  The schedule and the re-deal plan are kernel arguments of the
+// elimination kernels (k_flatten.hip).
+typedef struct pfxk_dle_sched { uint32_t wavesA, UA, wavesB, UB, UC; } pfxk_dle_sched; // waves [0, wavesA) own UA units each, the next wavesB UB, the rest UC
+typedef struct pfxk_dle_plan { uint32_t s1, seg; } pfxk_dle_plan; // re-deal attempts in front of layers s1, s1 + seg, s1 + 2 seg, ... (seg == 0: none)
+// kernel: the low four bits of `path`, and which of the fields below count.  path: the kernel, then the template kernel's GENERAL and F arguments (the streaming and
+// elimination kernels always run under the fast-division precondition, without GENERAL), a dirty rectangle, a tool preview, the per-chunk start table
 enum { PFXK_FLATTEN_TEMPLATE = 0, PFXK_FLATTEN_STREAM = 1, PFXK_FLATTEN_DLE = 2, PFXK_FLATTEN_SRT = 3,
        PFXK_FLATTEN_GENERAL = 1 << 4, PFXK_FLATTEN_FAST_DIV = 1 << 5, PFXK_FLATTEN_REGION = 1 << 6, PFXK_FLATTEN_PREVIEW = 1 << 7, PFXK_FLATTEN_CHUNK_START = 1 << 8 };
+typedef struct pfxk_flatten_plan {
+    int kernel, path;
+    int general, fast_div;   // _TEMPLATE: flatten_kernel<GENERAL, F>
+    int px, nb;              // _STREAM: flatten_stream_kernel<PX, NB>; _DLE: flatten_dle_kernel<PX, ring, 1, NB>; _SRT: flatten_srt_kernel<PX> (nb 0)
+    int ring;                // _DLE: RING_LOG2
+    int diag;                // _SRT: 0, or the diagnostic build `stats` asks for: 2 = the load stream without the arithmetic, 4 = per-phase wave clocks
+    uint32_t grid;           // _TEMPLATE, _STREAM: workgroups of 256 lanes
+    uint32_t waves;          // _DLE, _SRT: one-wave workgroups, sched.wavesA + sched.wavesB + what the units left over need
+    uint32_t stats;          // _DLE, _SRT: pfxk_dle_cands.stats (pfx_tune "dle_stats")
+    pfxk_dle_sched sched;    // _DLE, _SRT
+    pfxk_dle_plan redeal;    // _SRT
+} pfxk_flatten_plan;
+// launches what *plan says; the chunk-activity pre-pass of a GENERAL launch runs first unless the caller filled d_chunk_active itself
+hipError_t pfxk_flatten(hipStream_t stream, const pfxk_flatten_plan* plan, const pfxk_layer_desc* d_layers, uint32_t n_layers, const float* d_adj_table,
+                        uint8_t* d_chunk_active, int chunk_active_ready, uint32_t w, uint32_t h, uint8_t* d_dst, const pfxk_preview* preview /* may be NULL */,
+                        const pfxk_region* region /* may be NULL */, const pfxk_dle_cands* cands /* read by _DLE and _SRT */,
+                        const uint8_t* d_chunk_start /* may be NULL: per-chunk first layer that can show (pfxk_chunk_start) */);
 // per-chunk alpha summary of a stored layer (bit 0: all 255, bit 1: none 0) over the chunk rectangle [cx0, cx0+ncx) x [cy0, cy0+ncy), and the
 // per-chunk start table of a stack (want[k]: 1 = Normal at opacity >= 1 needs bit 0, 2 = Overwrite needs bit 1, 0 = layer k never resets)
 hipError_t pfxk_chunk_alpha_flags(hipStream_t s, const uint8_t* d_px, uint32_t w, uint32_t h, uint32_t cx0, uint32_t cy0, uint32_t ncx, uint32_t ncy,
                                   uint8_t* d_flags);
 hipError_t pfxk_chunk_start(hipStream_t s, const uint8_t* const* d_flag_ptrs, const uint8_t* d_want, uint32_t n_layers, uint32_t n_chunks,
                             uint8_t* d_start, uint32_t* useful_pinned /* may be NULL: receives `tag` if any chunk starts above layer 0 */, uint32_t tag);
-void       pfxk_flatten_set_dle(int units_per_wave /* 0 = default, < 0 = keep */, int ring_log2 /* 10 | 11, else keep */);
 /* samples 256 units against the topmost reset candidate; *verdict_pinned = tag | 0x80000000 when at least half start at it outright (k_flatten.hip: dle_probe_kernel) */
 hipError_t pfxk_dle_probe(hipStream_t s, const pfxk_layer_desc* d_layers, uint32_t cand_layer, uint32_t cand_kind, uint32_t n_px, uint32_t* verdict_pinned, uint32_t tag);
 hipError_t pfxk_flatten_dle_stats(unsigned long long* out16 /* may be NULL */, int reset); // synchronises the device
-void       pfxk_flatten_set_dle_dev(int stats_on /* < 0 keep */, int cfg /* < 0 keep */);
-void       pfxk_flatten_set_dle_sched(int sched /* 0 equal streams, 1 shrinking */, int fracA, int fracB); // < 0 keeps
-void       pfxk_flatten_set_dle_plan(int kernel /* 0 class sorting, 1 round-3 kernel; < 0 keeps */, int s1 /* first re-deal attempt, layers above the topmost candidate: -1 = 1, 0 = never; < -1 keeps */,
-                                     int s2 /* layers between attempts: -1 = 3, 0 = one attempt only; < -1 keeps */);
 // out[0] += byte values for which a typed UNORM8 store of RN(k / 255) does not write k or the typed load does not return RN(k / 255)
 hipError_t pfxk_unorm_store_check(hipStream_t s, uint8_t* d_scratch1k, unsigned long long* d_out);
-void       pfxk_flatten_set_variant(int v); // tuning knob: 0 = shipped kernel, 1.. = experimental pixels-per-lane / occupancy variants
 // counts (into *d_out) operand pairs for which the shared-reciprocal division differs from the IEEE divide
 hipError_t pfxk_rdiv_check(hipStream_t s, uint64_t seed, uint32_t blocks, uint32_t iters, unsigned long long* d_out);
 // the same count with explicit biased-exponent ranges [lo, hi] (1 .. 254) for numerator and denominator (k_effects2.hip); a quarter of the numerators are 0

@@ -33,7 +33,7 @@ LATTICE = (256, 256)
 # pfx_int_flatten_last_path (pfx_internal.h)
 K_TEMPLATE, K_STREAM, K_DLE, K_SRT = 0, 1, 2, 3
 P_GENERAL, P_FAST, P_REGION, P_PREVIEW, P_CHUNK_START = 1 << 4, 1 << 5, 1 << 6, 1 << 7, 1 << 8
-FAST_DIV_MIN = float(f32(2.0) ** -40)   # pfx_api.cpp: opacity_allows_fast_div
+FAST_DIV_MIN = float(f32(2.0) ** -40)   # pfx_internal.h: opacity_allows_fast_div
 
 
 def below(x):
@@ -72,7 +72,7 @@ def is_adj(L):
 
 
 def fast_div(layers):
-    """pfx_api.cpp: every layer of the call counts, hidden and adjustment layers too; NaN fails the comparison"""
+    """pfx_flatten.cpp: every layer of the call counts, hidden and adjustment layers too; NaN fails the comparison"""
     return all(f32(L.get("opacity", 1.0)) >= f32(FAST_DIV_MIN) for L in layers)
 
 
@@ -99,7 +99,8 @@ class Case:
     def path(self):
         """(value, mask) the launch-path seam must show after this composite, from the rule the host code documents: a preview, a rectangle, a live mask or
         an adjustment layer needs flatten_kernel<true, F>; a raster-only stack with an opacity below 2^-40 (or NaN) flatten_kernel<false, false>; every other
-        stack one of the fast kernels (which one depends on depth, candidates and verdicts: only `not the template` is fixed here)"""
+        stack one of the fast kernels (which one depends on depth, candidates and verdicts: only `not the template` is fixed here; the choice among them and their shapes
+        are pinned at the plan seam: tests/test_flatten_dispatch_host.py, tests/test_gpu_flatten_plan.py)"""
         fast = P_FAST if fast_div(self.layers) else 0
         special = (P_PREVIEW if self.preview is not None else 0) | (P_REGION if self.region() else 0)
         n_desc = sum(1 for L in self.layers if L.get("visible", True) and (is_adj(L) or L.get("pixels") is not None))

@@ -279,7 +279,7 @@ def test_f_raster_only_off_the_fast_path(gpu, size):
 
 # ---- G: the editing session ------------------------------------------------------------------------------------------------------------------------------------------
 def start_table(layers):
-    """pfx_api.cpp: build_stack's chunk_meta and chunk_start_kernel on the mirror: (some layer above the bottom one may reset a chunk, some chunk does start above
+    """pfx_flatten.cpp: build_stack's chunk_meta and chunk_start_kernel on the mirror: (some layer above the bottom one may reset a chunk, some chunk does start above
     layer 0).  Normal at opacity >= 1 resets a chunk whose alpha is all 255, Overwrite one without an alpha 0; masked layers never"""
     desc = [L for L in layers if L.get("visible", True) and L.get("pixels") is not None]
     wanted = useful = False

@@ -229,7 +229,7 @@ def test_streaming_kernel_shapes_agree_with_the_oracle(gpu, n):
 @pytest.mark.parametrize("n", [4, 5, 6, 7, 9, 17])
 @pytest.mark.parametrize("cls", ["light", "medium", "heavy", "mixed"])
 def test_streaming_kernel_shape_by_mode_class(gpu, n, cls):
-    """the automatic shape (flatten_variant 0) follows the heaviest blend mode of the stack (pfx_api.cpp: build_stack -> pfxk_flatten mode_class): light and medium
+    """the automatic shape (flatten_variant 0) follows the heaviest blend mode of the stack (pfx_flatten.cpp: build_stack -> pfx_int_flatten_plan mode_class): light and medium
     stacks of 5+ layers run 4 pixels per lane (one tile per wave from 7 layers, grid-stride below / for medium), heavy ones and stacks of up to 4 layers 2 — every
     class at the depths where the rule switches, on a width that leaves a ragged last tile"""
     w, h = 397, 71

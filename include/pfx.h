@@ -1237,6 +1237,64 @@ int pfx_perspective_crop_dev(pfx_ctx* ctx, const float corners_xy[8], const void
 /* one layer through host buffers: cropped_bytes >= out_w * out_h * 4 of the plan */
 int pfx_perspective_crop(pfx_ctx* ctx, const float corners_xy[8], const uint8_t* layer, uint8_t* cropped, size_t cropped_bytes, uint32_t w, uint32_t h);
 
+/* ================= clone stamp, heal brush (live stroke), pencil (ref: src/ui/panels/tools/behavior/raster/clone_heal.rs) =================
+ * The three dab-list tools that write into the preview layer besides the brush: clone_stamp_circle / _line :6-132, heal_circle / _line :141-292,
+ * draw_pixel_and_get_bounds / draw_pixel_line_and_get_bounds :295-431.  A drag frame on the device is pfx_*_dev with that frame's points onto the resident
+ * preview, then pfx_flatten_preview_dev; the release is pfx_stroke_commit_dev (commit_bezier_to_layer / commit_eraser_to_layer, the kernel of pfx_brush_commit).
+ * The pointer-event smoothing of the callers is input handling: callers hand over the smoothed positions.  Smudge is not covered.
+ *   lines    pfx_stroke_line_points, the stepping of clone_stamp_line / heal_line: d = end - start, distance = sqrt(dx dx + dy dy); below 0.1 the start point
+ *            alone, with no canvas test; else steps = ceil(distance), t = i / steps for i in 0 ..= steps, p = start + d * t, kept only if x >= 0 && (x as u32) < w
+ *            and likewise y.  The single circle of a stroke's first event has no such test: callers put that point into the list themselves.
+ *            pfx_pencil_line_cells: Bresenham from floor(start) to floor(end) (err = dx - dy; e2 = 2 err; e2 > -dy steps x, e2 < dx steps y); only cells inside
+ *            the canvas are listed.  Both fill at most `capacity` entries and always return the full count in *n_out: a caller whose buffer was too small comes
+ *            back with room for *n_out.  PFX_ERR_INVALID: NULL n_out, a NULL list with a capacity, a non-finite coordinate, a bad size, a segment longer
+ *            than 2^24 steps (pencil: a coordinate beyond +-2^24).
+ *   shared   radius = size / 2.  Per dab the box is min = (c - radius).max(0) as u32, max = ((c + radius) as u32).min(dim - 1) with saturating casts (a dab left
+ *            of the canvas still tests column 0).  Per pixel of the box: a selection byte of 0 skips; dist = sqrt(dx dx + dy dy) with d = pixel - centre;
+ *            dist > radius skips.  Dabs apply in list order: `>=` below compares with the preview's current, quantised alpha byte.
+ *   clone    geom = compute_brush_alpha(dist, radius) (the brush's: hardness, anti_aliased), geom < 0.01 skips; sx = round(x + offset_x) as i32 (half away
+ *            from zero), sy likewise, a source outside the canvas skips; alpha = geom * (sa / 255.0); alpha >= old_a / 255.0 writes ((s / 255.0) * 255.0) as u8
+ *            per colour channel — which need not be s — and (alpha * 255.0) as u8.  A source alpha of 0 over an empty preview writes rgb under alpha 0.
+ *   heal     t = clamp(dist / radius, 0, 1), hard_t = clamp(hardness * 0.9 + 0.1, 0, 1); geom = 1 below hard_t, else s = (t - hard_t) / (1 - hard_t + 1e-6),
+ *            geom = 1 - s s (3 - 2 s); geom < 0.01 skips.  seed = x * 1619 + y * 3929 wrapping in u32, angle_offset = seed as f32 / 4294967296.0 * TAU; for i in
+ *            0..24: angle = angle_offset + (i as f32 / 24.0) * TAU, radii sample_radius * 0.75 then sample_radius: sx = round(x as f32 + cos(angle) * rr) as
+ *            i32, sy with sin; samples inside the canvas add r, g, b to f32 sums and 1 to count.  count < 1 skips; geom >= old_a / 255.0 writes (sum / count)
+ *            as u8 per channel and (geom * 255.0) as u8.
+ *   pencil   per listed cell inside the canvas whose selection byte is not 0: color[3] >= old_a / 255.0 writes (c * 255.0) as u8 four times.  Idempotent: a
+ *            cell listed twice is harmless.
+ *   dirty    optional output {x0, y0, x1, y1}: Rect::union (componentwise min / max) of the rects the reference returns per dab, (min - 1 saturating, min(max
+ *            + 2, dim)), computed on the host with the reference's float operations; zeros when nothing was listed.  A lone dab right of or below the canvas
+ *            gives the reference's inverted rect (x0 >= x1): empty.  The pencil's box is taken over the listed in-canvas cells WITHOUT the selection (the
+ *            device tier's selection lives on the device): it contains the reference's, and equals it without a selection.
+ * All arithmetic is single correctly rounded f32 operations in the reference's order, except cos / sin: the f64 routine rounded once, within one ulp of the
+ * reference's cosf / sinf, so that a heal pixel can differ only where a sample coordinate sits within that ulp of a rounding boundary.
+ * n_points / n_cells == 0 is a no-op with PFX_OK (sizes, descriptor and buffers are still checked).  Refused with PFX_ERR_INVALID before anything is launched
+ * and with nothing written: a NULL tool / colour, source, preview or list; a tool field, colour channel or point that is not finite; an RGBA8 device pointer
+ * that is not 4-byte aligned; a preview that overlaps the source or the selection (pfx_stroke_commit_dev: a layer that overlaps the preview or the selection);
+ * w * h outside the document limit. */
+typedef struct pfx_clone_stamp_tool { float size, hardness; int32_t anti_aliased; float offset_x, offset_y; } pfx_clone_stamp_tool;   /* properties + clone_stamp_state.offset */
+typedef struct pfx_heal_ring_tool { float size, hardness, sample_radius; } pfx_heal_ring_tool;                                       /* properties + content_aware_state */
+/* host only, no context */
+int pfx_stroke_line_points(float x0, float y0, float x1, float y1, uint32_t w, uint32_t h, float* points_xy, uint32_t capacity, uint32_t* n_out);
+int pfx_pencil_line_cells(float x0, float y0, float x1, float y1, uint32_t w, uint32_t h, int32_t* cells_xy, uint32_t capacity, uint32_t* n_out);
+/* source_dev, preview_dev: w * h RGBA8; sel_dev: w * h bytes or NULL; points_xy / cells_xy: host arrays of n pairs; asynchronous on the context's stream */
+int pfx_clone_stamp_dev(pfx_ctx* ctx, const pfx_clone_stamp_tool* tool, const void* source_dev, void* preview_dev, const void* sel_dev /* may be NULL */, uint32_t w,
+                        uint32_t h, const float* points_xy, uint32_t n_points, uint32_t dirty[4] /* may be NULL */);
+int pfx_heal_ring_dev(pfx_ctx* ctx, const pfx_heal_ring_tool* tool, const void* source_dev, void* preview_dev, const void* sel_dev /* may be NULL */, uint32_t w,
+                      uint32_t h, const float* points_xy, uint32_t n_points, uint32_t dirty[4] /* may be NULL */);
+int pfx_pencil_dev(pfx_ctx* ctx, const float color[4], void* preview_dev, const void* sel_dev /* may be NULL */, uint32_t w, uint32_t h, const int32_t* cells_xy,
+                   uint32_t n_cells, uint32_t dirty[4] /* may be NULL */);
+/* the same through host buffers: the preview is changed in place */
+int pfx_clone_stamp(pfx_ctx* ctx, const pfx_clone_stamp_tool* tool, const uint8_t* source, uint8_t* preview_inout, const uint8_t* sel /* may be NULL */, uint32_t w,
+                    uint32_t h, const float* points_xy, uint32_t n_points, uint32_t dirty[4] /* may be NULL */);
+int pfx_heal_ring(pfx_ctx* ctx, const pfx_heal_ring_tool* tool, const uint8_t* source, uint8_t* preview_inout, const uint8_t* sel /* may be NULL */, uint32_t w,
+                  uint32_t h, const float* points_xy, uint32_t n_points, uint32_t dirty[4] /* may be NULL */);
+int pfx_pencil(pfx_ctx* ctx, const float color[4], uint8_t* preview_inout, const uint8_t* sel /* may be NULL */, uint32_t w, uint32_t h, const int32_t* cells_xy,
+               uint32_t n_cells, uint32_t dirty[4] /* may be NULL */);
+/* the release of a stroke on device memory, the layer in place: what pfx_brush_commit does through host buffers (a blend_mode above 24 commits as Normal) */
+int pfx_stroke_commit_dev(pfx_ctx* ctx, void* active_layer_dev, const void* preview_dev, const void* sel_dev /* may be NULL */, uint32_t w, uint32_t h,
+                          uint8_t blend_mode, int is_eraser);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,14 @@ class Gradient(C.Structure):   # pfx_gradient
                 ("mode", C.c_int32), ("preview_scale", C.c_uint32)]
 
 
+class CloneStampTool(C.Structure):   # pfx_clone_stamp_tool
+    _fields_ = [("size", C.c_float), ("hardness", C.c_float), ("anti_aliased", C.c_int32), ("offset_x", C.c_float), ("offset_y", C.c_float)]
+
+
+class HealRingTool(C.Structure):   # pfx_heal_ring_tool
+    _fields_ = [("size", C.c_float), ("hardness", C.c_float), ("sample_radius", C.c_float)]
+
+
 _lib = None
 
 
@@ -189,5 +197,14 @@ def load() -> C.CDLL:
     lib.pfx_perspective_crop_plan.argtypes = [C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.pfx_perspective_crop_dev.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_uint32]
     lib.pfx_perspective_crop.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32]
+    _line = [C.c_float] * 4 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.pfx_stroke_line_points.argtypes = _line
+    lib.pfx_pencil_line_cells.argtypes = _line
+    _stroke = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]   # after the context and the tool
+    lib.pfx_clone_stamp_dev.argtypes = lib.pfx_clone_stamp.argtypes = [C.c_void_p, C.POINTER(CloneStampTool)] + _stroke
+    lib.pfx_heal_ring_dev.argtypes = lib.pfx_heal_ring.argtypes = [C.c_void_p, C.POINTER(HealRingTool)] + _stroke
+    lib.pfx_pencil_dev.argtypes = lib.pfx_pencil.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                             C.c_void_p]
+    lib.pfx_stroke_commit_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint8, C.c_int]
     _lib = lib
     return lib

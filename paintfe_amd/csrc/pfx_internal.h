@@ -299,6 +299,10 @@ extern "C" int pfx_int_textfx_span(float radius, int32_t dy);
 // for ceil(radius) above PFX_TEXT_FX_MAX_RADIUS, each before anything is launched; asynchronous (not in include/pfx.h)
 extern "C" int pfx_int_textfx_disc_dev(pfx_ctx* ctx, const void* src_plane, void* dst_plane, uint32_t w, uint32_t h, float radius, int take_min);
 
+// for the tests: the most chunk-list entries pfx_clone_stamp[_dev] / pfx_heal_ring[_dev] put into one launch (a longer stroke goes in consecutive pieces);
+// process-wide, 0 = back to the default (8 Mi); returns the previous value (not in include/pfx.h)
+extern "C" uint64_t pfx_int_dab_piece_entries(uint64_t entries);
+
 // blur_with_selection on device-resident images (pfx_api.cpp); mask_host may be NULL (= no selection)
 int pfx_int_blur_with_selection_dev(pfx_ctx* ctx, const void* d_src, void* d_dst, uint32_t w, uint32_t h, float sigma,
                                     const uint8_t* mask_host, const void* d_mask);

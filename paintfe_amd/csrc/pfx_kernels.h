@@ -516,6 +516,21 @@ hipError_t pfxk_gradient_apply(hipStream_t s, const uint32_t* d_lut, const uint8
 typedef struct pfxk_crop { float cx[4], cy[4]; uint32_t w, h, out_w, out_h, n_layers; } pfxk_crop;   // corners TL, TR, BR, BL
 hipError_t pfxk_perspective_crop(hipStream_t s, const uint8_t* const* d_layers, uint8_t* const* d_outs, const pfxk_crop* P);
 
+// ---- k_dabtools.hip ---- the clone stamp, the heal brush's live stroke and the pencil (src/ui/panels/tools/behavior/raster/clone_heal.rs); host side:
+// pfx_dabtools.cpp
+enum { PFXK_DAB_CLONE = 0, PFXK_DAB_HEAL = 1 };
+// what is uniform over a stroke: radius = size / 2; hard_t = clamp(hardness * 0.9 + 0.1, 0, 1) and hard_den = 1 - hard_t + 1e-6 (heal_circle :194, :198)
+typedef struct pfxk_dabtool { float radius, hardness, hard_t, hard_den, sample_radius, offset_x, offset_y; int32_t tool, anti_aliased; } pfxk_dabtool;
+// one dab after the host prologue: its centre and its pixel box [x0, x1] x [y0, y1] (:17-20, :149-152), 16-byte aligned: x0 > x1 = the dab touches no pixel
+typedef struct pfxk_dab { float cx, cy; uint32_t pad[2]; uint32_t x0, x1, y0, y1; } pfxk_dab;
+// the dabs dealt to the 64 x 64 chunks their boxes touch, as pfxk_brush_stamps_binned takes them: d_chunks = n_chunks x {chunk x, chunk y, first entry,
+// entries}, d_bins = dab indices in stroke order per chunk.  d_source is only read; it shares no byte with d_preview
+hipError_t pfxk_dab_stroke(hipStream_t s, const pfxk_dabtool* T, const uint8_t* d_source, uint8_t* d_preview, const uint8_t* d_sel, uint32_t w, uint32_t h,
+                           const pfxk_dab* d_dabs, const uint32_t* d_chunks, uint32_t n_chunks, const uint32_t* d_bins);
+// draw_pixel_and_get_bounds :295-367 for n cells (x, y pairs); a cell outside the canvas is skipped.  color: the four f32 channels
+hipError_t pfxk_pencil_cells(hipStream_t s, uint8_t* d_preview, const uint8_t* d_sel, uint32_t w, uint32_t h, const int32_t* d_cells, uint32_t n, float r, float g,
+                             float b, float a);
+
 #ifdef __cplusplus
 }
 #endif

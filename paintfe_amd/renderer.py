@@ -251,6 +251,38 @@ def gradient_drag_scale(w: int, h: int) -> int:
     return int(_lib.load().pfx_gradient_drag_scale(C.c_uint32(w), C.c_uint32(h)))
 
 
+def clone_stamp_tool(size: float, hardness: float, anti_aliased: bool = True, offset=(0.0, 0.0)) -> _lib.CloneStampTool:
+    """a pfx_clone_stamp_tool: the tool's properties and clone_stamp_state.offset (source = pixel + offset)"""
+    return _lib.CloneStampTool(float(size), float(hardness), int(bool(anti_aliased)), float(offset[0]), float(offset[1]))
+
+
+def heal_ring_tool(size: float, hardness: float, sample_radius: float) -> _lib.HealRingTool:
+    """a pfx_heal_ring_tool: the tool's properties and content_aware_state.sample_radius"""
+    return _lib.HealRingTool(float(size), float(hardness), float(sample_radius))
+
+
+def _line_list(fn, name, start, end, w, h, dtype):
+    n = C.c_uint32(0)
+    args = [C.c_float(start[0]), C.c_float(start[1]), C.c_float(end[0]), C.c_float(end[1]), C.c_uint32(w), C.c_uint32(h)]
+    st = fn(*args, None, C.c_uint32(0), C.byref(n))
+    out = np.empty((n.value, 2), dtype)
+    if st == _lib.OK and n.value:
+        st = fn(*args, _p(out), C.c_uint32(n.value), C.byref(n))
+    if st != _lib.OK:
+        raise PfxError(st, f"{name} refused its arguments")
+    return out
+
+
+def stroke_line_points(start, end, w: int, h: int) -> np.ndarray:
+    """pfx_stroke_line_points: the (n, 2) f32 dab centres clone_stamp_line / heal_line step through from start to end on a w x h canvas; host only"""
+    return _line_list(_lib.load().pfx_stroke_line_points, "pfx_stroke_line_points", start, end, w, h, np.float32)
+
+
+def pencil_line_cells(start, end, w: int, h: int) -> np.ndarray:
+    """pfx_pencil_line_cells: the (n, 2) i32 in-canvas cells of draw_pixel_line_and_get_bounds' Bresenham walk; host only"""
+    return _line_list(_lib.load().pfx_pencil_line_cells, "pfx_pencil_line_cells", start, end, w, h, np.int32)
+
+
 def _corners(corners):
     flat = [float(v) for c in corners for v in c]
     if len(flat) != 8:
@@ -1169,6 +1201,63 @@ class GpuRenderer:
         ins = (C.c_void_p * max(n, 1))(*[int(p) for p in layer_ptrs])
         outs = (C.c_void_p * max(n, 1))(*[int(p) for p in cropped_ptrs])
         self._check(self._lib.pfx_perspective_crop_dev(self._h, _corners(corners), ins, outs, C.c_uint32(n), C.c_uint32(w), C.c_uint32(h)))
+
+    # ---- clone stamp, heal brush (live stroke), pencil (pfx_clone_stamp*, pfx_heal_ring*, pfx_pencil*, pfx_stroke_commit_dev): `tool` is a clone_stamp_tool(...)
+    # or heal_ring_tool(...) descriptor, `points` (n, 2) dab centres, `cells` (n, 2) integer cells; each returns the dirty box (x0, y0, x1, y1) ----
+    def _dab_stroke(self, fn, tool, source, preview, points, selection):
+        src, out = _u8(source), _u8(preview).copy()
+        h, w = out.shape[:2]
+        sel = None if selection is None else _u8(selection)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
+        dirty = (C.c_uint32 * 4)()
+        self._check(fn(self._h, C.byref(tool), _p(src), _p(out), _p(sel), C.c_uint32(w), C.c_uint32(h), _p(pts), C.c_uint32(len(pts)), dirty))
+        return out, tuple(dirty)
+
+    def _dab_stroke_dev(self, fn, tool, source_ptr, preview_ptr, w, h, points, selection_ptr):
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
+        dirty = (C.c_uint32 * 4)()
+        self._check(fn(self._h, C.byref(tool), C.c_void_p(source_ptr), C.c_void_p(preview_ptr), C.c_void_p(selection_ptr or None), C.c_uint32(w), C.c_uint32(h), _p(pts),
+                       C.c_uint32(len(pts)), dirty))
+        return tuple(dirty)
+
+    def clone_stamp(self, tool, source, preview, points, selection=None):
+        """clone_stamp_circle for every point in order: (the preview (h, w, 4) with the dabs stamped from `source`, the dirty box)"""
+        return self._dab_stroke(self._lib.pfx_clone_stamp, tool, source, preview, points, selection)
+
+    def clone_stamp_dev(self, tool, source_ptr: int, preview_ptr: int, w: int, h: int, points, selection_ptr: int = 0):
+        """the same onto a device-resident preview in place (source, preview w * h RGBA8; selection w * h bytes); asynchronous; returns the dirty box"""
+        return self._dab_stroke_dev(self._lib.pfx_clone_stamp_dev, tool, source_ptr, preview_ptr, w, h, points, selection_ptr)
+
+    def heal_ring(self, tool, source, preview, points, selection=None):
+        """heal_circle for every point in order: (the preview with the ring averages of `source` written under the dabs, the dirty box)"""
+        return self._dab_stroke(self._lib.pfx_heal_ring, tool, source, preview, points, selection)
+
+    def heal_ring_dev(self, tool, source_ptr: int, preview_ptr: int, w: int, h: int, points, selection_ptr: int = 0):
+        """the same onto a device-resident preview in place; asynchronous; returns the dirty box"""
+        return self._dab_stroke_dev(self._lib.pfx_heal_ring_dev, tool, source_ptr, preview_ptr, w, h, points, selection_ptr)
+
+    def pencil(self, color, preview, cells, selection=None):
+        """draw_pixel_and_get_bounds for every cell: (the preview with `color` (four f32 channels) written, the dirty box of the in-canvas cells)"""
+        out = _u8(preview).copy()
+        h, w = out.shape[:2]
+        sel = None if selection is None else _u8(selection)
+        cl = np.ascontiguousarray(cells, np.int32).reshape(-1, 2)
+        dirty = (C.c_uint32 * 4)()
+        self._check(self._lib.pfx_pencil(self._h, _f4(color), _p(out), _p(sel), C.c_uint32(w), C.c_uint32(h), _p(cl), C.c_uint32(len(cl)), dirty))
+        return out, tuple(dirty)
+
+    def pencil_dev(self, color, preview_ptr: int, w: int, h: int, cells, selection_ptr: int = 0):
+        """the same onto a device-resident preview in place; asynchronous; returns the dirty box"""
+        cl = np.ascontiguousarray(cells, np.int32).reshape(-1, 2)
+        dirty = (C.c_uint32 * 4)()
+        self._check(self._lib.pfx_pencil_dev(self._h, _f4(color), C.c_void_p(preview_ptr), C.c_void_p(selection_ptr or None), C.c_uint32(w), C.c_uint32(h), _p(cl),
+                                             C.c_uint32(len(cl)), dirty))
+        return tuple(dirty)
+
+    def stroke_commit_dev(self, layer_ptr: int, preview_ptr: int, w: int, h: int, blend_mode: int = 0, is_eraser: bool = False, selection_ptr: int = 0):
+        """the release of a stroke: brush_commit on a device layer in place; asynchronous"""
+        self._check(self._lib.pfx_stroke_commit_dev(self._h, C.c_void_p(layer_ptr), C.c_void_p(preview_ptr), C.c_void_p(selection_ptr or None), C.c_uint32(w),
+                                                    C.c_uint32(h), C.c_uint8(blend_mode), C.c_int(int(is_eraser))))
 
     # ------------------------------------------------------------------ script front-end
     def resize_image(self, img, new_w: int, new_h: int, filter="bilinear"):   # transform.rs:347 (imageops::resize)

@@ -459,6 +459,30 @@ def main() -> int:
                          ("brush: dodge, diagonal stroke, size 100", r.make_brush(100.0, 0.75, True, (1, 1, 1, 1.0), mode=1), line((500, 500), (7000, 3800)))):
         timed(name, ["brush_stamps"], lambda: r.brush_stamps_dev(tgt.data_ptr(), w, h, b, pts), int(len(pts) * np.pi * (b.size / 2) ** 2), 0,
               "kernel only (the call adds the host prologue and the stamp upload, ~0.03-0.06 ms); Mpx_s = stamped pixel visits (a pixel stays in its lane's register across the stamps: no HBM figure); strokes of > 64 stamps are dealt to 64 x 64 chunks")
+    # ---------------- clone stamp, heal ring, release (k_dabtools.hip) on the same 8K preview, beside the brush's binned walk over the SAME dab list: the yardstick
+    # is the walk without a source gather.  px = stamped pixel visits as above.  The heal stroke at two steppings shows that the ring is evaluated per pixel, not
+    # per dab: halving the step doubles the walk and leaves the ring alone.  No time here is an acceptance criterion (profiles/dab_tools.md)
+    if not args.only or "dabtools" in args.only:
+        from paintfe_amd import clone_stamp_tool, heal_ring_tool
+        lay = torch.randint(0, 256, (h, w, 4), dtype=torch.uint8, device=dev, generator=g)
+        p0, p1 = (500.3, 700.2), (2499.3, 1100.7)
+        steps = {1.0: np.linspace(0.0, 1.0, 2000, dtype=np.float32), 0.5: np.linspace(0.0, 1.0, 3999, dtype=np.float32)}
+        strokes = {k: np.stack([p0[0] + (p1[0] - p0[0]) * t_, p0[1] + (p1[1] - p0[1]) * t_], axis=1) for k, t_ in steps.items()}
+        frame = strokes[1.0][1000:1016]
+        clone, heal = clone_stamp_tool(100.0, 0.75, True, (300.5, -200.5)), heal_ring_tool(100.0, 0.75, 30.0)
+        brush = r.make_brush(100.0, 0.75, True, (0.1, 0.2, 0.9, 1.0))
+        visits = lambda pts: int(len(pts) * np.pi * 50.0 ** 2)
+        note = "kernel only; the preview keeps the previous repetition's stroke, so every dab ties with what is there and writes again"
+        for label, pts in (("2000-dab stroke, stepping 1 px", strokes[1.0]), ("3999-dab stroke, stepping 0.5 px", strokes[0.5]), ("drag frame of 16 dabs", frame)):
+            timed(f"dabtools: clone stamp, size 100, {label}", ["clone_stamp"], lambda: r.clone_stamp_dev(clone, lay.data_ptr(), tgt.data_ptr(), w, h, pts), visits(pts), 0, note)
+            timed(f"dabtools: heal ring, size 100, sample_radius 30, {label}", ["heal_ring"], lambda: r.heal_ring_dev(heal, lay.data_ptr(), tgt.data_ptr(), w, h, pts), visits(pts), 0,
+                  note + "; 24 f64 cos + sin and 48 gathers per written pixel, once")
+            timed(f"dabtools yardstick: brush, size 100, {label}", ["brush_stamps"], lambda: r.brush_stamps_dev(tgt.data_ptr(), w, h, brush, pts), visits(pts), 0,
+                  "the same dab list through pfx_brush_stamps_ex_dev (binned above 64 stamps): the walk without a source")
+        timed("dabtools: stroke commit (release), Normal, 8K", ["stroke_commit"], lambda: r.stroke_commit_dev(lay.data_ptr(), tgt.data_ptr(), w, h), w * h, 4,
+              "pfxk_brush_commit on device memory: the preview is read everywhere (4 B/px, and one 8K frame stays in the Infinity Cache between repetitions); "
+              "the layer is read and written only under the stroke")
+        del lay
     del tgt
 
     # ---------------- 16K (config 4: mesh warp 6x6 Catmull-Rom + liquify displacement)

@@ -1295,6 +1295,64 @@ int pfx_pencil(pfx_ctx* ctx, const float color[4], uint8_t* preview_inout, const
 int pfx_stroke_commit_dev(pfx_ctx* ctx, void* active_layer_dev, const void* preview_dev, const void* sel_dev /* may be NULL */, uint32_t w, uint32_t h,
                           uint8_t blend_mode, int is_eraser);
 
+/* ================= line / curve tool (ref: src/ui/panels/tools/behavior/raster/bezier_math.rs, bezier_commit.rs) =================
+ * rasterize_bezier :76-286 redraws a cubic Bezier on every pointer event: 20 to 5000 anti-aliased dots at a spacing of a tenth of the size, then up to two
+ * arrowheads.  A drag frame on the device is pfx_line_render_dev onto the resident preview, then pfx_flatten_preview_dev with the tool's blend mode; the release
+ * is pfx_stroke_commit_dev, and in mask-edit mode pfx_stroke_commit_mask_dev (commit_preview_to_layer_mask, bezier_commit.rs:229-295) on the w * h conceal bytes
+ * that pfx_layer_set_mask takes.  Out of scope: showing a mask-target preview in the compositor (preview_targets_mask), the handle overlay, Shift-snapping and
+ * the tool's stage machine, which are UI.
+ *   bounds   get_bezier_bounds :41-73: min / max of the four control points, padded by size / 2 + 2, plus max(3 size, 8) + max(1.5 size, 4) with an Arrow end
+ *            shape, clamped to [0, w] x [0, h]; four floats {min_x, min_y, max_x, max_y}, as the reference returns them.
+ *   clear    last_bounds NULL: the whole preview is cleared.  Else min = floor(b.min).max(0) as u32, max = ceil(b.max).min(dim) as u32 and
+ *            TiledImage::clear_region: every 64 x 64 chunk with cx in min_x / 64 .. ceil_div(max_x, 64), likewise cy, is cleared — whole chunks, not a
+ *            rectangle.  Pixels of other chunks stay as they were, stale ones of an earlier frame included.
+ *   dots     spacing = max(0.1 size, 0.5); steps = clamp(ceil((control net + chord) / spacing) as usize, 20, 5000); for i in 0 ..= steps: t = i / steps, the
+ *            point of :27-38, the running f32 length over ALL samples; kept if x >= 0 && y >= 0 && (x as u32) < w && (y as u32) < h (saturating casts); a
+ *            pattern (Dotted: on 0.5 size, off 1.5 size; Dashed: on 2 size, off 1.5 size) keeps it if length % (on + off) < on (fmodf; a NaN compares false);
+ *            with a selection the byte AT THE DOT'S OWN CELL (x as u32, y as u32) must not be 0; Flat caps drop i == 0 and i == steps.
+ *            Vec2::length is taken to be emath's x.hypot(y): that is a recollection, not verified against emath's source.  It enters `steps` and a pattern's
+ *            phase only, never a pixel's arithmetic.
+ *   dot      draw_bezier_circle_with_hardness :456-526, hardness 0.95: radius = size / 2, aa_pad = 1.5 below radius 1.5, else max(0.05 radius, 2) + 2 (1 without
+ *            AA); box min = (c - outer).max(0) as u32, max = (ceil(c + outer) as u32).min(dim - 1).  Per pixel: a selection byte of 0 skips; d = pixel - centre
+ *            (no half-pixel offset), dist = sqrt(dx dx + dy dy); compute_line_alpha (brush_render.rs:85-133: three regimes, radius < 1.5, < 3, else; without AA
+ *            dist < radius); alpha <= 0 skips; pixel_alpha = alpha * (a / 255.0); written iff pixel_alpha > old_a / 255.0: ((c / 255.0) * 255.0) as u8 per colour
+ *            channel — which need not be c — and (pixel_alpha * 255.0) as u8.
+ *   arrows   :212-284, End first, then Start, after all dots: tangents 3 (p3 - p2) and 3 (p1 - p0), length floored at 0.001, tip advanced by 1.5 size, length
+ *            max(3 size, 8), half width max(1.5 size, 4).  draw_filled_triangle :289-373: box padded by 1, pixel centres at + 0.5, three edge distances times
+ *            the winding sign (a cross product of 0 counts as positive), min_dist < -1 skips, full alpha at >= 1, else smoothstep of (min_dist + 1) / 2; the
+ *            same strict `>` write rule.
+ *   plan     pfx_line_plan lists the dots after the canvas test, the pattern and the Flat-cap rule but BEFORE the selection test, and the triangles in draw
+ *            order (tip, wing1, wing2 each; triangles_xy and n_triangles may be NULL).  It fills at most `capacity` dots and always reports the full count.
+ *   mask     pfx_stroke_commit_mask[_dev]: per pixel whose selection byte is not 0 and whose preview alpha s is not 0: reveal ? old (255 - s) / 255 :
+ *            old + (255 - old) s / 255, integer divisions.
+ * All arithmetic is single correctly rounded f32 operations in the reference's order; no libm call per pixel: the result equals the reference's bit for bit.
+ * Control points far outside the canvas are legal: the saturating casts and NaN rules above decide what is drawn, which may be nothing.
+ * Refused with PFX_ERR_INVALID before anything is launched and with nothing written: a NULL tool, preview or mask; a control point or a size that is not
+ * finite (any finite size is taken, as by the clone stamp); an enum out of range; a last_bounds value that is not finite; an RGBA8 device pointer that is not
+ * 4-byte aligned; a preview that overlaps the selection or the mask; w * h outside the document limit. */
+typedef struct pfx_line_tool {
+    float    p[8];        /* control points p0..p3, canvas pixels */
+    float    size;        /* properties.size */
+    uint8_t  color[4];    /* Color32 */
+    int32_t  pattern;     /* 0 solid, 1 dotted, 2 dashed   (LinePattern) */
+    int32_t  cap_style;   /* 0 round, 1 flat               (CapStyle) */
+    int32_t  end_shape;   /* 0 none, 1 arrow               (LineEndShape) */
+    int32_t  arrow_side;  /* 0 end, 1 start, 2 both        (ArrowSide) */
+    int32_t  anti_alias;
+} pfx_line_tool;
+/* host only, no context */
+int pfx_line_bounds(const pfx_line_tool* tool, uint32_t w, uint32_t h, float bounds[4]);
+int pfx_line_plan(const pfx_line_tool* tool, uint32_t w, uint32_t h, float* dots_xy, uint32_t capacity, uint32_t* n_out, float triangles_xy[12] /* may be NULL */,
+                  uint32_t* n_triangles /* may be NULL */);
+/* preview_dev: w * h RGBA8, changed in place; sel_dev: w * h bytes or NULL; asynchronous on the context's stream */
+int pfx_line_render_dev(pfx_ctx* ctx, const pfx_line_tool* tool, void* preview_dev, const void* sel_dev /* may be NULL */, uint32_t w, uint32_t h,
+                        const float last_bounds[4] /* NULL: first frame, clear all */, float bounds_out[4] /* may be NULL */);
+int pfx_line_render(pfx_ctx* ctx, const pfx_line_tool* tool, uint8_t* preview_inout, const uint8_t* sel /* may be NULL */, uint32_t w, uint32_t h,
+                    const float last_bounds[4] /* NULL: first frame, clear all */, float bounds_out[4] /* may be NULL */);
+/* conceal: w * h bytes, changed in place */
+int pfx_stroke_commit_mask_dev(pfx_ctx* ctx, void* conceal_dev, const void* preview_dev, const void* sel_dev /* may be NULL */, uint32_t w, uint32_t h, int reveal);
+int pfx_stroke_commit_mask(pfx_ctx* ctx, uint8_t* conceal_inout, const uint8_t* preview, const uint8_t* sel /* may be NULL */, uint32_t w, uint32_t h, int reveal);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,11 @@ class HealRingTool(C.Structure):   # pfx_heal_ring_tool
     _fields_ = [("size", C.c_float), ("hardness", C.c_float), ("sample_radius", C.c_float)]
 
 
+class LineTool(C.Structure):   # pfx_line_tool
+    _fields_ = [("p", C.c_float * 8), ("size", C.c_float), ("color", C.c_uint8 * 4), ("pattern", C.c_int32), ("cap_style", C.c_int32), ("end_shape", C.c_int32),
+                ("arrow_side", C.c_int32), ("anti_alias", C.c_int32)]
+
+
 _lib = None
 
 
@@ -206,5 +211,10 @@ def load() -> C.CDLL:
     lib.pfx_pencil_dev.argtypes = lib.pfx_pencil.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
                                                              C.c_void_p]
     lib.pfx_stroke_commit_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint8, C.c_int]
+    lib.pfx_line_bounds.argtypes = [C.POINTER(LineTool), C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
+    lib.pfx_line_plan.argtypes = [C.POINTER(LineTool), C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
+    lib.pfx_line_render_dev.argtypes = lib.pfx_line_render.argtypes = [C.c_void_p, C.POINTER(LineTool), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float),
+                                                                       C.POINTER(C.c_float)]
+    lib.pfx_stroke_commit_mask_dev.argtypes = lib.pfx_stroke_commit_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]
     _lib = lib
     return lib

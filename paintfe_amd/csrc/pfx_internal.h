@@ -302,6 +302,8 @@ extern "C" int pfx_int_textfx_disc_dev(pfx_ctx* ctx, const void* src_plane, void
 // for the tests: the most chunk-list entries pfx_clone_stamp[_dev] / pfx_heal_ring[_dev] put into one launch (a longer stroke goes in consecutive pieces);
 // process-wide, 0 = back to the default (8 Mi); returns the previous value (not in include/pfx.h)
 extern "C" uint64_t pfx_int_dab_piece_entries(uint64_t entries);
+// the same for pfx_line_render[_dev]'s dots (pfx_linetool.cpp): the clear rides with the first piece, the arrowheads with the last
+extern "C" uint64_t pfx_int_line_piece_entries(uint64_t entries);
 
 // blur_with_selection on device-resident images (pfx_api.cpp); mask_host may be NULL (= no selection)
 int pfx_int_blur_with_selection_dev(pfx_ctx* ctx, const void* d_src, void* d_dst, uint32_t w, uint32_t h, float sigma,

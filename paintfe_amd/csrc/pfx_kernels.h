@@ -531,6 +531,23 @@ hipError_t pfxk_dab_stroke(hipStream_t s, const pfxk_dabtool* T, const uint8_t* 
 hipError_t pfxk_pencil_cells(hipStream_t s, uint8_t* d_preview, const uint8_t* d_sel, uint32_t w, uint32_t h, const int32_t* d_cells, uint32_t n, float r, float g,
                              float b, float a);
 
+// ---- k_linetool.hip ---- the line / curve tool's rasteriser (src/ui/panels/tools/behavior/raster/bezier_math.rs:76-526) and the mask-target release
+// (bezier_commit.rs:229-295); host side: pfx_linetool.cpp
+// one arrowhead after the host prologue (draw_filled_triangle :304-328): vertex k is (vx[k], vy[k]) in draw order a, b, c; edge k runs from vertex k to vertex
+// (k + 1) % 3 with e = v1 - v0 and len = sqrt(ex ex + ey ey).max(0.001); sign = the winding; the pixel box [x0, x1] x [y0, y1], x0 > x1 = no pixel
+typedef struct pfxk_line_tri { float vx[3], vy[3], ex[3], ey[3], len[3], sign; uint32_t x0, x1, y0, y1; } pfxk_line_tri;
+// what is uniform over a call: compute_line_alpha's (effective_radius, fade_width, solid_radius) of the radius (brush_render.rs:103-118), the radius itself
+// for the non-AA `dist < radius`, src_a = color.a / 255.0, rgb = the three colour bytes after their round trip ((c / 255.0) * 255.0) as u8, alpha byte 0
+typedef struct pfxk_line { float radius, eff_radius, fade_width, solid_radius, src_a; uint32_t rgb; int32_t anti_alias; uint32_t n_tris; pfxk_line_tri tri[2]; } pfxk_line;
+// one dot: its centre, the cell (fx as u32, fy as u32) whose selection byte gates the whole dot, its pixel box (:482-485); the layout of pfxk_dab
+typedef struct pfxk_line_dot { float cx, cy; uint32_t cell_x, cell_y; uint32_t x0, x1, y0, y1; } pfxk_line_dot;
+// a chunk of the launch: d_chunks = n_chunks x {chunk x, chunk y, first entry, entries, flags, 0, 0, 0} (two uint4), d_bins = dot indices per chunk
+enum { PFXK_LINE_CLEAR = 1, PFXK_LINE_TRI0 = 2, PFXK_LINE_TRI1 = 4 };   // flags: the chunk starts from 0, not from the preview; triangle k's box touches it
+hipError_t pfxk_line_render(hipStream_t s, const pfxk_line* L, uint8_t* d_preview, const uint8_t* d_sel, uint32_t w, uint32_t h, const pfxk_line_dot* d_dots,
+                            const uint32_t* d_chunks, uint32_t n_chunks, const uint32_t* d_bins);
+// commit_preview_to_layer_mask: conceal bytes in place from the preview's alpha; reveal: old (255 - s) / 255, else old + (255 - old) s / 255
+hipError_t pfxk_line_commit_mask(hipStream_t s, uint8_t* d_conceal, const uint8_t* d_preview, const uint8_t* d_sel, uint32_t w, uint32_t h, int reveal);
+
 #ifdef __cplusplus
 }
 #endif

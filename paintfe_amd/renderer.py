@@ -283,6 +283,43 @@ def pencil_line_cells(start, end, w: int, h: int) -> np.ndarray:
     return _line_list(_lib.load().pfx_pencil_line_cells, "pfx_pencil_line_cells", start, end, w, h, np.int32)
 
 
+LINE_PATTERNS = ["solid", "dotted", "dashed"]     # LinePattern
+LINE_CAPS = ["round", "flat"]                     # CapStyle
+LINE_END_SHAPES = ["none", "arrow"]               # LineEndShape
+LINE_ARROW_SIDES = ["end", "start", "both"]       # ArrowSide
+
+
+def line_tool(points, size: float, color, pattern="solid", cap_style="round", end_shape="none", arrow_side="end", anti_alias: bool = True) -> _lib.LineTool:
+    """a pfx_line_tool: the four control points p0..p3 in canvas pixels, properties.size, the Color32 and the line options (names or their numbers)"""
+    flat = [float(v) for p in points for v in p]
+    if len(flat) != 8:
+        raise ValueError("points are four (x, y) pairs: p0, p1, p2, p3")
+    return _lib.LineTool((C.c_float * 8)(*flat), float(size), (C.c_uint8 * 4)(*[int(c) for c in color]), _enum(LINE_PATTERNS, pattern), _enum(LINE_CAPS, cap_style),
+                         _enum(LINE_END_SHAPES, end_shape), _enum(LINE_ARROW_SIDES, arrow_side), int(bool(anti_alias)))
+
+
+def line_bounds(tool, w: int, h: int):
+    """pfx_line_bounds: get_bezier_bounds as four f32 (min_x, min_y, max_x, max_y); host only"""
+    out = (C.c_float * 4)()
+    st = _lib.load().pfx_line_bounds(C.byref(tool), C.c_uint32(w), C.c_uint32(h), out)
+    if st != _lib.OK:
+        raise PfxError(st, "pfx_line_bounds refused its arguments")
+    return np.array(out, np.float32)
+
+
+def line_plan(tool, w: int, h: int):
+    """pfx_line_plan: ((n, 2) f32 dot centres after the canvas test, the pattern and the cap rule but before the selection test, (k, 3, 2) f32 arrowheads in
+    draw order, each tip, wing1, wing2); host only"""
+    lib, n, nt, tri = _lib.load(), C.c_uint32(0), C.c_uint32(0), (C.c_float * 12)()
+    st = lib.pfx_line_plan(C.byref(tool), C.c_uint32(w), C.c_uint32(h), None, C.c_uint32(0), C.byref(n), tri, C.byref(nt))
+    dots = np.empty((n.value, 2), np.float32)
+    if st == _lib.OK and n.value:
+        st = lib.pfx_line_plan(C.byref(tool), C.c_uint32(w), C.c_uint32(h), _p(dots), C.c_uint32(n.value), C.byref(n), tri, C.byref(nt))
+    if st != _lib.OK:
+        raise PfxError(st, "pfx_line_plan refused its arguments")
+    return dots, np.array(tri, np.float32)[:6 * nt.value].reshape(nt.value, 3, 2)
+
+
 def _corners(corners):
     flat = [float(v) for c in corners for v in c]
     if len(flat) != 8:
@@ -1258,6 +1295,44 @@ class GpuRenderer:
         """the release of a stroke: brush_commit on a device layer in place; asynchronous"""
         self._check(self._lib.pfx_stroke_commit_dev(self._h, C.c_void_p(layer_ptr), C.c_void_p(preview_ptr), C.c_void_p(selection_ptr or None), C.c_uint32(w),
                                                     C.c_uint32(h), C.c_uint8(blend_mode), C.c_int(int(is_eraser))))
+
+    # ---- line / curve tool (pfx_line_render*, pfx_stroke_commit_mask*): `tool` is a line_tool(...) descriptor, `last_bounds` the four floats the previous
+    # frame returned (None: first frame, the whole preview is cleared); each render returns this frame's bounds ----
+    line_bounds = staticmethod(line_bounds)
+    line_plan = staticmethod(line_plan)
+
+    @staticmethod
+    def _bounds4(last_bounds):
+        return None if last_bounds is None else (C.c_float * 4)(*[float(v) for v in last_bounds])
+
+    def line_render(self, tool, preview, last_bounds=None, selection=None):
+        """rasterize_bezier onto a copy of the preview (h, w, 4): (the preview, the frame's bounds as four f32)"""
+        out = _u8(preview).copy()
+        h, w = out.shape[:2]
+        sel = None if selection is None else _u8(selection)
+        bounds = (C.c_float * 4)()
+        self._check(self._lib.pfx_line_render(self._h, C.byref(tool), _p(out), _p(sel), C.c_uint32(w), C.c_uint32(h), self._bounds4(last_bounds), bounds))
+        return out, np.array(bounds, np.float32)
+
+    def line_render_dev(self, tool, preview_ptr: int, w: int, h: int, last_bounds=None, selection_ptr: int = 0):
+        """the same onto a device-resident preview in place (w * h RGBA8; selection w * h bytes); asynchronous; returns the frame's bounds"""
+        bounds = (C.c_float * 4)()
+        self._check(self._lib.pfx_line_render_dev(self._h, C.byref(tool), C.c_void_p(preview_ptr), C.c_void_p(selection_ptr or None), C.c_uint32(w), C.c_uint32(h),
+                                                  self._bounds4(last_bounds), bounds))
+        return np.array(bounds, np.float32)
+
+    def stroke_commit_mask(self, conceal, preview, reveal: bool = False, selection=None):
+        """commit_preview_to_layer_mask: the (h, w) conceal bytes with the preview's alpha committed (reveal: the mask eraser)"""
+        out, pv = _u8(conceal).copy(), _u8(preview)
+        h, w = pv.shape[:2]
+        sel = None if selection is None else _u8(selection)
+        self._check(self._lib.pfx_stroke_commit_mask(self._h, _p(out), _p(pv), _p(sel), C.c_uint32(w), C.c_uint32(h), C.c_int(int(bool(reveal)))))
+        return out
+
+    def stroke_commit_mask_dev(self, conceal_ptr: int, preview_ptr: int, w: int, h: int, reveal: bool = False, selection_ptr: int = 0):
+        """the same on device-resident conceal bytes in place; asynchronous"""
+        self._check(self._lib.pfx_stroke_commit_mask_dev(self._h, C.c_void_p(conceal_ptr), C.c_void_p(preview_ptr), C.c_void_p(selection_ptr or None), C.c_uint32(w),
+                                                         C.c_uint32(h), C.c_int(int(bool(reveal)))))
 
     # ------------------------------------------------------------------ script front-end
     def resize_image(self, img, new_w: int, new_h: int, filter="bilinear"):   # transform.rs:347 (imageops::resize)

@@ -485,6 +485,48 @@ def main() -> int:
         del lay
     del tgt
 
+    # ---------------- line / curve tool (k_linetool.hip): one drag frame of a 4K canvas diagonal — the focused clear with the frame's own bounds, the dots, the
+    # arrowheads — beside the brush's binned walk over the SAME number of stamps at the dots' places.  px = dot pixel visits (dots x the dot's box).  The note
+    # carries the dot count, the chunk-list entries and the call's wall-clock time, host prologue and uploads included.  No time is an acceptance criterion
+    # (profiles/line_tool.md)
+    if not args.only or "linetool" in args.only:
+        import time
+
+        from paintfe_amd import line_bounds, line_plan, line_tool
+        from tests import linetool_model as LM
+        lw, lh = 3840, 2160
+        pv = torch.zeros((lh, lw, 4), dtype=torch.uint8, device=dev)
+        p = [(40.5, 30.25), (1300.0, 700.0), (2500.0, 1500.0), (3800.5, 2130.75)]
+        for size in (1.0, 12.0, 60.0):
+            for label, opts in (("solid, arrows both", dict(end_shape="arrow", arrow_side="both")), ("dashed", dict(pattern="dashed"))):
+                tool = line_tool(p, size, (30, 90, 220, 255), **opts)
+                dots, tris = line_plan(tool, lw, lh)
+                boxes = [LM.dot_box(x, y, np.float32(size) / np.float32(2), True, lw, lh) for x, y in dots]
+                entries = sum((b[1] // 64 - b[0] // 64 + 1) * (b[3] // 64 - b[2] // 64 + 1) for b in boxes if b)
+                visits = sum((b[1] - b[0] + 1) * (b[3] - b[2] + 1) for b in boxes if b)
+                last = line_bounds(tool, lw, lh)
+                frame = lambda: r.line_render_dev(tool, pv.data_ptr(), lw, lh, last)
+                for _ in range(5):
+                    frame()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(20):
+                    frame()
+                    torch.cuda.synchronize()
+                wall = (time.perf_counter() - t0) / 20 * 1e3
+                timed(f"linetool: 4K diagonal drag frame, size {size:g}, {label}", ["line_render"], frame, visits, 0,
+                      f"kernel only; {len(dots)} dots, {len(tris)} arrowheads, {entries} chunk-list entries; the whole call, synchronised: {wall:.3f} ms")
+                nothing = (0.0, 0.0, 0.0, 0.0)   # bounds that clear no chunk: the dots and arrowheads alone, over the chunks they touch
+                timed(f"linetool: the same frame without a clear, size {size:g}, {label}", ["line_render"], lambda: r.line_render_dev(tool, pv.data_ptr(), lw, lh, nothing), visits, 0,
+                      "kernel only; the diagonal's bounds cover the canvas, so the frame above clears every chunk of it: the difference is that clear")
+                brush = r.make_brush(size, 0.95, True, (0.1, 0.35, 0.86, 1.0))
+                timed(f"linetool yardstick: brush, size {size:g}, the {len(dots)} stamps of '{label}'", ["brush_stamps"],
+                      lambda: r.brush_stamps_dev(pv.data_ptr(), lw, lh, brush, dots), visits, 0, "pfx_brush_stamps_ex_dev at the dots' places: no clear, no arrowheads")
+        conceal = torch.zeros((lh, lw), dtype=torch.uint8, device=dev)
+        timed("linetool: mask-target release, 4K", ["stroke_commit_mask"], lambda: r.stroke_commit_mask_dev(conceal.data_ptr(), pv.data_ptr(), lw, lh), lw * lh, 4,
+              "the preview's alpha is read everywhere; the conceal bytes are read and written only under the line")
+        del pv, conceal
+
     # ---------------- 16K (config 4: mesh warp 6x6 Catmull-Rom + liquify displacement)
     w, h = 15360, 8640
     px = w * h

@@ -21,10 +21,36 @@ enum : uint32_t {
 // computed once per denominator.  tests/test_gpu_parity.py::test_fast_division_matches_ieee checks 2^28 operand
 // pairs against `/` on the device; every golden / oracle parity test runs through this path.
 // (rdiv / rdiv_prepare / rdiv_apply live in k_common.h)
-template <bool FAST> PFX_DEV float fdiv(float n, float d)
+// RAW: the reciprocal without its Newton step (k_common.h: rdiv_prepare_raw), for a mode function whose operands are byte values only and for which
+// every (base, top) pair has been checked on the device (div_raw_rcp below)
+template <bool FAST, bool RAW = false> PFX_DEV float fdiv(float n, float d)
 {
-    if constexpr (FAST) return rdiv_apply(rdiv_prepare(d), n);
+    if constexpr (FAST && RAW) return rdiv_apply(rdiv_prepare_raw(d), n);
+    else if constexpr (FAST) return rdiv_apply(rdiv_prepare(d), n);
     else return n / d;
+}
+
+// ---- round 9: two shorter exact forms of the mode functions, one switch each for A/B (tools/build_variant.sh -DPFX_...=0; profiles/r09_tuning.md) ----
+#ifndef PFX_VIVID_SHORT
+#define PFX_VIVID_SHORT 1   // Vivid Light with one compare and two selects per channel: the arm is a sign s = +-1 carried through FMAs
+#endif
+#ifndef PFX_DIV_RAW_RCP
+#define PFX_DIV_RAW_RCP 1   // the mode functions' divisions on an unrefined v_rcp_f32, for the modes of PFX_DIV_RAW_MODES
+#endif
+// The mode functions divide byte-derived operands only: n and d are each one of a few hundred values, at most 65 536 pairs per mode, while the Newton
+// step of rdiv_prepare is there for 47 045 of 7e13 general significand pairs.  A mode's bit is set here only if tests/test_gpu_blend_allpairs.py passes
+// at tolerance 0 with it set: every (base, top) byte pair of every channel, through the class-sorting, streaming and general kernels.  (tools/lab/div_bytes.hip
+// compares the mode functions themselves with `/` on the device, pair by pair: 0 differences for all six on gfx950.)
+// Bit M = blend mode M; a build with -DPFX_DIV_RAW_MODES=0x2800f0 (all six) is the one that certifies them.  Divide (bit 19) stays on the refined
+// reciprocal: with it set, flatten_srt_kernel<3> spills ten more SGPRs and its static v_readlane reloads double, 57 -> 118 (profiles/r09_tuning.md).
+#ifndef PFX_DIV_RAW_MODES
+#define PFX_DIV_RAW_MODES 0x2000f0u
+#endif
+constexpr bool div_raw_rcp(uint32_t mode)
+{
+    constexpr uint32_t table = PFX_DIV_RAW_RCP ? (uint32_t)(PFX_DIV_RAW_MODES) : 0u;
+    constexpr uint32_t dividing = (1u << M_REFLECT) | (1u << M_GLOW) | (1u << M_COLOR_BURN) | (1u << M_COLOR_DODGE) | (1u << M_DIVIDE) | (1u << M_VIVID_LIGHT);
+    return ((table & dividing) >> mode) & 1u;
 }
 
 // ---- canvas_state.rs:1425-1505 ----
@@ -32,17 +58,17 @@ PFX_DEV float overlay_channel(float base, float top)
 {
     return (base < 0.5f) ? 2.0f * base * top : 1.0f - 2.0f * (1.0f - base) * (1.0f - top);
 }
-template <bool F> PFX_DEV float color_burn_channel(float base, float top)
+template <bool F, bool R = false> PFX_DEV float color_burn_channel(float base, float top)
 {
-    return (top == 0.0f) ? 0.0f : clamp01(1.0f - fdiv<F>(1.0f - base, top)); // 1 - q <= 1
+    return (top == 0.0f) ? 0.0f : clamp01(1.0f - fdiv<F, R>(1.0f - base, top)); // 1 - q <= 1
 }
-template <bool F> PFX_DEV float color_dodge_channel(float base, float top)
+template <bool F, bool R = false> PFX_DEV float color_dodge_channel(float base, float top)
 {
-    return (top >= 1.0f) ? 1.0f : clamp01(fdiv<F>(base, 1.0f - top)); // q >= 0
+    return (top >= 1.0f) ? 1.0f : clamp01(fdiv<F, R>(base, 1.0f - top)); // q >= 0
 }
-template <bool F> PFX_DEV float reflect_channel(float base, float top)
+template <bool F, bool R = false> PFX_DEV float reflect_channel(float base, float top)
 {
-    return (top >= 1.0f) ? 1.0f : clamp01(fdiv<F>(base * base, 1.0f - top));
+    return (top >= 1.0f) ? 1.0f : clamp01(fdiv<F, R>(base * base, 1.0f - top));
 }
 // v_max_f32 / v_min_f32 as ONE instruction: fmaxf / fminf make hipcc canonicalise both operands first (two more v_max x, x) because
 // it cannot prove that values read from memory are not signalling NaNs; the blend operands are bytes / 255.
@@ -101,39 +127,60 @@ PFX_DEV float soft_light_channel_lds(float base, float top)
     if (top <= 0.5f) return base - (1.0f - 2.0f * top) * base * (1.0f - base);
     return base + (2.0f * top - 1.0f) * (d - base);
 }
-template <bool F> PFX_DEV float divide_channel(float base, float top)
+template <bool F, bool R = false> PFX_DEV float divide_channel(float base, float top)
 {
-    return (top <= 0.0f) ? 1.0f : clamp01(fdiv<F>(base, top));
+    return (top <= 0.0f) ? 1.0f : clamp01(fdiv<F, R>(base, top));
 }
-template <bool F> PFX_DEV float vivid_light_channel(float base, float top)
+template <bool F, bool R = false> PFX_DEV float vivid_light_channel(float base, float top)
 {
     // canvas_state.rs:1479-1497.  Both branches divide; the operands are selected first so that a lane pays for one
     // division (the branch is per-lane data, so "both sides" is what a divergent wave would execute anyway).
+#if PFX_VIVID_SHORT
+    // The arm as a number: c = 0 on the burn arm (top <= 0.5), 1 on the dodge arm, s = 1 - 2c = +-1.  For base, top in [0, 1] every FMA below is
+    // the ONE rounding of the operation it stands for, because its other factor is +-1 or 2 and its addend 0 or +-1:
+    //   t2 = 2 top - c          burn: 2 top, exact.  dodge: 2 (top - 0.5) is exact for top > 0.5 (Sterbenz) and so is 2 top - 1: the same number
+    //   d  = s t2 + c           burn: t2.            dodge: RN(1 - t2)
+    //   n  = -s base + (1 - c)  burn: RN(1 - base).  dodge: base + 0 = base (base >= +0)
+    //   v  = -s q + (1 - c)     burn: RN(1 - q).     dodge: q + 0
+    // The rare sides, t2 <= 0 on the burn arm (-> 0) and t2 >= 1 on the dodge arm (-> 1), are both d <= 0 with result c; the quotient of such a lane
+    // (x / 0, x / negative) is discarded.  tests/test_blend_short_forms_host.py holds t2, d, n and the result to the form below, all 65 536 byte pairs.
+    const float c = (top <= 0.5f) ? 0.0f : 1.0f;
+    const float s = __builtin_fmaf(-2.0f, c, 1.0f), ic = 1.0f - c;
+    const float t2 = __builtin_fmaf(2.0f, top, -c);
+    const float d = __builtin_fmaf(s, t2, c);
+    const float n = __builtin_fmaf(-s, base, ic);
+    const float q = fdiv<F, R>(n, d);
+    const float v = clamp01(__builtin_fmaf(-s, q, ic));
+    return (d <= 0.0f) ? c : v;
+#else
     const bool lo = (top <= 0.5f);
     const float t2 = lo ? 2.0f * top : 2.0f * (top - 0.5f);
     const float n = lo ? 1.0f - base : base;
     const float d = lo ? t2 : 1.0f - t2;
-    const float q = fdiv<F>(n, d);
+    const float q = fdiv<F, R>(n, d);
     const float burn = (t2 <= 0.0f) ? 0.0f : clamp01(1.0f - q);
     const float dodge = (t2 >= 1.0f) ? 1.0f : clamp01(q);
     return lo ? burn : dodge;
+#endif
 }
 PFX_DEV float pin_light_channel(float base, float top)
 {
+    // (as one v_med3_f32 of base, 2 top - 1, 2 top: exact, 28 issue cycles per pixel shorter, and not faster by the A/B rule: profiles/r09_tuning.md)
     return (top <= 0.5f) ? vmin(base, 2.0f * top) : vmax(base, 2.0f * (top - 0.5f));
 }
 
 template <uint32_t M, bool F>
 PFX_DEV float blend_fn(float b, float t)
 {
+    constexpr bool R = div_raw_rcp(M);
     if constexpr (M == M_NORMAL) return t;
     else if constexpr (M == M_MULTIPLY) return b * t;
     else if constexpr (M == M_SCREEN) return 1.0f - (1.0f - b) * (1.0f - t);
     else if constexpr (M == M_ADDITIVE) return clamp01(b + t);               // min(b + t, 1), b + t >= 0
-    else if constexpr (M == M_REFLECT) return reflect_channel<F>(b, t);
-    else if constexpr (M == M_GLOW) return reflect_channel<F>(t, b);
-    else if constexpr (M == M_COLOR_BURN) return color_burn_channel<F>(b, t);
-    else if constexpr (M == M_COLOR_DODGE) return color_dodge_channel<F>(b, t);
+    else if constexpr (M == M_REFLECT) return reflect_channel<F, R>(b, t);
+    else if constexpr (M == M_GLOW) return reflect_channel<F, R>(t, b);
+    else if constexpr (M == M_COLOR_BURN) return color_burn_channel<F, R>(b, t);
+    else if constexpr (M == M_COLOR_DODGE) return color_dodge_channel<F, R>(b, t);
     else if constexpr (M == M_OVERLAY) return overlay_channel(b, t);
     else if constexpr (M == M_DIFFERENCE) return __builtin_fabsf(b - t);
     else if constexpr (M == M_NEGATION) return 1.0f - __builtin_fabsf(1.0f - b - t);
@@ -143,9 +190,9 @@ PFX_DEV float blend_fn(float b, float t)
     else if constexpr (M == M_SOFT_LIGHT) return soft_light_channel(b, t);
     else if constexpr (M == M_EXCLUSION) return b + t - 2.0f * b * t;
     else if constexpr (M == M_SUBTRACT) return clamp01(b - t);               // max(b - t, 0), b - t <= 1
-    else if constexpr (M == M_DIVIDE) return divide_channel<F>(b, t);
+    else if constexpr (M == M_DIVIDE) return divide_channel<F, R>(b, t);
     else if constexpr (M == M_LINEAR_BURN) return clamp01(b + t - 1.0f);
-    else if constexpr (M == M_VIVID_LIGHT) return vivid_light_channel<F>(b, t);
+    else if constexpr (M == M_VIVID_LIGHT) return vivid_light_channel<F, R>(b, t);
     else if constexpr (M == M_LINEAR_LIGHT) return clamp01(b + 2.0f * t - 1.0f);
     else if constexpr (M == M_PIN_LIGHT) return pin_light_channel(b, t);
     else if constexpr (M == M_HARD_MIX) return (b + t >= 1.0f) ? 1.0f : 0.0f;

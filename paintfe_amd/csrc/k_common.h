@@ -56,6 +56,9 @@ PFX_DEV rdiv rdiv_prepare(float d)
     const float e = __builtin_fmaf(-d, y0, 1.0f);
     return {d, __builtin_fmaf(e, y0, y0)};
 }
+// The reciprocal as the hardware gives it.  rdiv_apply on it is NOT correctly rounded in general (the 47045 pairs above); it is for a caller whose
+// operand pairs are few enough to have been checked one by one on the device (k_blend.h: div_raw_rcp).
+PFX_DEV rdiv rdiv_prepare_raw(float d) { return {d, __builtin_amdgcn_rcpf(d)}; }
 PFX_DEV float rdiv_apply(const rdiv k, float n)
 {
     const float q0 = n * k.y;

@@ -783,6 +783,19 @@ PFX_DEV void srt_layers(float (&acc)[PX][4], const pfxk_layer_desc* __restrict__
     }
 }
 
+// Cache policy of two request sites (round 10; the buffer intrinsics' last argument: 0 = default, 2 = nt), each measured alone and together against the parent
+// build, six alternations on one box, 8K x 32 layers (S2), 200-step windows: flatten 0.9620-0.9630 ms -> early loads nt 0.9533-0.9556, store nt 0.9587-0.9603,
+// both 0.9491-0.9516; the step 1.1063-1.1074 -> 1.0931-1.0962 ms.  Traffic, instruction counts and the kernel descriptor are unchanged; the load stream without
+// arithmetic is 1.1 % SLOWER under this policy, so what it buys is not bandwidth.  On the natural pass's loads nt, sc1 and sc0 sc1 cost 3-4 % and on the
+// candidate-alpha loads nt costs 1-2 % (the alpha request brings in the line the layer load then hits), so those sites keep the default policy and carry no macro;
+// PFX_EARLY_NB 4 and PFX_SRT_PIPE_PARTS 3 were measured again under this policy and are both slower (profiles/r10_tuning.md).
+#ifndef PFX_SRT_AUX_EARLY
+#define PFX_SRT_AUX_EARLY 2   // the early pass's typed xyzw loads (srt_early_pipe::fetch, its slot included; srt_early in the builds that run it)
+#endif
+#ifndef PFX_SRT_AUX_STORE
+#define PFX_SRT_AUX_STORE 2   // the class-sorting kernel's dword store of the result
+#endif
+
 // The early groups' pass (one pixel per lane, layers [lb, le) below the split): a set is four registers here, so NB sets keep NB - 1 layers in flight for the
 // price of two of the natural pass's.  The pass is short on arithmetic (a third of a natural step) and long on memory time — the group's lanes sit on a random
 // quarter of the unit's pixels, so every layer's load still touches all of the unit's cache lines — i.e. it is paced by how many loads a wave has in flight.
@@ -801,7 +814,7 @@ PFX_DEV void srt_early(float (&acc)[1][4], const pfxk_layer_desc* __restrict__ l
         constexpr int S = decltype(SET)::value;
         m[S] = nd.mode; o[S] = nd.adj_off;
         const pfx_v4i rs = make_rsrc_canonical(nd.pixels, bytes, PFX_RSRC_UNORM8X4);
-        const pfx_v4f v = pfx_buffer_load_format_v4f32(rs, voff, 0, 0);
+        const pfx_v4f v = pfx_buffer_load_format_v4f32(rs, voff, 0, PFX_SRT_AUX_EARLY);
         t[S][0][0] = v.x; t[S][0][1] = v.y; t[S][0][2] = v.z; t[S][0][3] = v.w;
         nptr += 1;
         nd = *nptr;
@@ -1005,7 +1018,7 @@ PFX_DEV void srt_early_pipe(float (&acc)[PX][4], float (&tn)[2][PX][4], const pf
         constexpr int S = decltype(SET)::value;
         m[S] = nd.mode; o[S] = nd.adj_off;
         const pfx_v4i rs = make_rsrc_canonical(nd.pixels, bytes, PFX_RSRC_UNORM8X4);
-        const pfx_v4f x = pfx_buffer_load_format_v4f32(rs, v, 0, 0);
+        const pfx_v4f x = pfx_buffer_load_format_v4f32(rs, v, 0, PFX_SRT_AUX_EARLY);
         t[S][0][0] = x.x; t[S][0][1] = x.y; t[S][0][2] = x.z; t[S][0][3] = x.w;
         nptr += 1;
         desc_read(nd, nptr);
@@ -1298,7 +1311,7 @@ __global__ __launch_bounds__(64) PFX_SRT_ATTR void flatten_srt_kernel(const pfxk
             uint32_t px = 0u;
 #pragma unroll
             for (int c = 0; c < 4; ++c) px = __builtin_amdgcn_cvt_pk_u8_f32(acc[j][c] * 255.0f, c, px);
-            pfx_buffer_store_i32((int)px, rs_dst, voff[j], 0, 0);
+            pfx_buffer_store_i32((int)px, rs_dst, voff[j], 0, PFX_SRT_AUX_STORE);
 #endif
         }
         if constexpr (TR) { const unsigned long long c = __builtin_amdgcn_s_memtime(); tph[3] += c - tc0; tc0 = c; }

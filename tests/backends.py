@@ -168,6 +168,14 @@ class GpuBackend:
     def adjust(self, img, op, params=(), lut=None, mask=None, sparse=0):
         return self.r.adjust(img, op, params, lut, mask, sparse)
 
+    def rhai_adjust_dev(self, ptr, w, h, op, params=()):
+        """pfx_rhai_adjust_dev: the Rhai flavour in place on a device image (the package wraps only the staged form)"""
+        import ctypes as C
+        from paintfe_amd.renderer import RHAI_OPS
+        arr = (C.c_float * max(len(params), 1))(*[float(x) for x in params])
+        self.r._check(self.r._lib.pfx_rhai_adjust_dev(self.r._h, C.c_void_p(ptr), C.c_uint32(w), C.c_uint32(h), C.c_int(RHAI_OPS.index(op)), arr,
+                                                      C.c_uint32(len(params))))
+
     def auto_levels(self, img, mask=None):
         return self.r.auto_levels(img, mask)
 

@@ -157,11 +157,31 @@ __global__ __launch_bounds__(TX* YG) void gauss_v_kernel(const float4* __restric
     }
 }
 
+constexpr size_t LDS_LIMIT = 160u * 1024u; // per workgroup
+
+size_t h_lds_bytes(int radius)
+{
+    const int h_entries = H_TILE + 2 * radius + H_SLACK;
+    return (size_t)(h_entries + (h_entries >> 2) + 1) * sizeof(float4);
+}
+
+// The vertical pass's tile shapes, by config index (pfxk_gauss_v_tile picks one; launch_v instantiates them from this table).
+struct v_tile { int tx, yg, rs; }; // columns, lanes per column (4 output rows each), LDS row stride in float4
+constexpr v_tile V_TILES[5] = {
+    {8, 32, 10},  // 0: 8 x 128, the shipped default.  Measured at 8K, sigma=16 (profiles/r01_tuning.md): 0.344 ms vs
+                  //    0.368 (8x256 rows), 0.350 (4x256), 0.446 (16x256)
+    {16, 64, 16}, // 1: 16 x 256
+    {4, 64, 5},   // 2: 4 x 256, the narrowest (LDS bound of the huge radii)
+    {8, 64, 10},  // 3: 8 x 256
+    {8, 128, 10}, // 4: 8 x 512
+};
+
+size_t v_lds_bytes(int rows, int rs, int radius) { return (size_t)(rows + 2 * radius + V_SLACK) * rs * sizeof(float4); }
+
 template <bool EXACT>
 hipError_t launch_h(hipStream_t stream, const uint8_t* d_src, float4* tmp, const float* wts, int radius, uint32_t w, uint32_t h)
 {
-    const int h_entries = H_TILE + 2 * radius + H_SLACK;
-    const size_t lds_h = (size_t)(h_entries + (h_entries >> 2) + 1) * sizeof(float4);
+    const size_t lds_h = h_lds_bytes(radius);
     hipError_t e = grant_lds_for((const void*)gauss_h_kernel<EXACT>, lds_h);
     if (e) return e;
     dim3 gh((w + H_TILE - 1) / H_TILE, h);
@@ -173,8 +193,8 @@ template <bool EXACT, int TX, int YG, int RS>
 hipError_t launch_v_cfg(hipStream_t stream, const float4* tmp, uint8_t* d_dst, const float* wts, int radius, uint32_t w, uint32_t h)
 {
     constexpr int ROWS = 4 * YG;
-    const size_t lds_v = (size_t)(ROWS + 2 * radius + V_SLACK) * RS * sizeof(float4);
-    if (lds_v > 160u * 1024u) return hipErrorInvalidValue;
+    const size_t lds_v = v_lds_bytes(ROWS, RS, radius);
+    if (lds_v > LDS_LIMIT) return hipErrorInvalidValue; // a forced shape that does not fit
     hipError_t e = grant_lds_for((const void*)gauss_v_kernel<EXACT, TX, YG, RS>, lds_v);
     if (e) return e;
     dim3 gv((w + TX - 1) / TX, (h + ROWS - 1) / ROWS);
@@ -193,23 +213,34 @@ int g_mfma_seg = 0; // tuning knob (pfxk_gauss_set_mfma_segments): row segments 
 int g_mfma_cols64 = 6;   // 6 and 8 K blocks (sigma 5.4 .. 16) ship on it: 8K sigma 8 0.094 -> 0.090, sigma 16 0.122 -> 0.111; 4 K blocks measure equal (0.075) and stay on two 32-column workgroups per CU.  pfxk_gauss_set_mfma_cols64 (pfx_tune "gauss_cols64"): bit 0 / 1 / 2 = launches with 4 / 6 / 8 K blocks on the 64-column kernel (else the 32-column one); identical results
 std::atomic<int> g_mfma_wp{1}, g_mfma_hp{2};   // process-wide development knobs read by batch workers' threads
 
+// The tile choice (pfxk_gauss_v_tile below, the one place that makes it).  The tile's halo (2r rows) is reloaded by every tile: beyond the
+// matrix-core kernel's radii (sigma 16 .. 100 in the reference's advanced dialog) taller tiles pay — measured at 8K: sigma 50 1.06 -> 0.92 ms
+// with 16 x 256, sigma 64 2.2 -> 1.1 with 8 x 512, sigma 100 3.3 -> 2.0 with 8 x 256
+int v_tile_index(int radius, int cfg_knob)
+{
+    int cfg = cfg_knob & 0xff;
+    if (cfg == 0 && radius > 110) cfg = radius <= 160 ? 1 : (radius <= 240 ? 4 : 3); // 16 x 256, 8 x 512, 8 x 256 (what still fits 160 KB of LDS)
+    if (radius > 340) cfg = 0; // the knob ends here
+    if (radius > 380) cfg = 2; // narrowest tile for huge radii (LDS bound)
+    return cfg >= 1 && cfg <= 4 ? cfg : 0;
+}
+
+template <bool EXACT, int CFG>
+hipError_t launch_v_tile(hipStream_t stream, const float4* tmp, uint8_t* d_dst, const float* wts, int radius, uint32_t w, uint32_t h)
+{
+    constexpr v_tile t = V_TILES[CFG];
+    return launch_v_cfg<EXACT, t.tx, t.yg, t.rs>(stream, tmp, d_dst, wts, radius, w, h);
+}
+
 template <bool EXACT>
 hipError_t launch_v(hipStream_t stream, const float4* tmp, uint8_t* d_dst, const float* wts, int radius, uint32_t w, uint32_t h)
 {
-    int cfg = g_v_cfg & 0xff;
-    // The tile's halo (2r rows) is reloaded by every tile: beyond the matrix-core kernel's radii (sigma 16 .. 100 in the reference's advanced
-    // dialog) taller tiles pay — measured at 8K: sigma 50 1.06 -> 0.92 ms with 16 x 256, sigma 64 2.2 -> 1.1 with 8 x 512, sigma 100 3.3 -> 2.0 with 8 x 256
-    if (cfg == 0 && radius > 110) cfg = radius <= 160 ? 1 : (radius <= 240 ? 4 : 3); // 16 x 256, 8 x 512, 8 x 256 (what still fits 160 KB of LDS)
-    if (radius > 340) cfg = 0;
-    if (radius > 380) cfg = 2; // narrowest tile for huge radii (LDS bound)
-    switch (cfg) {
-    case 1: return launch_v_cfg<EXACT, 16, 64, 16>(stream, tmp, d_dst, wts, radius, w, h);
-    case 2: return launch_v_cfg<EXACT, 4, 64, 5>(stream, tmp, d_dst, wts, radius, w, h);
-    case 3: return launch_v_cfg<EXACT, 8, 64, 10>(stream, tmp, d_dst, wts, radius, w, h);
-    case 4: return launch_v_cfg<EXACT, 8, 128, 10>(stream, tmp, d_dst, wts, radius, w, h);
-    // shipped: 8 columns x 128 rows, 256 threads.  Measured at 8K, sigma=16 (profiles/r01_tuning.md): 0.344 ms vs
-    // 0.368 (8x256 rows), 0.350 (4x256), 0.446 (16x256)
-    default: return launch_v_cfg<EXACT, 8, 32, 10>(stream, tmp, d_dst, wts, radius, w, h);
+    switch (pfxk_gauss_v_tile(radius, g_v_cfg, nullptr, nullptr, nullptr)) {
+    case 1: return launch_v_tile<EXACT, 1>(stream, tmp, d_dst, wts, radius, w, h);
+    case 2: return launch_v_tile<EXACT, 2>(stream, tmp, d_dst, wts, radius, w, h);
+    case 3: return launch_v_tile<EXACT, 3>(stream, tmp, d_dst, wts, radius, w, h);
+    case 4: return launch_v_tile<EXACT, 4>(stream, tmp, d_dst, wts, radius, w, h);
+    default: return launch_v_tile<EXACT, 0>(stream, tmp, d_dst, wts, radius, w, h);
     }
 }
 
@@ -922,6 +953,19 @@ __global__ __launch_bounds__(G6_T) void gauss_strip64_kernel(const CHAIN chain_a
 // LDS bounds: H tile (1024 + 2r + 12) x 20 B and the narrowest V tile (256 + 2r + 4) rows x 5 x 16 B <= 160 KiB
 extern "C" int pfxk_gauss_max_radius(void) { return 850; }
 extern "C" void pfxk_gauss_set_v_config(int cfg) { g_v_cfg = cfg; }
+// Pure: the vertical tile of a radius under a value of the "gauss_v_cfg" knob (its low byte forces a shape up to radius 340; 0 = automatic).
+// Returns the config index 0 .. 4 and fills in the tile's columns, output rows and the LDS bytes its launch requests; the launch refuses a
+// forced shape whose bytes exceed 160 KiB.
+extern "C" int pfxk_gauss_v_tile(int radius, int cfg_knob, int* tx, int* rows, size_t* lds_bytes)
+{
+    const int cfg = v_tile_index(radius, cfg_knob);
+    const v_tile t = V_TILES[cfg];
+    if (tx) *tx = t.tx;
+    if (rows) *rows = 4 * t.yg;
+    if (lds_bytes) *lds_bytes = v_lds_bytes(4 * t.yg, t.rs, radius);
+    return cfg;
+}
+extern "C" size_t pfxk_gauss_h_lds_bytes(int radius) { return h_lds_bytes(radius); } // what the horizontal pass's launch requests
 extern "C" void pfxk_gauss_set_mfma_segments(int n) { g_mfma_seg = n > 0 && n < 256 ? n : 0; }
 extern "C" void pfxk_gauss_set_mfma_parts(int wp, int hp) { g_mfma_wp = wp == 1 ? 1 : 2; g_mfma_hp = (hp == 1 && wp == 1) ? 1 : 2; }
 extern "C" void pfxk_gauss_set_mfma_cols64(int mask) { g_mfma_cols64 = mask & 7; }

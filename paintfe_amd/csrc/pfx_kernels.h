@@ -98,6 +98,10 @@ hipError_t pfxk_round_pack_check(hipStream_t s, unsigned long long* d_out /* [2]
 int        pfxk_gauss_max_radius(void);
 int        pfxk_gauss_weight_pad(void);
 void       pfxk_gauss_set_v_config(int cfg); // tuning knob, 0 = shipped
+/* pure: the vertical pass's tile for a radius under a value of that knob (low byte: 1 .. 4 force a shape up to radius 340, 0 = by radius, others = config 0).
+   Returns the config index 0 .. 4; fills in (each may be NULL) the tile's columns, its output rows and the LDS bytes the launch requests (refused above 160 KiB) */
+int        pfxk_gauss_v_tile(int radius, int cfg_knob, int* tx, int* rows, size_t* lds_bytes);
+size_t     pfxk_gauss_h_lds_bytes(int radius); // pure: the LDS bytes the horizontal pass's launch requests
 void       pfxk_gauss_set_mfma_segments(int n); // tuning knob of the matrix-core kernel, 0 = automatic
 /* bit-exact mode, radii 1 .. pfxk_gauss_fused_exact_max_radius() (the compiled limit): both passes in one kernel, the f32 intermediate in an LDS ring (k_gauss_exact.hip);
    _enabled: the process-wide A/B knob, read where the path is chosen (pfx_gauss.cpp), not by the launchers */

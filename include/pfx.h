@@ -1353,6 +1353,42 @@ int pfx_line_render(pfx_ctx* ctx, const pfx_line_tool* tool, uint8_t* preview_in
 int pfx_stroke_commit_mask_dev(pfx_ctx* ctx, void* conceal_dev, const void* preview_dev, const void* sel_dev /* may be NULL */, uint32_t w, uint32_t h, int reveal);
 int pfx_stroke_commit_mask(pfx_ctx* ctx, uint8_t* conceal_inout, const uint8_t* preview, const uint8_t* sel /* may be NULL */, uint32_t w, uint32_t h, int reveal);
 
+/* ================= histogram, per-band Hue/Saturation, colour range (ref: src/ops/adjustments.rs :883-937, :1594-1674, :1684-1792) =================
+ * The last pixel loops of the colour dialogs: the Levels dialog's histograms, Hue/Saturation with six colour bands, and the Colour Range dialog's mask.
+ * Images are w * h RGBA8; masks are w * h bytes, 0 = unselected, anything else = selected (the reference also takes a smaller mask; this surface does not).
+ * The `_dev` forms take device pointers (an RGBA8 one 4-byte aligned) and are asynchronous on the context's stream unless stated; the others stage host
+ * buffers.  A NULL context, a zero side, more than 256 Mpx, a NULL required pointer and the overlaps named below are PFX_ERR_INVALID before any launch; a
+ * refused call leaves its outputs untouched.
+ *
+ * compute_histogram: hist_out = R[256], G[256], B[256], L[256] counts in host memory; the call waits for the device (as pfx_selection_bounds_dev does).  A
+ * pixel is counted when sel is NULL or its mask byte is not 0, and its alpha is not 0.  L = min(round(0.2126f * r + 0.7152f * g + 0.0722f * b), 255), f32, left
+ * to right, unfused, half away from zero.  Exact: integer sums.  The counters are 32-bit: 2^32 pixels would wrap one, the 256 Mpx document limit is below it. */
+int pfx_histogram(pfx_ctx* ctx, const uint8_t* image, uint32_t w, uint32_t h, const uint8_t* sel /* may be NULL */, uint32_t hist_out[1024]);
+int pfx_histogram_dev(pfx_ctx* ctx, const void* image_dev, uint32_t w, uint32_t h, const void* sel_dev /* may be NULL */, uint32_t hist_out[1024]);
+/* hue_saturation_per_band_from_flat: bands[0 .. 5] = Reds, Yellows, Greens, Cyans, Blues, Magentas, centred on 0, 60, .. 300 degrees; a pixel's hue is in a
+ * band with weight 1 within 30 degrees of the centre, falling linearly to 0 at 45.  Hue shifts, saturation factors and lightness offsets of the global
+ * sliders and of every band of weight above 0 add up, in band order.  Bit-exact class; alpha is untouched; mask byte 0 copies the source pixel.  sparse_mode as
+ * pfx_adjust: the dialog's path is PFX_FROM_FLAT; PFX_DENSE skips the chunk zeroing; PFX_IN_PLACE works too (the bank's own chunk code runs here), though the
+ * reference has no such caller.  bands is host memory in both forms.  result == image (in place) is allowed, any other overlap of result with image or sel is
+ * refused, as is a slider value that is not finite.  Not part of pfx_chain_dev. */
+typedef struct pfx_hue_band { float hue, saturation, lightness; } pfx_hue_band;   /* HueBandAdjust: degrees -180 .. 180, percent -100 .. 100, percent -100 .. 100 */
+int pfx_hsl_bands(pfx_ctx* ctx, const uint8_t* image, uint8_t* result, uint32_t w, uint32_t h, float global_hue, float global_sat, float global_light,
+                  const pfx_hue_band bands[6], const uint8_t* sel /* may be NULL */, int sparse_mode);
+int pfx_hsl_bands_dev(pfx_ctx* ctx, const void* image_dev, void* result_dev, uint32_t w, uint32_t h, float global_hue, float global_sat, float global_light,
+                      const pfx_hue_band bands[6], const void* sel_dev /* may be NULL */, int sparse_mode);
+/* select_color_range: the new mask is 0 where alpha is 0, where the HSL saturation is below sat_min, or where the hue is further than hue_tolerance_deg (at
+ * least 0.36 degrees) from hue_center_deg around the wheel; elsewhere 255 * (1 - (distance / tolerance) ^ (1 / max(clamp(fuzziness, 0.001, 1), 0.01))),
+ * truncated.  It is combined with base_sel (NULL = all zero) by THIS function's rule, not apply_selection_shape's: combine_mode 0 replace, 1 add = max(new,
+ * base), 2 subtract = base saturating-minus new, 3 intersect = new * base / 255 in integers.  Every byte of sel_out is written; sel_out == base_sel (in place)
+ * is allowed, any other overlap of sel_out is refused.  The power is a libm call: off the few pixels where one f32 ulp of it moves the byte the result equals
+ * the reference's on glibc; on those it is within 1 (tests/colorrange_model.py).
+ * Also PFX_ERR_INVALID: combine_mode above 3, a setting that is not finite, hue_center_deg outside [0, 360] — beyond that range the reference's folded distance
+ * can go negative and its powf return NaN; the dialog's slider runs from 0 to 360 (src/ui/dialogs/core/selection.rs:58), so this refuses nothing it can send. */
+int pfx_select_color_range(pfx_ctx* ctx, const uint8_t* image, const uint8_t* base_sel /* may be NULL */, uint32_t w, uint32_t h, float hue_center_deg,
+                           float hue_tolerance_deg, float sat_min, float fuzziness, uint8_t combine_mode, uint8_t* sel_out);
+int pfx_select_color_range_dev(pfx_ctx* ctx, const void* image_dev, const void* base_sel_dev /* may be NULL */, uint32_t w, uint32_t h, float hue_center_deg,
+                               float hue_tolerance_deg, float sat_min, float fuzziness, uint8_t combine_mode, void* sel_out_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,7 @@
 // Header-only; link with -lpfx.  Nothing here does pixel arithmetic.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <optional>
 #include <stdexcept>
@@ -220,6 +221,26 @@ inline RgbaImage pixelate_core(GpuRenderer& g, const RgbaImage& flat, uint32_t b
 inline RgbaImage adjust(GpuRenderer& g, const RgbaImage& flat, pfx_adjust_op op, const std::vector<float>& p, const uint8_t* lut = nullptr,
                         const GrayImage* mask = nullptr, pfx_sparse_mode sparse = PFX_FROM_FLAT)
 { return apply(g, flat, [&](uint8_t* o) { return pfx_adjust(g.raw(), flat.data.data(), o, flat.width, flat.height, op, p.data(), (uint32_t)p.size(), lut, m(mask), sparse); }); }
+struct Histogram { std::array<uint32_t, 256> r, g, b, l; };
+inline Histogram compute_histogram(GpuRenderer& g, const RgbaImage& flat, const GrayImage* mask = nullptr)                                  // adjustments.rs:883
+{
+    uint32_t hist[1024];
+    g.check(pfx_histogram(g.raw(), flat.data.data(), flat.width, flat.height, m(mask), hist));
+    Histogram out;
+    std::copy(hist, hist + 256, out.r.begin()); std::copy(hist + 256, hist + 512, out.g.begin());
+    std::copy(hist + 512, hist + 768, out.b.begin()); std::copy(hist + 768, hist + 1024, out.l.begin());
+    return out;
+}
+inline RgbaImage hue_saturation_per_band(GpuRenderer& g, const RgbaImage& flat, float global_hue, float global_sat, float global_light,
+                                         const std::array<pfx_hue_band, 6>& bands, const GrayImage* mask = nullptr, pfx_sparse_mode sparse = PFX_FROM_FLAT) // :1635
+{ return apply(g, flat, [&](uint8_t* o) { return pfx_hsl_bands(g.raw(), flat.data.data(), o, flat.width, flat.height, global_hue, global_sat, global_light, bands.data(), m(mask), sparse); }); }
+inline GrayImage select_color_range(GpuRenderer& g, const RgbaImage& flat, float hue_center_deg, float hue_tolerance_deg, float sat_min, float fuzziness,
+                                    uint8_t combine_mode = 0, const GrayImage* base = nullptr)                                               // adjustments.rs:1684
+{
+    GrayImage out((size_t)flat.width * flat.height);
+    g.check(pfx_select_color_range(g.raw(), flat.data.data(), m(base), flat.width, flat.height, hue_center_deg, hue_tolerance_deg, sat_min, fuzziness, combine_mode, out.data()));
+    return out;
+}
 inline RgbaImage warp_mesh_catmull_rom(GpuRenderer& g, const RgbaImage& src, const std::vector<float>& orig_xy, const std::vector<float>& def_xy,
                                        uint32_t cols, uint32_t rows)                                                                    // transform.rs:1743
 { return apply(g, src, [&](uint8_t* o) { return pfx_warp_mesh_catmull_rom(g.raw(), src.data.data(), orig_xy.data(), def_xy.data(), cols, rows, src.width, src.height, o); }); }

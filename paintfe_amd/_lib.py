@@ -153,6 +153,10 @@ class LineTool(C.Structure):   # pfx_line_tool
                 ("arrow_side", C.c_int32), ("anti_alias", C.c_int32)]
 
 
+class HueBand(C.Structure):   # pfx_hue_band
+    _fields_ = [("hue", C.c_float), ("saturation", C.c_float), ("lightness", C.c_float)]
+
+
 _lib = None
 
 
@@ -216,5 +220,12 @@ def load() -> C.CDLL:
     lib.pfx_line_render_dev.argtypes = lib.pfx_line_render.argtypes = [C.c_void_p, C.POINTER(LineTool), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float),
                                                                        C.POINTER(C.c_float)]
     lib.pfx_stroke_commit_mask_dev.argtypes = lib.pfx_stroke_commit_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]
+    lib.pfx_histogram.argtypes = lib.pfx_histogram_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.pfx_hsl_bands.argtypes = lib.pfx_hsl_bands_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float,
+                                                                   C.POINTER(HueBand), C.c_void_p, C.c_int]
+    lib.pfx_select_color_range.argtypes = lib.pfx_select_color_range_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float,
+                                                                                     C.c_float, C.c_float, C.c_uint8, C.c_void_p]
+    lib.pfx_int_colorrange_info.restype = C.c_int
+    lib.pfx_int_colorrange_info.argtypes = [C.c_int]
     _lib = lib
     return lib

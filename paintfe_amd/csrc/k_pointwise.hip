@@ -20,7 +20,6 @@ using namespace pfxk::pw;
 
 namespace {
 
-// grid = one block per 64x64 chunk; lane = (cg = tid % 16 -> 4 px, rows tid/16 + {0,16,32,48})
 template <int OP, bool RHAI>
 __global__ __launch_bounds__(256) void pointwise_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                         const uint8_t* __restrict__ mask, const uint8_t* __restrict__ lut_g,
@@ -32,103 +31,7 @@ __global__ __launch_bounds__(256) void pointwise_kernel(const uint8_t* __restric
         reinterpret_cast<uint32_t*>(lut)[threadIdx.x] = reinterpret_cast<const uint32_t*>(lut_g)[threadIdx.x];
         __syncthreads();
     }
-    const uint32_t cxn = (w + 63u) / 64u;
-    const uint32_t bid = xcd_swizzle(blockIdx.x, gridDim.x);
-    const uint32_t bx = (bid % cxn) * 64u, by = (bid / cxn) * 64u;
-    const uint32_t cg = threadIdx.x & 15u, r0 = threadIdx.x >> 4;
-    const uint32_t x = bx + cg * 4u;
-    const bool vec = (w & 3u) == 0u; // rows 16-byte aligned -> one dwordx4 per row
-    const uint32_t* s32 = reinterpret_cast<const uint32_t*>(src);
-    uint32_t* d32 = reinterpret_cast<uint32_t*>(dst);
-
-    if (!mask && vec && bx + 64u <= w && by + 64u <= h) {
-        // interior chunk without a selection mask (every chunk of an 8K frame but the bottom row's): no per-pixel bounds or mask
-        // logic, so the 16 pixels of a lane are straight-line code — the general path below spends ~5 exec-mask branches per pixel
-        uint4 v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = *reinterpret_cast<const uint4*>(s32 + (size_t)(by + r0 + 16u * k) * w + x);
-        int any_in = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) any_in |= (int)((v[k].x | v[k].y | v[k].z | v[k].w) >> 24);
-        const bool live = sparse_mode == 2 ? __syncthreads_or(any_in) != 0 : true; // IN_PLACE: an unpopulated chunk is never visited
-        int any_out = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (live) {
-                v[k].x = apply_px<OP, RHAI>(P, lut, v[k].x); v[k].y = apply_px<OP, RHAI>(P, lut, v[k].y);
-                v[k].z = apply_px<OP, RHAI>(P, lut, v[k].z); v[k].w = apply_px<OP, RHAI>(P, lut, v[k].w);
-            } else v[k] = make_uint4(0u, 0u, 0u, 0u);
-            any_out |= (int)((v[k].x | v[k].y | v[k].z | v[k].w) >> 24);
-        }
-        const bool drop = sparse_mode == 1 ? __syncthreads_or(any_out) == 0 : false; // FROM_FLAT: a chunk whose alpha is all zero is dropped
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            *reinterpret_cast<uint4*>(d32 + (size_t)(by + r0 + 16u * k) * w + x) = drop ? make_uint4(0u, 0u, 0u, 0u) : v[k];
-        return;
-    }
-
-    uint32_t in[4][4], out[4][4];
-    bool ok[4][4];
-    int any_in = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t y = by + r0 + 16u * k;
-        const size_t rowoff = (size_t)y * w + x;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) { ok[k][p] = (y < h) && (x + p < w); in[k][p] = 0u; }
-        if (y < h && x < w) {
-            if (vec) {
-                const uint4 v = *reinterpret_cast<const uint4*>(s32 + rowoff);
-                in[k][0] = v.x; in[k][1] = v.y; in[k][2] = v.z; in[k][3] = v.w;
-            } else {
-#pragma unroll
-                for (int p = 0; p < 4; ++p) if (ok[k][p]) in[k][p] = s32[rowoff + p];
-            }
-        }
-#pragma unroll
-        for (int p = 0; p < 4; ++p) any_in |= (int)(in[k][p] >> 24);
-    }
-    bool live = true;
-    if (sparse_mode == 2) live = __syncthreads_or(any_in) != 0; // IN_PLACE: unpopulated chunk is never visited
-
-    int any_out = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t y = by + r0 + 16u * k;
-        uint32_t m4 = 0x01010101u;
-        if (mask && y < h && x < w) {
-            const size_t mo = (size_t)y * w + x;
-            if (vec) m4 = *reinterpret_cast<const uint32_t*>(mask + mo);
-            else { m4 = 0; for (int p = 0; p < 4; ++p) if (ok[k][p]) m4 |= (uint32_t)mask[mo + p] << (8 * p); }
-        }
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const bool sel = ((m4 >> (8 * p)) & 0xffu) != 0u;
-            uint32_t v = 0u;
-            if (live) v = sel ? apply_px<OP, RHAI>(P, lut, in[k][p]) : in[k][p];
-            out[k][p] = ok[k][p] ? v : 0u;
-            any_out |= (int)(out[k][p] >> 24);
-        }
-    }
-    if (sparse_mode == 1) { // FROM_FLAT: from_rgba_image(&out) drops a chunk whose alpha is all zero
-        if (__syncthreads_or(any_out) == 0) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-#pragma unroll
-                for (int p = 0; p < 4; ++p) out[k][p] = 0u;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t y = by + r0 + 16u * k;
-        if (!(y < h && x < w)) continue;
-        const size_t rowoff = (size_t)y * w + x;
-        if (vec) *reinterpret_cast<uint4*>(d32 + rowoff) = make_uint4(out[k][0], out[k][1], out[k][2], out[k][3]);
-        else {
-#pragma unroll
-            for (int p = 0; p < 4; ++p) if (ok[k][p]) d32[rowoff + p] = out[k][p];
-        }
-    }
+    chunk_walk(xcd_swizzle(blockIdx.x, gridDim.x), src, dst, mask, sparse_mode, w, h, [&](uint32_t px) __attribute__((always_inline)) { return apply_px<OP, RHAI>(P, lut, px); });   // k_pointwise.h: the mask and the sparse modes
 }
 
 // A chain of pointwise ops in ONE pass (pfx_chain_dev): the same chunk tiling, dense mode, no selection.  A lane's 16 pixels go through the ops one op at a time

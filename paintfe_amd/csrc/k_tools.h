@@ -1,9 +1,9 @@
-// k_tools.h — what the tool kernels share: k_shapes, k_inpaint, k_flood, k_select, k_colorkey, k_overlay, k_textfx, k_textwarp, k_gradient, k_dabtools and k_linetool include it, no other file does
+// k_tools.h — what the tool kernels share: k_shapes, k_inpaint, k_flood, k_select, k_colorkey, k_overlay, k_textfx, k_textwarp, k_gradient, k_dabtools, k_linetool and k_colorrange include it, no other file does
 // (the effect bank, the Gaussians and the compositor keep compiling from k_common.h alone).  A new tool kernel starts from here.
 //
 //   launch     stream_blocks / aligned_to / launch_stream for a streaming kernel, tile_grid for one workgroup per tile, dims_ok.
 //   walk       stream_walk: four pixels per lane, then the n % 4 tail, else pixel by pixel — the loop of every streaming kernel; tile_xy: a tiled one's origin.
-//   helpers    umin / umax, and the device flavour of atan2 / cos / sin: the f64 routine rounded once to f32.
+//   helpers    umin / umax, and the device flavour of atan2 / cos / sin: the f64 routine rounded once to f32 (k_colorrange.hip keeps its pow beside its one use).
 //
 // Deliberately NOT here, so that nobody folds them:
 //   the float-to-integer casts (as_u32, cast_u32, as_index, cvt_u32_sat, as_i32, round_u32): each restates a different Rust cast over a different domain — NaN or

@@ -305,6 +305,10 @@ extern "C" uint64_t pfx_int_dab_piece_entries(uint64_t entries);
 // the same for pfx_line_render[_dev]'s dots (pfx_linetool.cpp): the clear rides with the first piece, the arrowheads with the last
 extern "C" uint64_t pfx_int_line_piece_entries(uint64_t entries);
 
+// for the tests: the shape of the histogram kernel (k_colorrange.hip): which = 0 the most workgroups of one launch, 1 the private LDS copies of a workgroup; -1 =
+// unknown `which` (not in include/pfx.h)
+extern "C" int pfx_int_colorrange_info(int which);
+
 // blur_with_selection on device-resident images (pfx_api.cpp); mask_host may be NULL (= no selection)
 int pfx_int_blur_with_selection_dev(pfx_ctx* ctx, const void* d_src, void* d_dst, uint32_t w, uint32_t h, float sigma,
                                     const uint8_t* mask_host, const void* d_mask);

@@ -552,6 +552,24 @@ hipError_t pfxk_line_render(hipStream_t s, const pfxk_line* L, uint8_t* d_previe
 // commit_preview_to_layer_mask: conceal bytes in place from the preview's alpha; reveal: old (255 - s) / 255, else old + (255 - old) s / 255
 hipError_t pfxk_line_commit_mask(hipStream_t s, uint8_t* d_conceal, const uint8_t* d_preview, const uint8_t* d_sel, uint32_t w, uint32_t h, int reveal);
 
+// ---- k_colorrange.hip ---- the colour dialogs' last pixel loops (src/ops/adjustments.rs): compute_histogram :883, hue_saturation_per_band_from_flat :1635,
+// select_color_range :1684; host side: pfx_colorrange.cpp
+// the histogram kernel's grid never exceeds this many workgroups of 256 lanes (a lane takes 4 pixels per step on the 16-byte path, 1 on the byte path); a
+// workgroup keeps PFXK_HIST_COPIES private copies of the 1024 counters in LDS
+#define PFXK_HIST_MAX_BLOCKS 1024
+#define PFXK_HIST_COPIES 8
+// d_hist: 1024 u32 counters R[256] G[256] B[256] L[256], zeroed by a launch of its own, then counted into; d_mask may be NULL
+hipError_t pfxk_histogram(hipStream_t s, const uint8_t* d_src, const uint8_t* d_mask, size_t n, uint32_t* d_hist);
+// what is uniform over a per-band call: the global sliders after the host's f32 expressions (:1644-1645) and, per band, the factors that do not depend on the
+// pixel: hue, saturation / 100.0, lightness * 255.0 / 100.0
+typedef struct pfxk_hsl_bands { float g_hue, g_sat, g_light; float hue[6], sat[6], light[6]; } pfxk_hsl_bands;
+// the pointwise bank's chunk walk (k_pointwise.h: chunk_walk) with the per-band pixel function: d_mask may be NULL, d_dst may be d_src, sparse_mode as pfxk_adjust
+hipError_t pfxk_hsl_bands_apply(hipStream_t s, const uint8_t* d_src, uint8_t* d_dst, const uint8_t* d_mask, const pfxk_hsl_bands* B, int sparse_mode, uint32_t w, uint32_t h);
+// :1705-1707 prepared on the host, with expo = 1.0 / fuzz.max(0.01); combine: 0 replace, 1 add, 2 subtract, 3 intersect (:1742-1787)
+typedef struct pfxk_color_range { float hue_center, hue_tol, sat_min, expo; uint32_t combine; } pfxk_color_range;
+// d_base may be NULL (all zero) and may be d_out; every byte of d_out is written
+hipError_t pfxk_color_range_select(hipStream_t s, const uint8_t* d_src, const uint8_t* d_base, uint8_t* d_out, size_t n, const pfxk_color_range* R);
+
 #ifdef __cplusplus
 }
 #endif

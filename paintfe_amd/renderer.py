@@ -174,6 +174,14 @@ def _color_to_alpha(target, tolerance, softness, strength, spill_suppression, al
     return s
 
 
+def _hue_bands(bands):
+    """six pfx_hue_band from up to six (hue, saturation, lightness) triples"""
+    b = (_lib.HueBand * 6)()
+    for i, (hue, sat, light) in enumerate(bands):
+        b[i] = _lib.HueBand(float(hue), float(sat), float(light))
+    return b
+
+
 def _color_removal(seed, tolerance, smoothness, contiguous):
     r = _lib.ColorRemoval()
     r.seed_x, r.seed_y, r.tolerance, r.smoothness, r.contiguous = int(seed[0]), int(seed[1]), tolerance, int(smoothness), int(contiguous)
@@ -1109,6 +1117,60 @@ class GpuRenderer:
         """the last color_removal's 0 flood passes, 1 ring launches, 2 the ring kernel's tile edge, 3 its chunk (levels per launch), 4 kernel launches
         (pfx_int_colorkey_last; for tests and profiles)"""
         return int(self._lib.pfx_int_colorkey_last(self._h, C.c_int(which)))
+
+    # ------------------------------------------------------------------ histogram, per-band Hue/Saturation, colour range (ref: src/ops/adjustments.rs:883, :1635, :1684)
+    def histogram(self, img, mask=None) -> np.ndarray:
+        """compute_histogram: a (4, 256) uint32 array, rows R, G, B, luminance, over the pixels with alpha != 0 that `mask` (if any) selects"""
+        s = _u8(img)
+        h, w = s.shape[:2]
+        m = None if mask is None else _u8(mask)
+        hist = np.empty((4, 256), np.uint32)
+        self._check(self._lib.pfx_histogram(self._h, _p(s), C.c_uint32(w), C.c_uint32(h), _p(m), _p(hist)))
+        return hist
+
+    def histogram_dev(self, src_ptr: int, w: int, h: int, mask_ptr: int = 0) -> np.ndarray:
+        """the same of a device-resident image; waits for the device"""
+        hist = np.empty((4, 256), np.uint32)
+        self._check(self._lib.pfx_histogram_dev(self._h, C.c_void_p(src_ptr), C.c_uint32(w), C.c_uint32(h), C.c_void_p(mask_ptr or None), _p(hist)))
+        return hist
+
+    def hsl_bands(self, img, global_hue: float = 0.0, global_sat: float = 0.0, global_light: float = 0.0, bands=(), mask=None, sparse: int = FROM_FLAT, out=None):
+        """hue_saturation_per_band_from_flat: bands = up to six (hue degrees, saturation percent, lightness percent) for Reds, Yellows, Greens, Cyans, Blues,
+        Magentas (missing ones are zero); out may be `img` itself"""
+        src = _u8(img)
+        h, w = src.shape[:2]
+        dst = np.empty_like(src) if out is None else out
+        m = None if mask is None else _u8(mask)
+        self._check(self._lib.pfx_hsl_bands(self._h, _p(src), _p(dst), C.c_uint32(w), C.c_uint32(h), C.c_float(global_hue), C.c_float(global_sat), C.c_float(global_light),
+                                            _hue_bands(bands), _p(m), C.c_int(sparse)))
+        return dst
+
+    def hsl_bands_dev(self, src_ptr: int, dst_ptr: int, w: int, h: int, global_hue: float = 0.0, global_sat: float = 0.0, global_light: float = 0.0, bands=(),
+                      mask_ptr: int = 0, sparse: int = FROM_FLAT):
+        """dst_ptr == src_ptr works in place"""
+        self._check(self._lib.pfx_hsl_bands_dev(self._h, C.c_void_p(src_ptr), C.c_void_p(dst_ptr), C.c_uint32(w), C.c_uint32(h), C.c_float(global_hue), C.c_float(global_sat),
+                                                C.c_float(global_light), _hue_bands(bands), C.c_void_p(mask_ptr or None), C.c_int(sparse)))
+
+    def select_color_range(self, img, hue_center: float, hue_tolerance: float, sat_min: float, fuzziness: float, combine="replace", base=None, out=None):
+        """select_color_range: the (h, w) mask of the pixels within hue_tolerance degrees of hue_center (0 .. 360) whose saturation is at least sat_min, merged
+        with `base` by the function's own rule (add = max, subtract = saturating, intersect = product / 255); out may be `base` itself (in place)"""
+        s = _u8(img)
+        h, w = s.shape[:2]
+        b = None if base is None else _u8(base)
+        o = np.empty((h, w), np.uint8) if out is None else out
+        self._check(self._lib.pfx_select_color_range(self._h, _p(s), _p(b), C.c_uint32(w), C.c_uint32(h), C.c_float(hue_center), C.c_float(hue_tolerance),
+                                                     C.c_float(sat_min), C.c_float(fuzziness), C.c_uint8(_enum(COMBINE_MODES, combine).value), _p(o)))
+        return o
+
+    def select_color_range_dev(self, src_ptr: int, w: int, h: int, hue_center: float, hue_tolerance: float, sat_min: float, fuzziness: float, out_ptr: int,
+                               combine="replace", base_ptr: int = 0):
+        self._check(self._lib.pfx_select_color_range_dev(self._h, C.c_void_p(src_ptr), C.c_void_p(base_ptr or None), C.c_uint32(w), C.c_uint32(h), C.c_float(hue_center),
+                                                         C.c_float(hue_tolerance), C.c_float(sat_min), C.c_float(fuzziness),
+                                                         C.c_uint8(_enum(COMBINE_MODES, combine).value), C.c_void_p(out_ptr)))
+
+    def colorrange_info(self, which: int) -> int:
+        """0 the most workgroups of one histogram launch, 1 a workgroup's private copies of the counters (pfx_int_colorrange_info; for tests and profiles)"""
+        return int(self._lib.pfx_int_colorrange_info(C.c_int(which)))
 
     # ---- the floating selection (pfx_overlay_*): `ov` is an `overlay(...)` descriptor ----
     def overlay_commit(self, ov, source, base, overwrite_mask=None) -> np.ndarray:

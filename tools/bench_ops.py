@@ -220,7 +220,24 @@ def main() -> int:
     timed("selection: bounds", ["selection_bounds"], lambda: r.selection_bounds_dev(sp, w, h), px, 1, "the call waits for the device: 16 bytes read back")
     timed("selection: fill through a grey mask", ["selection_fill"], lambda: r.selection_fill_dev(d, sp, w, h, (200, 30, 60, 255)), px, 9, "an upper bound: 1 B read everywhere, 4 B read + written only inside the disc (0.29 of the canvas)")
     timed("selection: delete through a grey mask", ["selection_delete"], lambda: r.selection_delete_dev(d, sp, w, h), px, 9)
-    del sel, sel_out
+    # ---------------- histogram, per-band Hue/Saturation, colour range (k_colorrange.hip).  The histogram is a reduction over the image like auto-levels' min / max
+    # pass (the "minmax" timer inside pfx_auto_levels, host-buffer entry point: the staging is outside that timer), which is timed beside it on the same bytes
+    six_bands = [(30.0, -40.0, 10.0), (-60.0, 80.0, -15.0), (90.0, 25.0, 30.0), (-120.0, -75.0, -5.0), (150.0, 60.0, 20.0), (-170.0, -20.0, -35.0)]
+    flat_img = torch.empty_like(src)
+    flat_img[...] = torch.tensor([200, 100, 50, 255], dtype=torch.uint8, device=dev)
+    timed("colorrange: histogram, noise", ["histogram"], lambda: r.histogram_dev(s, w, h), px, 4, "4 B read per pixel, four LDS atomics per counted pixel; the call waits for 4 KiB read back")
+    timed("colorrange: histogram, noise, 70 % selection", ["histogram"], lambda: r.histogram_dev(s, w, h, mask_ptr=m), px, 5)
+    timed("colorrange: histogram, flat image", ["histogram"], lambda: r.histogram_dev(flat_img.data_ptr(), w, h), px, 4, "every lane on the same four bins: 8 private copies per workgroup")
+    if not args.only or args.only in "colorrange: auto-levels min/max pass":
+        src_host = src.cpu().numpy()
+        timed("colorrange: auto-levels min/max pass", ["minmax"], lambda: r.auto_levels(src_host), px, 4, "the histogram's yardstick: the same bytes, also a reduction", reps=3, warm=False)
+        del src_host
+    timed("colorrange: per-band hue/saturation, six bands + global", ["hsl_bands"], lambda: r.hsl_bands_dev(s, d, w, h, -15.0, 20.0, 5.0, six_bands), px, 8, "PFX_FROM_FLAT, no selection")
+    timed("colorrange: per-band hue/saturation, 70 % selection", ["hsl_bands"], lambda: r.hsl_bands_dev(s, d, w, h, -15.0, 20.0, 5.0, six_bands, mask_ptr=m), px, 9)
+    timed("colorrange: select, hue 30 +- 20, fuzziness 0.5", ["color_range"], lambda: r.select_color_range_dev(s, w, h, 30.0, 20.0, 0.1, 0.5, so), px, 5, "an f64 pow per pixel inside the tolerance")
+    timed("colorrange: select, hue 60 +- 180, fuzziness 0.3, add to a base", ["color_range"], lambda: r.select_color_range_dev(s, w, h, 60.0, 180.0, 0.0, 0.3, so, "add", m), px, 6,
+          "every opaque pixel takes the pow")
+    del sel, sel_out, flat_img
     # ---------------- removal by colour (k_colorkey.hip): colour to alpha is a streaming pass like HSL; the colour remover is the passability map, the connected
     # flood's passes (contiguous scope) and ceil(smoothness / 32) ring launches, the last one writing the image.  The HSL row and the bucket tool's flood of the
     # same image are repeated under this section's name so that one `--only colorkey` run holds them side by side

@@ -1389,6 +1389,53 @@ int pfx_select_color_range(pfx_ctx* ctx, const uint8_t* image, const uint8_t* ba
 int pfx_select_color_range_dev(pfx_ctx* ctx, const void* image_dev, const void* base_sel_dev /* may be NULL */, uint32_t w, uint32_t h, float hue_center_deg,
                                float hue_tolerance_deg, float sat_min, float fuzziness, uint8_t combine_mode, void* sel_out_dev);
 
+/* ================= background removal around the model (ref: src/ops/ai.rs :615-949, :1324-1445) =================
+ * Filter -> Remove Background runs a segmentation model in the caller's ONNX runtime; these are the reference's own pixel loops in front of the model and
+ * behind it, so that the layer, the model's input tensor, its outputs and the layer's new alpha stay on the device.  Images are w * h RGBA8; grey images and
+ * mattes are one byte per pixel; values are f32.  The `_dev` forms take device pointers (an RGBA8 or f32 one 4-byte aligned) and are asynchronous on the context's
+ * stream unless stated; the others stage host buffers.  Bit-exact class: f32 with one rounding per operation, glibc's expf, the bit-exact Lanczos3 resize.
+ * PFX_ERR_INVALID before any launch, outputs untouched: a NULL context, settings or required pointer; a zero side or more than 256 Mpx (values: 256 M); a
+ * tensor_size of 0; a threshold or edge_feather that is not finite; an is_probability outside -1 .. 1; a misaligned RGBA8 / f32 device pointer; an output that
+ * shares a byte with an input, except result == image where stated.  PFX_ERR_UNSUPPORTED: |mask_expansion| or |expansion| above 64, fill_holes above 64,
+ * ceil(edge_feather) above 256 (the dialog's sliders stop at 10, 20 and 20), and a resize in which one 64-column output tile reaches more than 2048 source
+ * columns (a model output wider than 2048 shrunk to a few dozen pixels).
+ *
+ * Tensor (preprocess_image): imageops::resize(image, S, S, Lanczos3) — pfx_resize_image, the same-size copy included — then plane c of the [3][S][S] tensor =
+ * ((p as f32 / 255.0) - MEAN[c]) / STD[c] for c = R, G, B; MEAN = {0.485, 0.456, 0.406}, STD = {0.229, 0.224, 0.225}; alpha is ignored.
+ * Score (is_probability_space, mask_confidence_score) of n_values f32: step = max(n / 10000, 1); min / max over the indices 0, step, 2 step, .. ignoring NaN, from
+ * f32::MAX / f32::MIN; is_probability = min >= -0.05 && max <= 1.05; prob = is_probability ? clamp(v, 0, 1) : 1 / (1 + expf(-v)), a NaN stays NaN; a value is
+ * decisive when prob as f64 lies outside 0.1 ..= 0.9, a NaN counts; confidence = decisive / n, 0.0 for n = 0 (with is_probability 0).  The call waits for its
+ * 16 bytes of result, as pfx_histogram_dev does.  Exact.
+ * Pick (ModelProfile::detect, preferred_output_index, the selection :1356-1380): host only, no context.  confidence[i] < 0 (or NaN) marks an output the caller
+ * could not read; it is skipped.  Among the outputs within 0.01 of the best confidence the profile's preferred index wins — the last output of a 1024 x 1024
+ * model with five or more outputs (BiRefNet), else the first — otherwise the highest confidence, the last of equal ones.  PFX_ERR_INVALID for NULL, n_outputs 0
+ * or no usable output.
+ * Post-process (postprocess_mask) on prob_w x prob_h values: (1) byte: prob as above with the given is_probability (-1: detected on these values, which waits
+ * for the device), then with smooth_edges r = 1 / (1 + expf(-(prob - threshold) * 12.0)), (r * 255.0).clamp(0, 255) as u8 (truncating, NaN -> 0), else prob >=
+ * threshold ? 255 : 0.  (2) expansion: |mask_expansion| iterations, each reading the previous image whole: dilating, a pixel with centre < 128 becomes the maximum
+ * of its in-image 3 x 3 neighbourhood; eroding, one with centre > 128 the minimum; 128 never changes and a pixel that has crossed 128 is frozen, so n iterations
+ * are not a (2n + 1)^2 window.  (3) close: fill_holes dilations, then fill_holes erosions.  (4) imageops::resize(GrayImage, w, h, Lanczos3) unless the sizes are
+ * equal.  (5) feather, if edge_feather > 0.5: r = max(ceil(edge_feather), 1), a row pass then a column pass of (sum / count) as u8 over 2r + 1 edge-clamped
+ * samples.  (6) a' = ((a / 255.0) * (m / 255.0) * 255.0).clamp(0, 255) as u8; the rgb is copied.
+ * pfx_matte_postprocess[_dev] is steps 1 - 6 and equals the stage calls composed; matte (may be NULL) receives the final w * h matte.  result == image (in place)
+ * is allowed there and in pfx_matte_apply_dev; no other overlap of an output is.  pfx_matte_expand_dev: a negative expansion erodes, 0 copies.
+ * pfx_matte_feather_dev copies at edge_feather <= 0.5. */
+typedef struct pfx_matte_settings { float threshold, edge_feather; int32_t mask_expansion, smooth_edges; uint32_t fill_holes; } pfx_matte_settings;  /* RemoveBgSettings */
+int pfx_matte_tensor(pfx_ctx* ctx, const uint8_t* image, uint32_t w, uint32_t h, uint32_t tensor_size, float* tensor /* 3 * tensor_size^2 */);
+int pfx_matte_tensor_dev(pfx_ctx* ctx, const void* image_dev, uint32_t w, uint32_t h, uint32_t tensor_size, void* tensor_dev);
+int pfx_matte_score(pfx_ctx* ctx, const float* values, size_t n_values, int32_t* is_probability, double* confidence);
+int pfx_matte_score_dev(pfx_ctx* ctx, const void* values_dev, size_t n_values, int32_t* is_probability /* host */, double* confidence /* host */);
+int pfx_matte_pick_output(uint32_t input_w, uint32_t input_h, const double* confidence, uint32_t n_outputs, uint32_t* picked);
+int pfx_matte_byte_dev(pfx_ctx* ctx, const void* values_dev, uint32_t prob_w, uint32_t prob_h, int32_t is_probability, const pfx_matte_settings* settings, void* grey_dev);
+int pfx_matte_expand_dev(pfx_ctx* ctx, const void* grey_dev, uint32_t prob_w, uint32_t prob_h, int32_t expansion, void* grey_out_dev);
+int pfx_matte_resize_dev(pfx_ctx* ctx, const void* grey_dev, uint32_t prob_w, uint32_t prob_h, void* matte_dev, uint32_t w, uint32_t h);
+int pfx_matte_feather_dev(pfx_ctx* ctx, const void* grey_dev, uint32_t w, uint32_t h, float edge_feather, void* matte_dev);
+int pfx_matte_apply_dev(pfx_ctx* ctx, const void* image_dev, const void* matte_dev, uint32_t w, uint32_t h, void* result_dev);
+int pfx_matte_postprocess_dev(pfx_ctx* ctx, const void* values_dev, uint32_t prob_w, uint32_t prob_h, int32_t is_probability, const void* image_dev, uint32_t w, uint32_t h,
+                              const pfx_matte_settings* settings, void* result_dev, void* matte_dev /* may be NULL */);
+int pfx_matte_postprocess(pfx_ctx* ctx, const float* values, uint32_t prob_w, uint32_t prob_h, int32_t is_probability, const uint8_t* image, uint32_t w, uint32_t h,
+                          const pfx_matte_settings* settings, uint8_t* result, uint8_t* matte /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

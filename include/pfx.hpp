@@ -241,6 +241,36 @@ inline GrayImage select_color_range(GpuRenderer& g, const RgbaImage& flat, float
     g.check(pfx_select_color_range(g.raw(), flat.data.data(), m(base), flat.width, flat.height, hue_center_deg, hue_tolerance_deg, sat_min, fuzziness, combine_mode, out.data()));
     return out;
 }
+// background removal around the model (src/ops/ai.rs): the tensor in front of it, the score of each output, the pick, the post-process behind it
+inline std::vector<float> preprocess_image(GpuRenderer& g, const RgbaImage& input, uint32_t target_size)                                  // ai.rs:731
+{
+    std::vector<float> tensor((size_t)3 * target_size * target_size);
+    g.check(pfx_matte_tensor(g.raw(), input.data.data(), input.width, input.height, target_size, tensor.data()));
+    return tensor;
+}
+struct MaskScore { bool is_probability; double confidence; };
+inline MaskScore mask_confidence_score(GpuRenderer& g, const std::vector<float>& data)                                                     // ai.rs:706
+{
+    int32_t is_prob = 0;
+    double confidence = 0.0;
+    g.check(pfx_matte_score(g.raw(), data.data(), data.size(), &is_prob, &confidence));
+    return {is_prob != 0, confidence};
+}
+inline std::optional<uint32_t> pick_output(uint32_t input_w, uint32_t input_h, const std::vector<double>& confidence)                      // ai.rs:1356-1380
+{
+    uint32_t picked = 0;
+    if (pfx_matte_pick_output(input_w, input_h, confidence.data(), (uint32_t)confidence.size(), &picked) != PFX_OK) return std::nullopt;
+    return picked;
+}
+inline RgbaImage postprocess_mask(GpuRenderer& g, const std::vector<float>& values, uint32_t mask_w, uint32_t mask_h, const RgbaImage& original,
+                                  const pfx_matte_settings& settings, int32_t is_probability = -1, GrayImage* matte = nullptr)             // ai.rs:766 behind :1402-1415
+{
+    if (matte) matte->resize((size_t)original.width * original.height);
+    return apply(g, original, [&](uint8_t* o) {
+        return pfx_matte_postprocess(g.raw(), values.data(), mask_w, mask_h, is_probability, original.data.data(), original.width, original.height, &settings, o,
+                                     matte ? matte->data() : nullptr);
+    });
+}
 inline RgbaImage warp_mesh_catmull_rom(GpuRenderer& g, const RgbaImage& src, const std::vector<float>& orig_xy, const std::vector<float>& def_xy,
                                        uint32_t cols, uint32_t rows)                                                                    // transform.rs:1743
 { return apply(g, src, [&](uint8_t* o) { return pfx_warp_mesh_catmull_rom(g.raw(), src.data.data(), orig_xy.data(), def_xy.data(), cols, rows, src.width, src.height, o); }); }

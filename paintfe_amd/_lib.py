@@ -157,6 +157,10 @@ class HueBand(C.Structure):   # pfx_hue_band
     _fields_ = [("hue", C.c_float), ("saturation", C.c_float), ("lightness", C.c_float)]
 
 
+class MatteSettings(C.Structure):   # pfx_matte_settings
+    _fields_ = [("threshold", C.c_float), ("edge_feather", C.c_float), ("mask_expansion", C.c_int32), ("smooth_edges", C.c_int32), ("fill_holes", C.c_uint32)]
+
+
 _lib = None
 
 
@@ -227,5 +231,18 @@ def load() -> C.CDLL:
                                                                                      C.c_float, C.c_float, C.c_uint8, C.c_void_p]
     lib.pfx_int_colorrange_info.restype = C.c_int
     lib.pfx_int_colorrange_info.argtypes = [C.c_int]
+    _u32 = C.c_uint32
+    lib.pfx_matte_tensor.argtypes = lib.pfx_matte_tensor_dev.argtypes = [C.c_void_p, C.c_void_p, _u32, _u32, _u32, C.c_void_p]
+    lib.pfx_matte_score.argtypes = lib.pfx_matte_score_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+    lib.pfx_matte_pick_output.argtypes = [_u32, _u32, C.POINTER(C.c_double), _u32, C.POINTER(_u32)]
+    lib.pfx_matte_byte_dev.argtypes = [C.c_void_p, C.c_void_p, _u32, _u32, C.c_int32, C.POINTER(MatteSettings), C.c_void_p]
+    lib.pfx_matte_expand_dev.argtypes = [C.c_void_p, C.c_void_p, _u32, _u32, C.c_int32, C.c_void_p]
+    lib.pfx_matte_resize_dev.argtypes = [C.c_void_p, C.c_void_p, _u32, _u32, C.c_void_p, _u32, _u32]
+    lib.pfx_matte_feather_dev.argtypes = [C.c_void_p, C.c_void_p, _u32, _u32, C.c_float, C.c_void_p]
+    lib.pfx_matte_apply_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _u32, _u32, C.c_void_p]
+    lib.pfx_matte_postprocess.argtypes = lib.pfx_matte_postprocess_dev.argtypes = [C.c_void_p, C.c_void_p, _u32, _u32, C.c_int32, C.c_void_p, _u32, _u32,
+                                                                                   C.POINTER(MatteSettings), C.c_void_p, C.c_void_p]
+    lib.pfx_int_matte_info.restype = C.c_int
+    lib.pfx_int_matte_info.argtypes = [C.c_int]
     _lib = lib
     return lib

@@ -26,6 +26,13 @@ struct pfx_layer_state { // GpuLayerState (ref: src/gpu/renderer.rs:206-209): de
     uint64_t generation = 0;
 };
 
+struct pfx_matte_axes {   // the matte resize's tables on the device, kept for the next call of the same sizes (pfx_matte.cpp: prepare_resize)
+    pfx_devbuf buf;
+    bool valid = false;
+    uint32_t pw = 0, ph = 0, w = 0, h = 0, span_max = 0;
+    size_t n_u32 = 0, v_wts = 0;   // u32 entries in front of the weights; vertical weights in front of the horizontal ones
+};
+
 struct pfx_timing_rec {
     std::string name;
     hipEvent_t start, stop;
@@ -107,6 +114,9 @@ struct pfx_ctx {
     pfx_devbuf overlay_ws;                              // the floating selection's scaled source (pfx_overlay.cpp); pfx_resize_image_dev itself uses fx_a and st_tmp
     pfx_devbuf textfx_ws;                               // the text styles' planes, blur images and cropped region (pfx_textfx.cpp); the Gaussian itself uses st_tmp
     pfx_devbuf textwarp_ws;                             // a placed text block's warped and rotated buffers (pfx_textwarp.cpp)
+    pfx_devbuf matte_ws, matte_tab;                     // background removal (pfx_matte.cpp): the stages' byte planes and the scaled model input; the 768-entry
+    bool matte_tab_valid = false;                       // normalisation table, uploaded once
+    pfx_matte_axes matte_axes;
 };
 
 // ---- error plumbing ----
@@ -308,6 +318,11 @@ extern "C" uint64_t pfx_int_line_piece_entries(uint64_t entries);
 // for the tests: the shape of the histogram kernel (k_colorrange.hip): which = 0 the most workgroups of one launch, 1 the private LDS copies of a workgroup; -1 =
 // unknown `which` (not in include/pfx.h)
 extern "C" int pfx_int_colorrange_info(int which);
+
+// for the tests: the shape of the matte kernels (k_matte.hip): which = 0 the morphology's tile edge, 1 its iterations per launch (= its apron), 2 / 3 the columns /
+// rows of the one-channel resize's output tile, 4 the outputs of one workgroup of the feather's row pass, 5 the columns of one workgroup of its column pass, 6 the
+// most source columns one resize tile may reach, 7 the most at which the tile keeps its full height, 8 its rows beyond that; -1 = unknown `which` (not in include/pfx.h)
+extern "C" int pfx_int_matte_info(int which);
 
 // blur_with_selection on device-resident images (pfx_api.cpp); mask_host may be NULL (= no selection)
 int pfx_int_blur_with_selection_dev(pfx_ctx* ctx, const void* d_src, void* d_dst, uint32_t w, uint32_t h, float sigma,

@@ -570,6 +570,43 @@ typedef struct pfxk_color_range { float hue_center, hue_tol, sat_min, expo; uint
 // d_base may be NULL (all zero) and may be d_out; every byte of d_out is written
 hipError_t pfxk_color_range_select(hipStream_t s, const uint8_t* d_src, const uint8_t* d_base, uint8_t* d_out, size_t n, const pfxk_color_range* R);
 
+// ---- k_matte.hip ---- background removal around the model (src/ops/ai.rs): preprocess_image :731, is_probability_space :675, mask_confidence_score :706,
+// postprocess_mask :766, apply_mask_expansion :850, blur_grayscale :913; host side: pfx_matte.cpp
+// the morphology's workgroup owns a PFXK_MATTE_TILE^2 tile and runs up to PFXK_MATTE_K iterations per launch on it and an apron of that many cells in LDS; the
+// one-channel resize's output tile (TOY rows while a tile reaches at most TALL_SPAN source columns, TOY_WIDE beyond); the most source columns a tile may reach; the outputs of one workgroup of the feather's row pass and
+// the columns of one workgroup of its column pass; the feather's largest radius
+#define PFXK_MATTE_TILE 64
+#define PFXK_MATTE_K 16
+#define PFXK_MATTE_RZ_TOX 64
+#define PFXK_MATTE_RZ_TOY 32
+#define PFXK_MATTE_RZ_TALL_SPAN 512
+#define PFXK_MATTE_RZ_TOY_WIDE 8
+#define PFXK_MATTE_RZ_MAX_SPAN 2048
+#define PFXK_MATTE_BOX_CHUNK 1024
+#define PFXK_MATTE_BOX_COLS 256
+#define PFXK_MATTE_MAX_FEATHER 256
+// plane c of d_tensor (n floats each) = d_table[c * 256 + channel c of the pixel]; d_table: 768 floats built on the host
+hipError_t pfxk_matte_tensor(hipStream_t s, const uint8_t* d_rgba, const float* d_table, float* d_tensor, size_t n);
+// d_out[0 .. 3] = the sampled minimum and maximum over the indices 0, step, 2 step, .. as order-preserving u32 keys (PFXK_MATTE_KEY; NaN skipped, the start
+// values are FLT_MAX and -FLT_MAX), the decisive count with the values read as probabilities, the decisive count with them read as logits
+hipError_t pfxk_matte_score(hipStream_t s, const float* d_values, uint32_t n, uint32_t step, uint32_t* d_out);
+#define PFXK_MATTE_KEY(f32_bits) (((f32_bits) & 0x80000000u) ? ~(f32_bits) : ((f32_bits) | 0x80000000u))
+// to_probability + postprocess_mask's byte step
+hipError_t pfxk_matte_byte(hipStream_t s, const float* d_values, uint8_t* d_grey, size_t n, int is_prob, int smooth, float threshold);
+// `iters` (1 .. PFXK_MATTE_K) iterations of apply_mask_expansion's conditional 3 x 3 dilate (or erode) from d_src into d_dst, which share no byte
+hipError_t pfxk_matte_morph(hipStream_t s, const uint8_t* d_src, uint8_t* d_dst, uint32_t w, uint32_t h, uint32_t iters, int dilate);
+// imageops::resize of one byte per sample, tables as pfxk_resize; span_max at most PFXK_MATTE_RZ_MAX_SPAN.  d_matte (may be NULL) receives the nw x nh matte; with
+// d_image the tile's epilogue also writes d_result = d_image with its alpha multiplied by the matte (d_result may be d_image)
+hipError_t pfxk_matte_resize(hipStream_t s, const uint8_t* d_grey, const uint32_t* v_left, const uint32_t* v_count, const uint32_t* v_off, const float* v_wts,
+                             const uint32_t* h_left, const uint32_t* h_count, const uint32_t* h_off, const float* h_wts, uint32_t w, uint32_t nw, uint32_t nh,
+                             uint32_t span_max, uint8_t* d_matte, const uint8_t* d_image, uint8_t* d_result);
+// blur_grayscale's two passes, r = 1 .. PFXK_MATTE_MAX_FEATHER: edge-clamped windows of 2 r + 1 samples, integer sums, (sum / count) as u8.  The column pass walks
+// bands of `band` rows.  d_src and d_dst share no byte
+hipError_t pfxk_matte_box_h(hipStream_t s, const uint8_t* d_src, uint8_t* d_dst, uint32_t w, uint32_t h, uint32_t r);
+hipError_t pfxk_matte_box_v(hipStream_t s, const uint8_t* d_src, uint8_t* d_dst, uint32_t w, uint32_t h, uint32_t r, uint32_t band);
+// a' = ((a / 255.0) * (m / 255.0) * 255.0).clamp(0, 255) as u8, the rgb copied; d_result may be d_image
+hipError_t pfxk_matte_apply(hipStream_t s, const uint8_t* d_image, const uint8_t* d_matte, uint8_t* d_result, size_t n);
+
 #ifdef __cplusplus
 }
 #endif

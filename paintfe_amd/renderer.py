@@ -182,6 +182,11 @@ def _hue_bands(bands):
     return b
 
 
+def matte_settings(threshold: float = 0.5, edge_feather: float = 0.0, mask_expansion: int = 0, smooth_edges: bool = True, fill_holes: int = 0):
+    """pfx_matte_settings (RemoveBgSettings, ref: src/ops/ai.rs:19-49; the defaults are its Default)"""
+    return _lib.MatteSettings(float(threshold), float(edge_feather), int(mask_expansion), int(bool(smooth_edges)), int(fill_holes))
+
+
 def _color_removal(seed, tolerance, smoothness, contiguous):
     r = _lib.ColorRemoval()
     r.seed_x, r.seed_y, r.tolerance, r.smoothness, r.contiguous = int(seed[0]), int(seed[1]), tolerance, int(smoothness), int(contiguous)
@@ -1171,6 +1176,76 @@ class GpuRenderer:
     def colorrange_info(self, which: int) -> int:
         """0 the most workgroups of one histogram launch, 1 a workgroup's private copies of the counters (pfx_int_colorrange_info; for tests and profiles)"""
         return int(self._lib.pfx_int_colorrange_info(C.c_int(which)))
+
+    # ------------------------------------------------------------------ background removal around the model (ref: src/ops/ai.rs); settings: matte_settings(...)
+    def matte_tensor(self, img, tensor_size: int) -> np.ndarray:
+        """preprocess_image: the (3, S, S) float32 model input of an RGBA8 image — Lanczos3 to S x S, ImageNet normalisation, alpha ignored"""
+        s = _u8(img)
+        h, w = s.shape[:2]
+        out = np.empty((3, tensor_size, tensor_size), np.float32)
+        self._check(self._lib.pfx_matte_tensor(self._h, _p(s), C.c_uint32(w), C.c_uint32(h), C.c_uint32(tensor_size), _p(out)))
+        return out
+
+    def matte_tensor_dev(self, image_ptr: int, w: int, h: int, tensor_size: int, tensor_ptr: int):
+        self._check(self._lib.pfx_matte_tensor_dev(self._h, C.c_void_p(image_ptr), C.c_uint32(w), C.c_uint32(h), C.c_uint32(tensor_size), C.c_void_p(tensor_ptr)))
+
+    def _matte_score(self, fn, values, n):
+        is_prob, conf = C.c_int32(-7), C.c_double(-7.0)
+        self._check(fn(self._h, values, C.c_size_t(n), C.byref(is_prob), C.byref(conf)))
+        return bool(is_prob.value), float(conf.value)
+
+    def matte_score(self, values):
+        """(is_probability_space, mask_confidence_score) of one output tensor of the model"""
+        v = np.ascontiguousarray(values, np.float32)
+        return self._matte_score(self._lib.pfx_matte_score, _p(v), v.size)
+
+    def matte_score_dev(self, values_ptr: int, n_values: int):
+        """the same of a device-resident tensor; waits for the device"""
+        return self._matte_score(self._lib.pfx_matte_score_dev, C.c_void_p(values_ptr), n_values)
+
+    def matte_byte_dev(self, values_ptr: int, prob_w: int, prob_h: int, settings, grey_ptr: int, is_probability: int = -1):
+        """to_probability + the threshold / sigmoid edge; is_probability -1 detects as the reference does (and waits for the device)"""
+        self._check(self._lib.pfx_matte_byte_dev(self._h, C.c_void_p(values_ptr), C.c_uint32(prob_w), C.c_uint32(prob_h), C.c_int32(is_probability), C.byref(settings),
+                                                 C.c_void_p(grey_ptr)))
+
+    def matte_expand_dev(self, grey_ptr: int, prob_w: int, prob_h: int, expansion: int, out_ptr: int):
+        """apply_mask_expansion: |expansion| conditional 3 x 3 dilations (> 0) or erosions (< 0)"""
+        self._check(self._lib.pfx_matte_expand_dev(self._h, C.c_void_p(grey_ptr), C.c_uint32(prob_w), C.c_uint32(prob_h), C.c_int32(expansion), C.c_void_p(out_ptr)))
+
+    def matte_resize_dev(self, grey_ptr: int, prob_w: int, prob_h: int, matte_ptr: int, w: int, h: int):
+        self._check(self._lib.pfx_matte_resize_dev(self._h, C.c_void_p(grey_ptr), C.c_uint32(prob_w), C.c_uint32(prob_h), C.c_void_p(matte_ptr), C.c_uint32(w), C.c_uint32(h)))
+
+    def matte_feather_dev(self, grey_ptr: int, w: int, h: int, edge_feather: float, matte_ptr: int):
+        self._check(self._lib.pfx_matte_feather_dev(self._h, C.c_void_p(grey_ptr), C.c_uint32(w), C.c_uint32(h), C.c_float(edge_feather), C.c_void_p(matte_ptr)))
+
+    def matte_apply_dev(self, image_ptr: int, matte_ptr: int, w: int, h: int, result_ptr: int):
+        """the image's alpha times the matte; result_ptr == image_ptr works in place"""
+        self._check(self._lib.pfx_matte_apply_dev(self._h, C.c_void_p(image_ptr), C.c_void_p(matte_ptr), C.c_uint32(w), C.c_uint32(h), C.c_void_p(result_ptr)))
+
+    def matte_postprocess_dev(self, values_ptr: int, prob_w: int, prob_h: int, image_ptr: int, w: int, h: int, settings, result_ptr: int, matte_ptr: int = 0,
+                              is_probability: int = -1):
+        """postprocess_mask in one call: equal to matte_byte_dev, matte_expand_dev (expansion, then the close), matte_resize_dev, matte_feather_dev and
+        matte_apply_dev composed; result_ptr == image_ptr works in place; matte_ptr (optional) receives the final w x h matte"""
+        self._check(self._lib.pfx_matte_postprocess_dev(self._h, C.c_void_p(values_ptr), C.c_uint32(prob_w), C.c_uint32(prob_h), C.c_int32(is_probability),
+                                                        C.c_void_p(image_ptr), C.c_uint32(w), C.c_uint32(h), C.byref(settings), C.c_void_p(result_ptr),
+                                                        C.c_void_p(matte_ptr or None)))
+
+    def matte_postprocess(self, values, img, settings, is_probability: int = -1, with_matte: bool = False):
+        """the same on host arrays: values (prob_h, prob_w) float32, img (h, w, 4); returns the image, or (image, matte) with with_matte"""
+        v = np.ascontiguousarray(values, np.float32)
+        s = _u8(img)
+        h, w = s.shape[:2]
+        out = np.empty_like(s)
+        matte = np.empty((h, w), np.uint8) if with_matte else None
+        self._check(self._lib.pfx_matte_postprocess(self._h, _p(v), C.c_uint32(v.shape[1]), C.c_uint32(v.shape[0]), C.c_int32(is_probability), _p(s), C.c_uint32(w),
+                                                    C.c_uint32(h), C.byref(settings), _p(out), _p(matte)))
+        return (out, matte) if with_matte else out
+
+    def matte_info(self, which: int) -> int:
+        """0 the morphology's tile edge, 1 its iterations per launch, 2 / 3 the resize's output tile columns / rows, 4 the feather's row-pass outputs per workgroup,
+        5 its column-pass columns per workgroup, 6 the resize tile's source-column cap, 7 the widest span of a full-height tile, 8 the tile's rows beyond it
+        (pfx_int_matte_info; for tests and profiles)"""
+        return int(self._lib.pfx_int_matte_info(C.c_int(which)))
 
     # ---- the floating selection (pfx_overlay_*): `ov` is an `overlay(...)` descriptor ----
     def overlay_commit(self, ov, source, base, overwrite_mask=None) -> np.ndarray:

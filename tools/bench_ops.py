@@ -238,6 +238,44 @@ def main() -> int:
     timed("colorrange: select, hue 60 +- 180, fuzziness 0.3, add to a base", ["color_range"], lambda: r.select_color_range_dev(s, w, h, 60.0, 180.0, 0.0, 0.3, so, "add", m), px, 6,
           "every opaque pixel takes the pow")
     del sel, sel_out, flat_img
+    # ---------------- background removal around the model (k_matte.hip): an 8K layer and a 1024 x 1024 model (BiRefNet's size).  The yardstick is the pointwise bank's
+    # invert on the same buffers in the same run: 8 B/px, which is the document traffic of the unfeathered post-process.  Every post-process row comes twice: the one
+    # call, and the stage calls composed (byte, expand, close, resize, feather, apply), whose full-size matte makes a round trip through memory
+    if not args.only or "matte" in args.only:
+        from paintfe_amd import matte_settings
+        S = 1024
+        spx = S * S
+        yy, xx = torch.meshgrid(torch.arange(S, device=dev, dtype=torch.float32), torch.arange(S, device=dev, dtype=torch.float32), indexing="ij")
+        blob = (1.0 - torch.hypot((xx - S * 0.45) / (S * 0.3), (yy - S * 0.55) / (S * 0.35))) * 9.0 + torch.randn((S, S), device=dev, generator=g) * 1.2
+        logit = blob.contiguous()
+        tensor_out = torch.empty((3, S, S), dtype=torch.float32, device=dev)
+        grey_a, grey_b = torch.empty((S, S), dtype=torch.uint8, device=dev), torch.empty((S, S), dtype=torch.uint8, device=dev)
+        full_a, full_b = torch.empty((h, w), dtype=torch.uint8, device=dev), torch.empty((h, w), dtype=torch.uint8, device=dev)
+        lp, tp, ga, gb, fa, fb = logit.data_ptr(), tensor_out.data_ptr(), grey_a.data_ptr(), grey_b.data_ptr(), full_a.data_ptr(), full_b.data_ptr()
+        post_bytes = 8 + 4 * spx / px   # the layer read and written, the model's output read
+
+        def composed(ms):
+            a, b = ga, gb
+            r.matte_byte_dev(lp, S, S, ms, a, is_probability=0)
+            for e in (ms.mask_expansion, ms.fill_holes, -ms.fill_holes):
+                if e:
+                    r.matte_expand_dev(a, S, S, e, b)
+                    a, b = b, a
+            r.matte_resize_dev(a, S, S, fa, w, h)
+            r.matte_feather_dev(fa, w, h, ms.edge_feather, fb)
+            r.matte_apply_dev(s, fb, w, h, d)
+
+        stage_timers = ["matte_byte", "matte_expand", "matte_resize", "matte_feather", "matte_apply"]
+        timed("matte yardstick: invert", ["adjust"], lambda: r.adjust_dev(s, d, w, h, "invert"), px, 8, "8 B/px on the same buffers, the same run")
+        timed("matte: tensor, 8K -> 3 x 1024 x 1024 f32", ["resize", "matte_tensor"], lambda: r.matte_tensor_dev(s, w, h, S, tp), px, 4 + 12 * spx / px,
+              "the RGBA Lanczos3 resize (a 7.5 x reduction: two passes through an f32 intermediate) and the table pass")
+        timed("matte: score of one 1024 x 1024 output", ["matte_score"], lambda: r.matte_score_dev(lp, spx), spx, 4, "an f64 expf per value; the call waits for 16 bytes")
+        timed("matte: score of five outputs", ["matte_score"], lambda: [r.matte_score_dev(lp, spx) for _ in range(5)], 5 * spx, 4)
+        for label, ms in (("defaults", matte_settings()), ("Portrait (feather 1, expansion 1, close 8)", matte_settings(0.5, 1.0, 1, True, 8)),
+                          ("feather 20", matte_settings(0.5, 20.0, 0, True, 0))):
+            timed(f"matte: postprocess, {label}", ["matte_postprocess"], lambda ms=ms: r.matte_postprocess_dev(lp, S, S, s, w, h, ms, d, is_probability=0), px, post_bytes)
+            timed(f"matte: stage calls composed, {label}", stage_timers, lambda ms=ms: composed(ms), px, post_bytes, "the matte written and read once more (feather: twice)")
+        del logit, blob, tensor_out, grey_a, grey_b, full_a, full_b, yy, xx
     # ---------------- removal by colour (k_colorkey.hip): colour to alpha is a streaming pass like HSL; the colour remover is the passability map, the connected
     # flood's passes (contiguous scope) and ceil(smoothness / 32) ring launches, the last one writing the image.  The HSL row and the bucket tool's flood of the
     # same image are repeated under this section's name so that one `--only colorkey` run holds them side by side

@@ -11,6 +11,13 @@
 //
 // Residency: the image lives on the device in one of two ping-pong buffers (ctx->st_in / st_out) for the whole script; the
 // selection mask lives in ctx->st_mask.  Host mirrors exist only while scalar accessors are in use.
+//
+// The mask and the transforms.  The reference never touches the mask in a transform.  After rotate_canvas_90cw / 90ccw the byte count still fits and the
+// same bytes are read as rows of the new width by is_selected, fill_selected and the `_core` effects (scripting.rs:343, :627-630, :1445): st_mask stays
+// flat here too.  Divergence, on purpose (next to the operation budget's, pfx_rhai.h): after a resize_canvas / resize_image that changes the size the
+// reference keeps the vector of the old size — is_selected reads it flat behind a length test, the `_core` effects get an all-zero mask if it is too
+// short and its first w * h bytes otherwise, fill_selected / delete_selected index past its end and panic.  Here the mask is dropped: has_selection() is
+// false afterwards and everything counts as selected.  tests/script_model.py follows this rule; tests/script_cases.py pins it.
 #include <algorithm>
 #include <chrono>
 #include <cmath>

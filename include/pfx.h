@@ -778,7 +778,7 @@ int pfx_batch_pipeline(const int* devices, uint32_t n_devices, uint32_t n_images
  * both colour mix.  Everything that is uniform over the image (rotation, angles, vertex lists, the heart's path) is computed on the host with the host libm, as
  * the reference does.  Bit-exact class, except pentagon, hexagon, octagon, star5 and star6, which evaluate atan2 / cos / sin per pixel: +-1 LSB class (the f64
  * routine rounded once, like pfx_twist_core).  The reference's 20 shape goldens are reproduced with tolerance 0.
- * Out of scope: custom SVG shapes (PlacedShape::custom_shape_data — kurbo polylines with 4-sample supersampling, :1065-1163).
+ * Custom path shapes (PlacedShape::custom_shape_data — polylines with 4-sample supersampling, :1065-1163) have their own section below: pfx_custom_shape_*.
  * The struct is always passed by pointer.  kind >= PFX_SHAPE_COUNT, fill_mode > PFX_SHAPE_BOTH or a non-finite cx / cy / hw / hh / rotation (the reference's
  * `as i32` would saturate the box to the whole canvas) return PFX_ERR_INVALID. */
 typedef enum pfx_shape_kind { /* ShapeKind's declaration order, shapes.rs:159-178 */
@@ -807,6 +807,43 @@ int pfx_shape_preview_dev(pfx_ctx* ctx, const pfx_shape* shape, uint32_t canvas_
  * the same blend mode and selection (canvas_w*canvas_h bytes or NULL).  Layer pixels outside the box are neither read nor written. */
 int pfx_shape_draw_dev(pfx_ctx* ctx, void* layer_dev, uint32_t canvas_w, uint32_t canvas_h, const pfx_shape* shape, uint8_t blend_mode,
                        const void* selection_dev /* may be NULL */);
+
+/* ================= shape tool: custom path shapes (ref: src/ops/shapes.rs:1065-1163, the custom branch of rasterize_shape :1241-1248) =================
+ * A PlacedShape with custom_shape_data: per pixel four sub-samples at (+-0.25, +-0.25); each sample is mapped into the path's bounds, tested for crossing parity
+ * over every segment of every polyline (even-odd fill) and, in Outline and Both mode, for its distance to the nearest segment against max(outline_width, 1).
+ * Coverage is the count of samples times 0.25; the colour is `primary` in all three fill modes.  `+ - * /`, sqrt and comparisons only: bit-exact class.  The
+ * reference has no golden of these functions; the yardstick is tests/customshape_model.py, itself held to a scalar transcription and hand-derived answers.
+ * Of pfx_shape, `secondary`, `anti_alias` and `corner_radius` are ignored, and `kind` is used for the bounding box alone (the reference leaves the previously
+ * selected built-in kind in PlacedShape::kind, and shape_local_corners reads it): the box is pfx_shape_bounds, unchanged.
+ * The path is HOST memory in every tier, `_dev` calls included: polylines in, pixels out.  It is flattened to segments, checked and staged into context scratch
+ * once per call; nothing is cached between calls.  A polyline of 0 or 1 points contributes no segment; a path without any segment is accepted and draws nothing.
+ * PFX_ERR_INVALID, with the output untouched: a NULL pointer, a non-finite point or bound, more than PFX_CUSTOM_SHAPE_MAX_SEGMENTS segments, what
+ * pfx_shape_bounds refuses (kind, fill_mode > PFX_SHAPE_BOTH, non-finite cx / cy / hw / hh / rotation), a non-finite outline_width, an icon size of 0 or above 1024.
+ * Out of scope: extract_svg_path_data / parse_custom_shape (:27-120: kurbo's BezPath::from_svg and flatten, a third-party crate whose flattening cannot be
+ * pinned here), the texture upload of the icon, the picker UI. */
+typedef struct pfx_custom_path {          /* CustomShapeRenderData, shapes.rs:13 */
+    const float*    points_xy;            /* every polyline's points, x y interleaved, host memory */
+    const uint32_t* polyline_points;      /* points per polyline */
+    uint32_t        n_polylines;
+    float           bounds[4];            /* min_x, min_y, max_x, max_y */
+} pfx_custom_path;
+#define PFX_CUSTOM_SHAPE_MAX_SEGMENTS 65536u
+/* host only, no context: windows(2) of every polyline, in order, as x1 y1 x2 y2 (what the kernel reads).  *n_segments is the path's count; seg_xyxy may be NULL
+ * with cap 0 to ask for the count alone.  PFX_ERR_INVALID for a refused path (above) or a count above cap. */
+int pfx_custom_shape_segments(const pfx_custom_path* path, float* seg_xyxy, uint32_t cap, uint32_t* n_segments);
+/* the three forms of pfx_shape_rasterize / pfx_shape_preview / pfx_shape_draw_dev, with the same contracts; w, h are the canvas.  buf = the box buffer, bit for
+ * bit the reference's `buf` (bw*bh*4 bytes; an empty box: PFX_OK, buffer untouched); preview = the whole canvas, every byte written; draw on image_dev, the
+ * layer (w*h*4), equals preview followed by pfx_brush_commit with sel_dev as the selection (w*h bytes) and neither reads nor writes outside the box. */
+int pfx_custom_shape_rasterize(pfx_ctx* ctx, const pfx_shape* shape, const pfx_custom_path* path, uint32_t w, uint32_t h, uint8_t* buf_rgba);
+int pfx_custom_shape_rasterize_dev(pfx_ctx* ctx, const pfx_shape* shape, const pfx_custom_path* path, uint32_t w, uint32_t h, void* buf_dev);
+int pfx_custom_shape_preview(pfx_ctx* ctx, const pfx_shape* shape, const pfx_custom_path* path, uint32_t w, uint32_t h, uint8_t* preview_rgba);
+int pfx_custom_shape_preview_dev(pfx_ctx* ctx, const pfx_shape* shape, const pfx_custom_path* path, uint32_t w, uint32_t h, void* preview_dev);
+int pfx_custom_shape_draw_dev(pfx_ctx* ctx, void* image_dev, uint32_t w, uint32_t h, const pfx_shape* shape, const pfx_custom_path* path, uint8_t blend_mode,
+                              const void* sel_dev /* may be NULL */);
+/* the shape picker's icon (render_custom_shape_icon :122-155): size x size RGBA8, 16 samples per pixel at (x + (s + 0.5) * 0.25) / size * 2 - 1, the path fitted
+ * to half extents 0.82, Filled.  Where the coverage is above 0: grey 235 (dark != 0) or 30 in r, g, b and alpha (255 * cov).round(); every other pixel is zero. */
+int pfx_custom_shape_icon(pfx_ctx* ctx, const pfx_custom_path* path, uint32_t size, int dark, uint8_t* rgba /* size*size*4 */);
+int pfx_custom_shape_icon_dev(pfx_ctx* ctx, const pfx_custom_path* path, uint32_t size, int dark, void* rgba_dev);
 
 /* ================= content-aware fill (ref: src/ops/inpaint.rs) =================
  * Images are w*h RGBA8, the hole mask is w*h bytes (> 0 = pixel to fill).  Both routines are in the bit-exact class: the reference's two inpaint goldens are

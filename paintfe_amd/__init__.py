@@ -10,7 +10,7 @@ from .renderer import (ADJUST_OPS, BLEND_MODES, DENSE, FROM_FLAT, IN_PLACE, RHAI
                        overlay, overlay_geometry, script_check, select_span, shape_bounds, text_block, text_effects, text_effects_plan, text_rotate_plan, text_warp, text_warp_plan, textfx_span,
                        tolerance_threshold, GRADIENT_PRESETS, GRADIENT_SHAPES, gradient, gradient_bake_eraser_lut, gradient_drag_scale, gradient_lut, gradient_preset_stops,
                        perspective_crop_plan, clone_stamp_tool, heal_ring_tool, pencil_line_cells, stroke_line_points, line_tool, line_bounds, line_plan,
-                       LINE_PATTERNS, LINE_CAPS, LINE_END_SHAPES, LINE_ARROW_SIDES, matte_settings)
+                       LINE_PATTERNS, LINE_CAPS, LINE_END_SHAPES, LINE_ARROW_SIDES, matte_settings, CustomPath, custom_shape_segments)
 
 from .project import PfeError, Project  # noqa: F401,E402
 
@@ -20,4 +20,4 @@ __all__ = ["GpuRenderer", "PfxError", "load", "LIB_PATH", "BLEND_MODES", "ADJUST
            "text_warp", "text_warp_plan", "text_rotate_plan", "text_block", "GRADIENT_SHAPES", "GRADIENT_PRESETS", "gradient", "gradient_lut",
            "gradient_preset_stops", "gradient_bake_eraser_lut", "gradient_drag_scale", "perspective_crop_plan", "clone_stamp_tool",
            "heal_ring_tool", "stroke_line_points", "pencil_line_cells", "line_tool", "line_bounds", "line_plan", "LINE_PATTERNS", "LINE_CAPS",
-           "LINE_END_SHAPES", "LINE_ARROW_SIDES", "matte_settings"]
+           "LINE_END_SHAPES", "LINE_ARROW_SIDES", "matte_settings", "CustomPath", "custom_shape_segments"]

@@ -68,6 +68,10 @@ class Shape(C.Structure):   # pfx_shape
                 ("anti_alias", C.c_uint8), ("_pad", C.c_uint8)]
 
 
+class CustomPath(C.Structure):   # pfx_custom_path
+    _fields_ = [("points_xy", C.c_void_p), ("polyline_points", C.c_void_p), ("n_polylines", C.c_uint32), ("bounds", C.c_float * 4)]
+
+
 class InpaintDab(C.Structure):   # pfx_inpaint_dab
     _fields_ = [("cx", C.c_float), ("cy", C.c_float), ("brush_radius", C.c_float), ("sample_radius", C.c_float), ("hardness", C.c_float)]
 
@@ -244,5 +248,13 @@ def load() -> C.CDLL:
                                                                                    C.POINTER(MatteSettings), C.c_void_p, C.c_void_p]
     lib.pfx_int_matte_info.restype = C.c_int
     lib.pfx_int_matte_info.argtypes = [C.c_int]
+    _cs = [C.c_void_p, C.POINTER(Shape), C.POINTER(CustomPath), _u32, _u32, C.c_void_p]
+    lib.pfx_custom_shape_rasterize.argtypes = lib.pfx_custom_shape_rasterize_dev.argtypes = _cs
+    lib.pfx_custom_shape_preview.argtypes = lib.pfx_custom_shape_preview_dev.argtypes = _cs
+    lib.pfx_custom_shape_draw_dev.argtypes = [C.c_void_p, C.c_void_p, _u32, _u32, C.POINTER(Shape), C.POINTER(CustomPath), C.c_uint8, C.c_void_p]
+    lib.pfx_custom_shape_icon.argtypes = lib.pfx_custom_shape_icon_dev.argtypes = [C.c_void_p, C.POINTER(CustomPath), _u32, C.c_int, C.c_void_p]
+    lib.pfx_custom_shape_segments.argtypes = [C.POINTER(CustomPath), C.c_void_p, _u32, C.POINTER(_u32)]
+    lib.pfx_int_customshape_info.restype = lib.pfx_int_customshape_cull.restype = C.c_int
+    lib.pfx_int_customshape_info.argtypes = lib.pfx_int_customshape_cull.argtypes = [C.c_int]
     _lib = lib
     return lib

@@ -1,4 +1,5 @@
-// k_shapes.hip — the shape tool's rasteriser: the 17 built-in SDF shapes of src/ops/shapes.rs (custom SVG shapes are out of scope).
+// k_shapes.hip — the shape tool's rasteriser: the 17 built-in SDF shapes of src/ops/shapes.rs (custom path shapes: k_customshape.hip; what the two share:
+// k_shape_pixel.h).
 //
 // Reference: rasterize_shape (src/ops/shapes.rs:1169-1305) — per pixel centre of the shape's bounding box: inverse-rotate into the shape's frame,
 // shape_sdf (:827, the sdf_* functions :357-824), coverage_from_sdf / smoothstep (:850, :1441), the fill / outline / both colour mix (:1251-1290) and
@@ -21,8 +22,7 @@
 // Three forms of one kernel: the box buffer (`buf` of the reference), the whole-canvas preview (tests/visual_shapes.rs:18-41: box pixels with a > 0 on
 // a zeroed canvas), and rasterise + commit in place (blend_pixel_static(layer, pixel, mode, 1.0) where a > 0 and the selection allows: what
 // pfx_brush_commit does with the preview) without an intermediate buffer.
-#include "k_tools.h"
-#include "k_blend.h"
+#include "k_shape_pixel.h"
 #include "pfx_kernels.h"
 
 using namespace pfxk;
@@ -166,10 +166,8 @@ PFX_DEV float coverage_from_sdf(float d, int aa) // :850; smoothstep(0.5, -0.5, 
 template <int SDF>
 PFX_DEV uint32_t shape_pixel(int col, int row, const pfxk_shape_params& P)
 {
-    const float px_canvas = (float)(P.x0 + col) + 0.5f, py_canvas = (float)(P.y0 + row) + 0.5f;
-    const float dx = px_canvas - P.cx, dy = py_canvas - P.cy;
-    const float lx = dx * P.inv_cos - dy * P.inv_sin;
-    const float ly = dx * P.inv_sin + dy * P.inv_cos;
+    float lx, ly;
+    shape_local(col, row, P, lx, ly);
     const float d = shape_sdf<SDF>(lx, ly, P);
     const int aa = P.anti_alias;
     uint32_t color = P.primary;
@@ -194,9 +192,7 @@ PFX_DEV uint32_t shape_pixel(int col, int row, const pfxk_shape_params& P)
             }
         }
     }
-    if (!(coverage > 0.001f)) return 0u;
-    // (a * cov).round().min(255.0) as u8: the product is in [0, 255], where round_u8f's clamp is the reference's min
-    return (color & 0x00ffffffu) | ((uint32_t)round_u8f(ubyte3(color) * coverage) << 24);
+    return shape_quantise(color, coverage);
 }
 
 // FORM 0: out = the box buffer (bw * bh); 1: out = the canvas (every pixel written); 2: out = the layer, committed in place over the box
@@ -204,7 +200,7 @@ template <int SDF, int FORM>
 __global__ __launch_bounds__(256) void shape_kernel(const pfxk_shape_params P, uint32_t* __restrict__ out, const uint8_t* __restrict__ selection,
                                                     uint32_t mode, int canvas_w, int canvas_h)
 {
-    const int tx = blockIdx.x * 64 + (threadIdx.x & 63), ty = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int tx = shape_tile_x(), ty = shape_tile_y();
     if constexpr (FORM == 1) {
         if (tx >= canvas_w || ty >= canvas_h) return;
         const int col = tx - P.x0, row = ty - P.y0;
@@ -215,23 +211,14 @@ __global__ __launch_bounds__(256) void shape_kernel(const pfxk_shape_params P, u
         if (tx >= P.bw || ty >= P.bh) return;
         const uint32_t px = shape_pixel<SDF>(tx, ty, P);
         if constexpr (FORM == 0) out[(size_t)ty * P.bw + tx] = px;
-        else {
-            if ((px >> 24) == 0u) return;
-            const size_t i = (size_t)(P.y0 + ty) * canvas_w + (P.x0 + tx);
-            if (selection && selection[i] == 0) return;
-            const uint32_t lp = out[i];
-            float acc[1][4] = {{ubyte0(lp), ubyte1(lp), ubyte2(lp), ubyte3(lp)}};
-            const uint32_t t[1] = {px};
-            blend4_dispatch<true, 1>(mode, acc, t, 1.0f, 1.0f);
-            out[i] = pack_rgba(acc[0][0], acc[0][1], acc[0][2], acc[0][3]);
-        }
+        else shape_commit(out, (size_t)(P.y0 + ty) * canvas_w + (P.x0 + tx), px, selection, mode);
     }
 }
 
 template <int SDF>
 void launch(hipStream_t s, int form, const pfxk_shape_params& P, uint32_t* out, const uint8_t* sel, uint32_t mode, uint32_t cw, uint32_t ch)
 {
-    const dim3 box_grid((P.bw + 63) / 64, (P.bh + 3) / 4), canvas_grid((cw + 63) / 64, (ch + 3) / 4);
+    const dim3 box_grid = shape_tile_grid(P.bw, P.bh), canvas_grid = shape_tile_grid(cw, ch);
     if (form == PFXK_SHAPE_BOX) shape_kernel<SDF, 0><<<box_grid, 256, 0, s>>>(P, out, sel, mode, (int)cw, (int)ch);
     else if (form == PFXK_SHAPE_CANVAS) shape_kernel<SDF, 1><<<canvas_grid, 256, 0, s>>>(P, out, sel, mode, (int)cw, (int)ch);
     else shape_kernel<SDF, 2><<<box_grid, 256, 0, s>>>(P, out, sel, mode, (int)cw, (int)ch);

@@ -1,4 +1,4 @@
-// k_tools.h — what the tool kernels share: k_shapes, k_inpaint, k_flood, k_select, k_colorkey, k_overlay, k_textfx, k_textwarp, k_gradient, k_dabtools, k_linetool and k_colorrange include it, no other file does
+// k_tools.h — what the tool kernels share: k_shapes, k_customshape, k_inpaint, k_flood, k_select, k_colorkey, k_overlay, k_textfx, k_textwarp, k_gradient, k_dabtools, k_linetool and k_colorrange include it, no other file does
 // (the effect bank, the Gaussians and the compositor keep compiling from k_common.h alone).  A new tool kernel starts from here.
 //
 //   launch     stream_blocks / aligned_to / launch_stream for a streaming kernel, tile_grid for one workgroup per tile, dims_ok.

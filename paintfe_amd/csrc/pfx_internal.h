@@ -324,6 +324,12 @@ extern "C" int pfx_int_colorrange_info(int which);
 // most source columns one resize tile may reach, 7 the most at which the tile keeps its full height, 8 its rows beyond that; -1 = unknown `which` (not in include/pfx.h)
 extern "C" int pfx_int_matte_info(int which);
 
+// for the tests and profiles: the custom-shape kernel (k_customshape.hip): which = 0 the segments of one batch, 1 the slots of an LDS segment list, 2 whether
+// culling is on; -1 = unknown `which`.  pfx_int_customshape_cull switches the culling (process-wide, default on) and returns the previous setting: results do
+// not depend on it (not in include/pfx.h)
+extern "C" int pfx_int_customshape_info(int which);
+extern "C" int pfx_int_customshape_cull(int on);
+
 // blur_with_selection on device-resident images (pfx_api.cpp); mask_host may be NULL (= no selection)
 int pfx_int_blur_with_selection_dev(pfx_ctx* ctx, const void* d_src, void* d_dst, uint32_t w, uint32_t h, float sigma,
                                     const uint8_t* mask_host, const void* d_mask);

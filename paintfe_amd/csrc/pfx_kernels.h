@@ -319,6 +319,27 @@ typedef struct pfxk_shape_params { // passed by value: lands in SGPRs / scalar l
 hipError_t pfxk_shape(hipStream_t s, int form, int sdf, const pfxk_shape_params* P, uint8_t* d_out, const uint8_t* d_selection /* COMMIT only, may be NULL */,
                       uint32_t mode /* COMMIT only: BlendMode::to_u8 */, uint32_t canvas_w, uint32_t canvas_h);
 
+// ---- k_customshape.hip ---- the shape tool with a custom path (shapes.rs:1065-1163) and the picker's icon (:122-155); host side: pfx_customshape.cpp
+#define PFXK_CUSTOM_BATCH 256   // segments a workgroup looks at per step, one per lane
+#define PFXK_CUSTOM_LIST 1024   // slots of each LDS segment list: consumed after every fourth batch
+typedef struct pfxk_custom_params { // passed by value; the forms and the box are k_shapes.hip's
+    int32_t  x0, y0, bw, bh;
+    float    cx, cy, inv_cos, inv_sin, hx, hy;
+    float    sx, sy, min_x, min_y;   // custom_shape_coverage_sample :1097-1101
+    float    max_scale;              // sx.max(sy)
+    float    outline_width;          // .max(1.0) applied
+    float    reach;                  // max(outline_width, 1) * max(sx, sy) * (1 + 2^-10), not rounded down: the distance cull's radius before its 2^-16 M
+    float    seg_abs;                // the largest |coordinate| of the segments
+    uint32_t primary;                // r | g << 8 | b << 16 | a << 24
+    int32_t  fill_mode;              // 0 outline, 1 filled, 2 both
+    uint32_t n_segments;
+    int32_t  cull;                   // 0: every segment goes on both lists (profiles/custom_shapes.md)
+} pfxk_custom_params;
+hipError_t pfxk_custom_shape(hipStream_t s, int form /* PFXK_SHAPE_* */, const pfxk_custom_params* P, const float* d_segs /* n_segments * 4, 16-byte aligned */,
+                             uint8_t* d_out, const uint8_t* d_selection /* COMMIT only, may be NULL */, uint32_t mode, uint32_t canvas_w, uint32_t canvas_h);
+hipError_t pfxk_custom_icon(hipStream_t s, const pfxk_custom_params* P /* hx, hy, sx, sy, min_x, min_y, seg_abs, n_segments, cull */, const float* d_segs,
+                            uint8_t* d_out /* size * size pixels */, uint32_t size, uint32_t fg);
+
 // ---- k_inpaint.hip ---- content-aware fill (inpaint.rs): instant heal dabs :76-192 and the onion-peeling PatchMatch :394-520; host side: pfx_inpaint.cpp
 // a dab as the kernel reads it: r = brush_radius.max(1.0), hard_t = (hardness * 0.9 + 0.1).clamp(0, 1), soft_den = 1.0 - hard_t + 1e-6, the dab's own pixel loop
 // bounds [x0, x1] x [y0, y1] (:93-96; x0 > x1 = none), ring = which 64-float set of d_rings (pfx_inpaint_ring_offsets of its sample radius)

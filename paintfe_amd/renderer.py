@@ -131,6 +131,30 @@ def shape_bounds(shape: Shape, canvas_w: int, canvas_h: int):
     return tuple(int(v) for v in box)
 
 
+class CustomPath:
+    """CustomShapeRenderData (ref: src/ops/shapes.rs:13) for the custom_shape_* calls: `polylines` a list of (n, 2) float32 arrays, `bounds` =
+    (min_x, min_y, max_x, max_y).  Host memory; every call flattens, checks and stages it anew."""
+
+    def __init__(self, polylines, bounds):
+        polys = [np.ascontiguousarray(p, np.float32).reshape(-1, 2) for p in polylines]
+        self._points = np.ascontiguousarray(np.concatenate(polys) if polys else np.zeros((0, 2), np.float32))
+        self._counts = np.array([len(p) for p in polys], np.uint32)
+        self.c = _lib.CustomPath(self._points.ctypes.data if self._points.size else None, self._counts.ctypes.data if self._counts.size else None,
+                                 len(polys), (C.c_float * 4)(*[float(b) for b in bounds]))
+
+
+def custom_shape_segments(path: CustomPath) -> np.ndarray:
+    """the (n, 4) float32 segments x1 y1 x2 y2 the kernel reads: windows(2) of every polyline, in order (pfx_custom_shape_segments).  Host only."""
+    lib, n = _lib.load(), C.c_uint32(0)
+    st = lib.pfx_custom_shape_segments(C.byref(path.c), None, C.c_uint32(0), C.byref(n))
+    if st != 0:
+        raise PfxError(st, "pfx_custom_shape_segments: bad path")
+    out = np.zeros((n.value, 4), np.float32)
+    if n.value and lib.pfx_custom_shape_segments(C.byref(path.c), out.ctypes.data_as(C.c_void_p), n, C.byref(n)) != 0:
+        raise PfxError(-1, "pfx_custom_shape_segments: bad path")
+    return out
+
+
 def inpaint_ring_offsets(sample_radius: float) -> np.ndarray:
     """the instant heal brush's 32 candidate offsets as 64 f32, x and y interleaved (inpaint.rs:141-147).  Host only."""
     out = np.zeros(64, np.float32)
@@ -912,6 +936,68 @@ class GpuRenderer:
 
     def rasterize_shape_dev(self, shape: Shape, w: int, h: int, box_ptr: int):
         self._check(self._lib.pfx_shape_rasterize_dev(self._h, C.byref(shape.to_c()), C.c_uint32(w), C.c_uint32(h), C.c_void_p(box_ptr)))
+
+    # ------------------------------------------------------------------ shape tool, custom path shapes (ref: src/ops/shapes.rs:1065-1163, :122-155)
+    custom_shape_segments = staticmethod(custom_shape_segments)
+
+    def rasterize_custom_shape(self, shape: Shape, path: CustomPath, canvas_w: int, canvas_h: int):
+        """rasterize_shape with custom_shape_data: (buf, (x0, y0, bw, bh)); shape.kind only shapes the box"""
+        box = shape_bounds(shape, canvas_w, canvas_h)
+        buf = np.zeros((box[3], box[2], 4), np.uint8)
+        if buf.size:
+            self._check(self._lib.pfx_custom_shape_rasterize(self._h, C.byref(shape.to_c()), C.byref(path.c), canvas_w, canvas_h, _p(buf)))
+        return buf, box
+
+    def custom_shape_preview(self, shape: Shape, path: CustomPath, canvas_w: int, canvas_h: int):
+        out = np.empty((canvas_h, canvas_w, 4), np.uint8)
+        self._check(self._lib.pfx_custom_shape_preview(self._h, C.byref(shape.to_c()), C.byref(path.c), canvas_w, canvas_h, _p(out)))
+        return out
+
+    def draw_custom_shape(self, layer, shape: Shape, path: CustomPath, blend_mode: int = 0, selection=None):
+        """rasterise and commit into a copy of `layer` on the device (pfx_custom_shape_draw_dev): custom_shape_preview + brush_commit in one kernel"""
+        l = _u8(layer)
+        h, w = l.shape[:2]
+        sel = None if selection is None else _u8(selection)
+        d_layer = self.dev_alloc(l.nbytes)
+        d_sel = self.dev_alloc(sel.nbytes) if sel is not None else 0
+        try:
+            self.dev_upload(d_layer, l)
+            if sel is not None:
+                self.dev_upload(d_sel, sel)
+            self.draw_custom_shape_dev(d_layer, w, h, shape, path, blend_mode, d_sel)
+            return self.dev_download(d_layer, l.shape)
+        finally:
+            self.dev_free(d_layer)
+            if d_sel:
+                self.dev_free(d_sel)
+
+    def draw_custom_shape_dev(self, layer_ptr: int, w: int, h: int, shape: Shape, path: CustomPath, blend_mode: int = 0, selection_ptr: int = 0):
+        self._check(self._lib.pfx_custom_shape_draw_dev(self._h, C.c_void_p(layer_ptr), w, h, C.byref(shape.to_c()), C.byref(path.c), blend_mode,
+                                                        C.c_void_p(selection_ptr or None)))
+
+    def custom_shape_preview_dev(self, shape: Shape, path: CustomPath, w: int, h: int, canvas_ptr: int):
+        self._check(self._lib.pfx_custom_shape_preview_dev(self._h, C.byref(shape.to_c()), C.byref(path.c), w, h, C.c_void_p(canvas_ptr)))
+
+    def rasterize_custom_shape_dev(self, shape: Shape, path: CustomPath, w: int, h: int, box_ptr: int):
+        self._check(self._lib.pfx_custom_shape_rasterize_dev(self._h, C.byref(shape.to_c()), C.byref(path.c), w, h, C.c_void_p(box_ptr)))
+
+    def custom_shape_icon(self, path: CustomPath, size: int, dark: bool):
+        """render_custom_shape_icon: (size, size, 4)"""
+        out = np.empty((size, size, 4), np.uint8)
+        self._check(self._lib.pfx_custom_shape_icon(self._h, C.byref(path.c), size, int(bool(dark)), _p(out)))
+        return out
+
+    def custom_shape_icon_dev(self, path: CustomPath, size: int, dark: bool, rgba_ptr: int):
+        self._check(self._lib.pfx_custom_shape_icon_dev(self._h, C.byref(path.c), size, int(bool(dark)), C.c_void_p(rgba_ptr)))
+
+    def customshape_info(self, which: int) -> int:
+        """0 the segments of one batch of the custom-shape kernel, 1 the slots of its LDS segment lists, 2 whether culling is on (pfx_int_customshape_info;
+        for tests and profiles)"""
+        return int(self._lib.pfx_int_customshape_info(which))
+
+    def customshape_cull(self, on: bool) -> bool:
+        """switch the kernel's segment culling (process-wide; results do not depend on it); returns the previous setting.  For tests and profiles"""
+        return bool(self._lib.pfx_int_customshape_cull(int(bool(on))))
 
     # ------------------------------------------------------------------ content-aware fill (ref: src/ops/inpaint.rs)
     inpaint_ring_offsets = staticmethod(inpaint_ring_offsets)

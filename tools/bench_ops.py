@@ -20,6 +20,74 @@ sys.path.insert(0, ROOT)
 HBM_PEAK = 8000.0
 
 
+def custom_shape_kept(shape, path, side):
+    """host restatement of the kernel's culling (k_customshape.hip, header 3): the average number of segments on a 64 x 4 tile's parity list and on its
+    distance list, over the tiles of the side x side box, from the same f32 values the kernel compares"""
+    from tests import customshape_model as CM
+    from tests import shape_model as M
+    F = np.float32
+    box = M.bounds(shape, side, side)
+    assert box == (0, 0, side, side)
+    lx, ly = CM.local_frame(shape, box)
+    sx, sy = CM.scales(path, shape["hw"], shape["hh"])
+    tw, th = -(-side // 64), -(-side // 4)
+
+    def tile_range(v):   # min and max of a tile's sample coordinates: both offsets, every pixel of the tile (lanes outside the box repeat an edge pixel)
+        lo = np.full((th * 4, tw * 64), np.inf, F)
+        hi = np.full((th * 4, tw * 64), -np.inf, F)
+        a, b = v[0].reshape(side, side), v[1].reshape(side, side)
+        lo[:side, :side], hi[:side, :side] = np.minimum(a, b), np.maximum(a, b)
+        return lo.reshape(th, 4, tw, 64).min((1, 3)).ravel(), hi.reshape(th, 4, tw, 64).max((1, 3)).ravel()
+    px = [((lx + o) + shape["hw"]) * sx + path["bounds"][0] for o in (F(-0.25), F(0.25))]
+    py = [((ly + o) + shape["hh"]) * sy + path["bounds"][1] for o in (F(-0.25), F(0.25))]
+    (xlo, xhi), (ylo, yhi) = tile_range(px), tile_range(py)
+    segs = CM.segments(path)
+    ms, ow = max(sx, sy), max(F(shape["outline_width"]), F(1))
+    m = np.maximum(np.maximum(np.abs(xlo), np.abs(xhi)), np.maximum(np.abs(ylo), np.abs(yhi)))
+    m = np.maximum(m, np.abs(segs).max()).astype(F)
+    reach = (np.nextafter(F(float(ow) * float(ms) * (1 + 1 / 1024)), F(np.inf)) + m * F(2.0 ** -16)).astype(F)[:, None]
+    kept_p = kept_d = 0
+    for k in range(0, len(segs), 512):
+        x1, y1, x2, y2 = (segs[k:k + 512, c][None, :] for c in range(4))
+        slo, shi = np.minimum(y1, y2), np.maximum(y1, y2)
+        kept_p += int(((np.abs(y2 - y1) > F(1e-6)) & ~(shi <= ylo[:, None]) & ~(slo > yhi[:, None])).sum())
+        gx = np.maximum(np.minimum(x1, x2) - xhi[:, None], xlo[:, None] - np.maximum(x1, x2))
+        gy = np.maximum(slo - yhi[:, None], ylo[:, None] - shi)
+        kept_d += int((~((gx > reach) | (gy > reach))).sum())
+    return kept_p / len(xlo), kept_d / len(xlo)
+
+
+def custom_shape_rows(r, timed, torch):
+    from paintfe_amd import CustomPath
+    from tests import customshape_cases as CC
+    from tests import customshape_model as CM
+    from tests import shape_cases as SC
+    side = 1500
+    box = torch.empty((side, side, 4), dtype=torch.uint8, device="cuda")
+    for n in (200, 2000, 20000):
+        th = np.arange(n) * (2 * math.pi / n)   # a smooth closed curve flattened into n chords: five lobes and a ripple
+        rad = 380.0 * (1 + 0.22 * np.sin(5 * th) + 0.08 * np.sin(13 * th + 1.0))
+        pts = np.stack([500 + rad * np.cos(th), 500 + rad * np.sin(th)], 1).astype(np.float32)
+        path = CM.path([np.concatenate([pts, pts[:1]])], (0, 0, 1000, 1000))
+        cp = CustomPath(path["polylines"], path["bounds"])
+        for rot in (0.0, 0.4):
+            kp, kd = custom_shape_kept(CC.shape("both", cx=750.0, cy=750.0, hw=748.0, hh=748.0, rotation=rot, outline_width=3.0), path, side)
+            for fill in ("filled", "outline", "both"):
+                shape = CC.shape(fill, cx=750.0, cy=750.0, hw=748.0, hh=748.0, rotation=rot, outline_width=3.0)
+                api = SC.to_api(shape)
+                assert r.shape_bounds(api, side, side) == (0, 0, side, side)
+                tested = f"{kp:.1f} parity" + ("" if fill == "filled" else f" + {kd:.1f} distance")
+                for cull in (True, False):
+                    was = r.customshape_cull(cull)
+                    try:
+                        timed(f"custom shape {fill}, {n} segments, rotation {rot}, culling {'on' if cull else 'off'}", ["custom_shape_rasterize"],
+                              lambda: r.rasterize_custom_shape_dev(api, cp, side, side, box.data_ptr()), side * side, 4,
+                              f"segments tested per sample: {tested if cull else str(n) + ' on every list'}", reps=3 if not cull and n >= 2000 else None,
+                              warm=cull or n < 2000)
+                    finally:
+                        r.customshape_cull(was)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
@@ -129,6 +197,12 @@ def main() -> int:
     timed("median r=4", ["median"], lambda: r.median_dev(s, d, w, h, 4), px, 8, "bit-plane radix select")
     timed("median r=5", ["median"], lambda: r.median_dev(s, d, w, h, 5), px, 8, "bit-plane radix select")
     timed("median r=7", ["median"], lambda: r.median_dev(s, d, w, h, 7), px, 8, "225-element windows, bit-plane radix select")
+    # ---------------- custom shape (k_customshape.hip): a 1500 x 1500 box, a smooth closed path of 200 / 2 000 / 20 000 segments, the three fill modes, rotation 0
+    # and 0.4 rad, each with the culling on and off.  The note carries the host-computed average number of segments a sample is tested against (parity list,
+    # distance list) with the culling; without it, it is the segment count for both.  The timer starts after the path's flattening and upload.
+    if not args.only or "custom shape" in args.only or args.only in "custom shape":
+        custom_shape_rows(r, timed, torch)
+
     # ---------------- the rest of the effect bank (k_effects2.hip), script VM, resamplers
     timed("pixelate block=8", ["pixelate"], lambda: r.pixelate_dev(s, d, w, h, 8), px, 8, "A6: nearest sample at the block centre (reads 1 / 64 of the pixels)")
     timed("vignette", ["vignette"], lambda: r.vignette_dev(s, d, w, h, 0.8, 0.5), px, 8)

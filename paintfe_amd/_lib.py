@@ -256,5 +256,8 @@ def load() -> C.CDLL:
     lib.pfx_custom_shape_segments.argtypes = [C.POINTER(CustomPath), C.c_void_p, _u32, C.POINTER(_u32)]
     lib.pfx_int_customshape_info.restype = lib.pfx_int_customshape_cull.restype = C.c_int
     lib.pfx_int_customshape_info.argtypes = lib.pfx_int_customshape_cull.argtypes = [C.c_int]
+    lib.pfx_int_warp_last.restype = lib.pfx_int_warp_info.restype = C.c_int
+    lib.pfx_int_warp_last.argtypes = [C.c_void_p, C.c_int]
+    lib.pfx_int_warp_info.argtypes = [C.c_int]
     _lib = lib
     return lib

@@ -334,6 +334,7 @@ __global__ __launch_bounds__(256) void mesh_kernel(const float2* __restrict__ g_
 // (profiles/r04_tuning.md): 32 x 1 0.447 ms, 16 x 1 0.48, 8 x 1 0.52, 32 x 4 0.434, 48 x 4 0.422, 64 x 4 0.427 — a workgroup writes 1 KB runs of a row, and the
 // u-dependent half of the surface is set up once per 48 rows
 constexpr uint32_t MESH_WALK = PFX_MESH_WALK, MESH_WX = PFX_MESH_WX;
+constexpr uint32_t MESH_XCD_MIN_ROWS = 16; // tile rows from which pfxk_warp_mesh takes the XCD-aware order: two per XCD
 static_assert(MESH_WALK <= 64 && (MESH_WX == 1 || MESH_WX == 2 || MESH_WX == 4), "mesh_roll_kernel: lane k evaluates row k; 4 waves per workgroup");
 // Rolling form of the fused warp (round 4): D rows' taps in flight all the time — row k + D is requested as soon as row k has been interpolated —
 // instead of batches of eight requested together and then consumed together; 7 D registers of taps instead of 56, so more waves fit.
@@ -420,15 +421,19 @@ __global__ __launch_bounds__(256) void mesh_roll_kernel(const uint32_t* __restri
 
 } // namespace
 
+int g_warp_buf32 = 1; // pfxk_warp_set_buf32 (pfx_tune "warp_buf32"): 0 = both warps address the source with 64-bit pointers whatever its size (the >= 4 GiB forms)
+extern "C" void pfxk_warp_set_buf32(int on) { g_warp_buf32 = on; }
 extern "C" hipError_t pfxk_warp_displacement(hipStream_t s, const uint8_t* d_src, uint32_t sw, uint32_t sh,
-                                             const float* d_disp, uint32_t w, uint32_t h, uint8_t* d_dst, uint32_t first_row)
+                                             const float* d_disp, uint32_t w, uint32_t h, uint8_t* d_dst, uint32_t first_row, pfxk_warp_plan* plan)
 {
+    if (plan) *plan = pfxk_warp_plan{0, 0u, 0u};
     if (w == 0 || h == 0) return hipSuccess;
     dim3 g((w + 63) / 64, (h + 4 * WARP_YR - 1) / (4 * WARP_YR));
-    const bool buf32 = sw >= 2u && sw < (1u << 24) && sh < (1u << 24) && (uint64_t)sw * sh * 4u < (1ull << 32);   // 32-bit byte offsets through a buffer resource
+    const bool buf32 = g_warp_buf32 && sw >= 2u && sw < (1u << 24) && sh < (1u << 24) && (uint64_t)sw * sh * 4u < (1ull << 32);   // 32-bit byte offsets through a buffer resource
 #define PFX_WD(P, B) warp_disp_kernel<P, B><<<g, 256, 0, s>>>((const uint32_t*)d_src, (int32_t)sw, (int32_t)sh, (const float2*)d_disp, w, h, (uint32_t*)d_dst, first_row)
     if (buf32) PFX_WD(true, true); else if (sw >= 2u) PFX_WD(true, false); else PFX_WD(false, false);
 #undef PFX_WD
+    if (plan) *plan = pfxk_warp_plan{(sw >= 2u ? PFXK_WARP_PAIR : 0) | (buf32 ? PFXK_WARP_BUF32 : 0), g.x, g.y};
     return hipGetLastError();
 }
 
@@ -439,6 +444,7 @@ extern "C" hipError_t pfxk_warp_displacement(hipStream_t s, const uint8_t* d_src
 // (pfx_displacement_brush) and the reference's bit for bit.
 // CHUNKED: the launch runs over the 64 x 64 chunks some dab's box touches (`chunks[blockIdx.x]` = chunk x | chunk y << 16, built by the host) instead of the
 // dabs' common bounding box, which for dabs spread over a large field is mostly untouched
+constexpr uint32_t DAB_CULL = 64; // dabs culled per trip: one per lane of the wave
 template <bool CHUNKED>
 __global__ __launch_bounds__(256) void disp_brush_kernel(float2* __restrict__ disp, uint32_t w, const pfxk_disp_dab* __restrict__ dabs, uint32_t n,
                                                          int bx0, int by0, int bx1, int by1, const uint32_t* __restrict__ chunks)
@@ -488,7 +494,7 @@ __global__ __launch_bounds__(256) void disp_brush_kernel(float2* __restrict__ di
             d.y += dx * weight * 0.1f;
         }
     };
-    for (uint32_t k0 = 0; k0 < n; k0 += 64u) {
+    for (uint32_t k0 = 0; k0 < n; k0 += DAB_CULL) {
         const uint32_t kk = k0 + lane;
         bool seen = false;
         if (kk < n) seen = !(seg_hi <= dabs[kk].x0 || px0 >= dabs[kk].x1 || py < dabs[kk].y0 || py >= dabs[kk].y1);
@@ -524,10 +530,12 @@ extern "C" hipError_t pfxk_disp_brushes_chunked(hipStream_t s, float* d_disp, ui
 }
 
 extern "C" hipError_t pfxk_mesh_displacement(hipStream_t s, const float* d_orig, const float* d_def, uint32_t cols,
-                                             uint32_t rows, uint32_t w, uint32_t h, float* d_disp)
+                                             uint32_t rows, uint32_t w, uint32_t h, float* d_disp, pfxk_warp_plan* plan)
 {
+    if (plan) *plan = pfxk_warp_plan{0, 0u, 0u};
     if (w == 0 || h == 0) return hipSuccess;
     dim3 g((w + 63) / 64, (h + 4 * MESH_YR * MESH_YB - 1) / (4 * MESH_YR * MESH_YB));
+    if (plan) *plan = pfxk_warp_plan{(cols + 1u) * (rows + 1u) <= MESH_LDS_PTS ? PFXK_WARP_IN_LDS : 0, g.x, g.y};
     if ((cols + 1u) * (rows + 1u) <= MESH_LDS_PTS)
         mesh_kernel<true><<<g, 256, (size_t)(cols + 1u) * (rows + 1u) * 16u, s>>>((const float2*)d_orig, (const float2*)d_def, cols, rows, w, h, (float2*)d_disp, 0u, h);
     else
@@ -539,17 +547,20 @@ int g_mesh_xcd = 1; // pfxk_warp_set_mesh_xcd (pfx_tune "mesh_xcd"): XCD-aware t
 extern "C" void pfxk_warp_set_mesh_xcd(int on) { g_mesh_xcd = on; }
 // band form: d_dst holds rows [first_row, first_row + h) of an h_full-row result; d_src is the whole w x h_full source
 extern "C" hipError_t pfxk_warp_mesh(hipStream_t s, const uint8_t* d_src, const float* d_orig, const float* d_def,
-                                     uint32_t cols, uint32_t rows, uint32_t w, uint32_t h, uint8_t* d_dst, uint32_t first_row, uint32_t h_full)
+                                     uint32_t cols, uint32_t rows, uint32_t w, uint32_t h, uint8_t* d_dst, uint32_t first_row, uint32_t h_full, pfxk_warp_plan* plan)
 {
+    if (plan) *plan = pfxk_warp_plan{0, 0u, 0u};
     if (w == 0 || h == 0) return hipSuccess;
     dim3 g((w + 64 * MESH_WX - 1) / (64 * MESH_WX), (h + MESH_WALK * (4 / MESH_WX) - 1) / (MESH_WALK * (4 / MESH_WX)));
     // rows in flight per lane: 2 measured best at 16K (profiles/r04_tuning.md: 0.565 ms against 0.573-0.59 for 3 / 4, 0.63 for 6 and for round 3's batches of 8)
     constexpr int ROLL = PFX_MESH_ROLL;
     const size_t lds = (size_t)(cols + 1u) * (rows + 1u) * 16u;
     const bool in_lds = (cols + 1u) * (rows + 1u) <= MESH_LDS_PTS;
-    const bool buf32 = w >= 2u && w < (1u << 24) && h_full < (1u << 24) && (uint64_t)w * h_full * 4u < (1ull << 32);
+    const bool buf32 = g_warp_buf32 && w >= 2u && w < (1u << 24) && h_full < (1u << 24) && (uint64_t)w * h_full * 4u < (1ull << 32);
     uint32_t gx = 0u, gy = 0u;
-    if (g_mesh_xcd && g.y >= 16u) {   // XCD-aware tile order (mesh_roll_kernel); small launches keep the plain 2-D grid
+    if (plan) *plan = pfxk_warp_plan{(in_lds ? PFXK_WARP_IN_LDS : 0) | (w >= 2u ? PFXK_WARP_PAIR : 0) | (buf32 ? PFXK_WARP_BUF32 : 0) |
+                                     (g_mesh_xcd && g.y >= MESH_XCD_MIN_ROWS ? PFXK_WARP_XCD : 0), g.x, g.y};   // the tile grid, also when the launch is one-dimensional
+    if (g_mesh_xcd && g.y >= MESH_XCD_MIN_ROWS) {   // XCD-aware tile order (mesh_roll_kernel); small launches keep the plain 2-D grid
         gx = g.x; gy = g.y;
         g = dim3(8u * ((gy + 7u) / 8u) * gx, 1u);
     }
@@ -558,4 +569,17 @@ extern "C" hipError_t pfxk_warp_mesh(hipStream_t s, const uint8_t* d_src, const 
     else { if (buf32) PFX_ROLL(false, true, true); else if (w >= 2u) PFX_ROLL(false, true, false); else PFX_ROLL(false, false, false); }
 #undef PFX_ROLL
     return hipGetLastError();
+}
+
+extern "C" int pfxk_warp_info(int which)
+{
+    switch (which) {
+        case 0: return (int)MESH_WALK;
+        case 1: return (int)MESH_WX;
+        case 2: return (int)MESH_LDS_PTS;
+        case 3: return (int)WARP_YR;
+        case 4: return (int)MESH_XCD_MIN_ROWS;
+        case 5: return (int)DAB_CULL;
+        default: return -1;
+    }
 }

@@ -379,7 +379,8 @@ int pfx_warp_displacement_band_dev(pfx_ctx* ctx, const void* src_dev, uint32_t s
     PFX_TRY(check_warp(ctx, "pfx_warp_displacement_dev", true, src_dev, sw, sh, disp_band_dev, w, band_rows, dst_band_dev));
     PFX_REQUIRE(ctx, (uint64_t)first_row + band_rows <= 0x7fffffffull, "pfx_warp_displacement_dev: band outside any image");
     pfx_timer t(ctx, "warp_displacement");
-    PFX_HIP(ctx, pfxk_warp_displacement(ctx->stream, (const uint8_t*)src_dev, sw, sh, (const float*)disp_band_dev, w, band_rows, (uint8_t*)dst_band_dev, first_row));
+    PFX_HIP(ctx, pfxk_warp_displacement(ctx->stream, (const uint8_t*)src_dev, sw, sh, (const float*)disp_band_dev, w, band_rows, (uint8_t*)dst_band_dev, first_row,
+                                        &ctx->last_warp));
     return PFX_OK;
 }
 
@@ -396,6 +397,8 @@ int pfx_displacement_brushes_dev(pfx_ctx* ctx, void* disp_dev, uint32_t w, uint3
     PFX_TRY(pfx_check_dims(ctx, "pfx_displacement_brushes_dev", w, h));
     PFX_TRY(pfx_check_args(ctx, "pfx_displacement_brushes_dev", true, {{disp_dev, (size_t)w * h * 8, PFX_ARG_OUT, "disp_dev"}}));
     PFX_REQUIRE(ctx, n_dabs == 0 || dabs, "pfx_displacement_brushes_dev: null dab list");
+    ctx->last_dab_launch = 0;   // nothing launched, unless the list reaches the canvas
+    ctx->last_dab_chunks = 0;
     if (n_dabs == 0) return PFX_OK;
     auto f2i = [](float v) -> int32_t { return v != v ? 0 : (v >= 2147483648.0f ? 2147483647 : (v <= -2147483648.0f ? (-2147483647 - 1) : (int32_t)v)); };
     std::vector<pfxk_disp_dab> k(n_dabs);
@@ -439,6 +442,8 @@ int pfx_displacement_brushes_dev(pfx_ctx* ctx, void* disp_dev, uint32_t w, uint3
     if (!chunks.empty()) PFX_TRY(pfx_h2d(ctx, (uint8_t*)ctx->d_pts.p + dab_bytes, chunks.data(), chunks.size() * 4u));
     PFX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // `k` / `chunks` are pageable host memory about to go out of scope
     pfx_timer t(ctx, "displacement_brush");
+    ctx->last_dab_launch = chunks.empty() ? 1 : 2;
+    ctx->last_dab_chunks = (int)chunks.size();
     if (!chunks.empty())
         PFX_HIP(ctx, pfxk_disp_brushes_chunked(ctx->stream, (float*)disp_dev, w, h, (const pfxk_disp_dab*)ctx->d_pts.p, n_dabs, bx0, by0, bx1, by1,
                                                (const uint32_t*)((const uint8_t*)ctx->d_pts.p + dab_bytes), (uint32_t)chunks.size()));
@@ -472,7 +477,7 @@ int pfx_mesh_displacement_dev(pfx_ctx* ctx, const float* orig_pts_xy, const floa
     const float *d_orig, *d_def;
     PFX_TRY(upload_points(ctx, orig_pts_xy, deformed_pts_xy, cols, rows, &d_orig, &d_def));
     pfx_timer t(ctx, "mesh_displacement");
-    PFX_HIP(ctx, pfxk_mesh_displacement(ctx->stream, d_orig, d_def, cols, rows, w, h, (float*)disp_dev));
+    PFX_HIP(ctx, pfxk_mesh_displacement(ctx->stream, d_orig, d_def, cols, rows, w, h, (float*)disp_dev, &ctx->last_warp));
     return PFX_OK;
 }
 
@@ -485,7 +490,7 @@ int pfx_warp_mesh_catmull_rom_band_dev(pfx_ctx* ctx, const void* src_dev, const 
     const float *d_orig, *d_def;
     PFX_TRY(upload_points(ctx, orig_pts_xy, deformed_pts_xy, cols, rows, &d_orig, &d_def));
     pfx_timer t(ctx, "warp_mesh");
-    PFX_HIP(ctx, pfxk_warp_mesh(ctx->stream, (const uint8_t*)src_dev, d_orig, d_def, cols, rows, w, band_rows, (uint8_t*)dst_band_dev, first_row, h));
+    PFX_HIP(ctx, pfxk_warp_mesh(ctx->stream, (const uint8_t*)src_dev, d_orig, d_def, cols, rows, w, band_rows, (uint8_t*)dst_band_dev, first_row, h, &ctx->last_warp));
     return PFX_OK;
 }
 
@@ -1054,6 +1059,21 @@ int pfx_chunk_populated(pfx_ctx* ctx, const uint8_t* src, uint32_t w, uint32_t h
     return pfx_unstage(ctx, populated, ctx->d_chunks, nchunks);
 }
 
+int pfx_int_warp_last(pfx_ctx* ctx, int which)
+{
+    if (!ctx) return -1;
+    switch (which) {
+        case 0: return ctx->last_warp.flags;
+        case 1: return ctx->last_warp.flags < 0 ? -1 : (int)ctx->last_warp.gx;
+        case 2: return ctx->last_warp.flags < 0 ? -1 : (int)ctx->last_warp.gy;
+        case 3: return ctx->last_dab_launch;
+        case 4: return ctx->last_dab_chunks;
+        default: return -1;
+    }
+}
+
+int pfx_int_warp_info(int which) { return pfxk_warp_info(which); }
+
 int pfx_tune(pfx_ctx* ctx, const char* key, int value)
 {
     if (!ctx || !key) return PFX_ERR_INVALID;
@@ -1066,6 +1086,7 @@ int pfx_tune(pfx_ctx* ctx, const char* key, int value)
     if (std::strcmp(key, "brush_binning") == 0) { ctx->brush_binning = value != 0; return PFX_OK; }   // 0: long strokes on the bounding-box kernel too
     if (std::strcmp(key, "gauss_fused_exact") == 0) { pfxk_gauss_set_fused_exact(value); return PFX_OK; }  // 0 = the bit-exact Gaussian always through the two kernels
     if (std::strcmp(key, "mesh_xcd") == 0) { pfxk_warp_set_mesh_xcd(value); return PFX_OK; }            // 0 = the fused mesh warp's plain 2-D tile order
+    if (std::strcmp(key, "warp_buf32") == 0) { pfxk_warp_set_buf32(value); return PFX_OK; }            // 0 = both warps' 64-bit-address forms whatever the source's size (the tests' way into them)
     if (std::strcmp(key, "shadow_plane") == 0) { ctx->shadow_plane_blur = value != 0; return PFX_OK; } // drop shadow: blur the alpha plane (1) or the RGBA expansion (0); identical results
     if (std::strcmp(key, "gauss_cols64") == 0) { pfxk_gauss_set_mfma_cols64(value); return PFX_OK; } // matrix-core Gaussian at 8 K blocks: 64-column (1) / 32-column (0) strips, same bits
     if (std::strcmp(key, "chain_fuse_heavy") == 0) { ctx->chain_fuse_heavy = value != 0; return PFX_OK; } // pfx_chain_dev: HSL / vibrance in a Gaussian's store too (measured: no gain)

@@ -57,6 +57,8 @@ struct pfx_ctx {
     int last_median_path = -1, last_box_plan = -1;   // what pfx_stencil_median / _box last launched; pfx_int_stencil_last_path reads them, nothing else does
     int last_resize_path = -1, last_resize_span = -1;   // what pfx_resize_image_dev last launched; pfx_int_resize_last reads them, nothing else does
     pfxk_flatten_plan last_flatten_plan = {-1, -1};     // what pfxk_flatten last launched for this context (path -1: nothing yet); pfx_int_flatten_last_path / _plan read it, nothing else does
+    pfxk_warp_plan last_warp = {-1, 0u, 0u};            // what the context's last mesh / displacement warp or mesh field launched (flags -1: nothing yet); pfx_int_warp_last reads it, nothing else does
+    int last_dab_launch = -1, last_dab_chunks = -1;     // likewise for pfx_displacement_brushes_dev: 0 no launch, 1 the bounding-box launch, 2 the chunk list and its length
     int last_brush_path = -1;                           // what pfx_brush_stamps_ex_dev last did; pfx_int_brush_last reads it, nothing else does
     pfx_devbuf fx_a, fx_b; // effect-bank scratch (crystallize cell table, drop-shadow planes)
     // small parameter buffers
@@ -276,6 +278,15 @@ extern "C" int pfx_int_brush_last(pfx_ctx* ctx);
 int pfx_stencil_tune(pfx_ctx* ctx, const char* key, int value);   // pfx_tune's median_* and box_* keys
 int pfx_stencil_median(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, int radius, const void* mask_dev);   // arguments are the caller's to check
 int pfx_stencil_box(pfx_ctx* ctx, const void* src_dev, void* dst_dev, uint32_t w, uint32_t h, int radius, const void* mask_dev, void* tmp_dev /* NULL: st_tmp */);
+
+// for the tests, what the context's last call into k_warp.hip launched (not in include/pfx.h).  which = 0 the PFXK_WARP_* bits of the last mesh warp, displacement
+// warp or mesh field (1 control points in LDS, 2 PAIR, 4 BUF32, 8 XCD tile order; a launcher sets only the bits it has), 1 / 2 its grid in x / y (the mesh warp's
+// tile grid, also when the XCD order launches it in one dimension); 3 the last pfx_displacement_brushes_dev: 0 no launch (no dab reaches the field), 1 the
+// launch over the dabs' common bounding box, 2 the launch over the 64 x 64 chunks their boxes touch, 4 the chunks of that list (0 for the others); -1 = none yet
+extern "C" int pfx_int_warp_last(pfx_ctx* ctx, int which);
+// the compile-time shape of those kernels: which = 0 MESH_WALK, 1 MESH_WX, 2 MESH_LDS_PTS, 3 WARP_YR, 4 the tile rows from which the mesh warp takes the XCD
+// order, 5 the dabs culled per trip of the dab loop; -1 = unknown `which`
+extern "C" int pfx_int_warp_info(int which);
 
 // for the tests and the profile notes, what the context's last pfx_inpaint_patchmatch[_dev] ran: which = 0 peels, 1 kernel launches (not in include/pfx.h)
 extern "C" int pfx_int_inpaint_last(pfx_ctx* ctx, int which);

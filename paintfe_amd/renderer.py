@@ -1800,6 +1800,17 @@ class GpuRenderer:
         self._check(self._lib.pfx_warp_mesh_catmull_rom_band_dev(self._h, C.c_void_p(src_ptr), _p(o), _p(d), C.c_uint32(cols), C.c_uint32(rows), C.c_uint32(w),
                                                                  C.c_uint32(h), C.c_void_p(dst_band_ptr), C.c_uint32(first_row), C.c_uint32(band_rows)))
 
+    def warp_last(self, which: int) -> int:
+        """what the last call into the warp kernels launched: 0 the bits (1 control points in LDS, 2 PAIR, 4 BUF32, 8 XCD tile order) of the last mesh warp,
+        displacement warp or mesh field, 1 / 2 its grid in x / y, 3 the last displacement_brushes_dev (0 no launch, 1 bounding box, 2 chunk list), 4 its chunks;
+        -1 = none yet (pfx_int_warp_last; for tests)"""
+        return int(self._lib.pfx_int_warp_last(self._h, C.c_int(which)))
+
+    def warp_info(self, which: int) -> int:
+        """0 MESH_WALK, 1 MESH_WX, 2 MESH_LDS_PTS, 3 WARP_YR, 4 the tile rows from which the mesh warp takes the XCD order, 5 the dabs culled per trip
+        (pfx_int_warp_info; for tests)"""
+        return int(self._lib.pfx_int_warp_info(C.c_int(which)))
+
     def selftest_round_pack(self):
         """(mismatches, signalling-NaN mismatches) of the device's round-and-pack against the step-by-step formula over all 2^32 floats"""
         bad, snan = C.c_uint64(0), C.c_uint64(0)
